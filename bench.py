@@ -85,6 +85,25 @@ def make_replay(device, seed, S=S, A=A):
     return buf
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(learner, out_dir):
+    """What the timed learner holds after its last timed update — the networks, their targets, the Adam moments and the
+    update counters (HipLearner.state_dict()) — as ``out_dir/<name>.npy`` (float32; the counters float64), so that two
+    builds run with the same arguments can be compared output for output."""
+    sd = learner.state_dict()
+    arrays = {k: sd[k].numpy().astype(np.float32) for k in ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v")}
+    for name, x in zip(("critic_target", "actor_target"), sd["targets"]):
+        arrays[name] = x.numpy().astype(np.float32)
+    arrays["counters"] = np.asarray(sd["counters"], dtype=np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+
+
 def cpu_baseline(budget_s: float = 14.0):
     """The CPU oracle (oracle/oprl_oracle.py, validated against the reference by
     tests/test_oracle_golden.py) on the same workload: numpy-index sampling from
@@ -547,6 +566,9 @@ def main():
                          "and the process exits (a hung collective must not leave the driver without a line)")
     ap.add_argument("--force-dp", action="store_true",
                     help="use the data-parallel path (RCCL all-reduce) even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed learner's state as DIR/<name>.npy (rank 0; the inputs are "
+                         "seeded, so runs with the same arguments are comparable array for array)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -744,6 +766,9 @@ def measure(args, wd):
     run(K)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        wd.kick("output dump")
+        dump_outputs(learner, args.dump_outputs)      # (before the instrumented pass steps the same learner on)
     wd.kick("checks + instrumented pass")
     if dist is not None:
         dt = all_max(dt)

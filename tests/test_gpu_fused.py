@@ -569,7 +569,7 @@ def test_tqc_step_n_rows_gathered_by_riders_equal_gather_launches(B, monkeypatch
         assert t.equal(getattr(riders, m)._oprl_arena, getattr(launches, m)._oprl_arena), m
 
 
-def test_tqc_wide_dw_equals_small_tiles(monkeypatch):
+def test_tqc_wide_dw_equals_small_tiles(monkeypatch, tmp_path):
     """csrc/dw_wide.hip (64x64 tiles for the 512x512 layers) against k_dw_adam's 16x32 tiles: same
     gradient up to the summation order over the minibatch, same Adam / Polyak / pack epilogue."""
     from oprl_amd.algos.tqc import TQC
@@ -588,7 +588,7 @@ def test_tqc_wide_dw_equals_small_tiles(monkeypatch):
         "t.cuda.synchronize()\n"
         "t.save({m: getattr(a, m)._oprl_arena.cpu() for m in ('actor', 'critic', 'critic_target')}, sys.argv[1])\n"
     ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = "/tmp/oprl_amd_test_dw_small.pt"
+    out = str(tmp_path / "dw_small.pt")
     env = dict(os.environ, OPRL_AMD_NO_RIDE="16")
     subprocess.run([sys.executable, "-c", code, out], check=True, env=env, timeout=300)
     ref = t.load(out)

@@ -48,11 +48,12 @@ def make_shard(rank):
 # update — whose 16 x 64 dW tiles all-reduce their gradients with the other rank's before Adam (dw_tile_x2.h): no
 # all-reduce launches, no apply launches.  Since round 6 the same holds for ("ddpg", 2, "f32") and ("ddpg", 2, "bf16"):
 # k_ddpg_chain<PrecF32 / PrecBF16> with the exchange in its tiles (the worker reports the form the rank ran).
-# world 4 / 3 / 8 (level 1 only: the in-tile exchange needs every rank's tile workgroups resident together, which one GPU
+# world 4 / 3 / 5 (level 1 only: the in-tile exchange needs every rank's tile workgroups resident together, which one GPU
 # offers to two ranks): the window kernels' slot arithmetic, flag counts and rank-ordered sums beyond a pair of ranks.
+# (At most six processes may hold one GPU at once, and this test's own process is one of them: five ranks at most.)
 @pytest.mark.parametrize("algo_name,level,prec,world", [("ddpg", 2, "f32", 2), ("ddpg", 1, "f32", 2), ("sac", 1, "f32", 2), ("td3", 1, "f32", 2),
                                                         ("ddpg", 2, "x2", 2), ("ddpg", 2, "bf16", 2),
-                                                        ("ddpg", 1, "f32", 4), ("sac", 1, "f32", 3), ("ddpg", 1, "f32", 8)])
+                                                        ("ddpg", 1, "f32", 4), ("sac", 1, "f32", 3), ("ddpg", 1, "f32", 5)])
 def test_two_process_p2p_data_parallel_step(algo_name, level, prec, world):
     K, B = 6, 32
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -180,12 +181,14 @@ def test_bench_two_rank_rehearsal_on_one_gpu(prec):
     assert d["config"]["parallelism"] == "dp2" and d["config"]["global_batch"] == 64, d["config"]
 
 
-@pytest.mark.parametrize("n", [4, 8])
+@pytest.mark.parametrize("n", [4])
 def test_bench_many_rank_rehearsal_on_one_gpu(n):
-    """The same rehearsal with 4 and 8 ranks on this GPU — world sizes the driver's scaling run uses.  The in-tile exchange
+    """The same rehearsal with 4 ranks on this GPU — a world size the driver's scaling run uses (8, the other one, cannot
+    share one GPU: at most six processes may hold it at once, and this test's process and the launcher, whose start-up
+    queries the device count, are two of them).  The in-tile exchange
     cannot come up here (every rank's tile workgroups would have to be resident together on ONE chip: its probe fails or
     is dropped, by design), so the line must come from the window kernels (level 1) with bit-identical replicas: rank
-    bookkeeping, window slots, flag counts, the max over ranks and the one line from rank 0 at dp4 / dp8."""
+    bookkeeping, window slots, flag counts, the max over ranks and the one line from rank 0 at dp4."""
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, OPRL_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))

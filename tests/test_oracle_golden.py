@@ -32,9 +32,14 @@ def test_sac_fixed_alpha_matches_reference():
 
 
 def test_sac_tuned_alpha_matches_reference():
+    # The actor's first update holds rows whose hidden pre-activation is within rounding of zero: which side of the ReLU
+    # they land on depends on the host's BLAS kernels (measured: 5e-7 on the host that generated the vectors, 4.0e-4 on
+    # after1.v_actor on an AMD EPYC host, whatever MKL_CBWR says there).  The Adam-moment digests therefore get this
+    # scenario's gate from the GPU tests (tests/test_gpu_algos.py::test_sac_walker_tuned_alpha: 1e-3, plus compare()'s
+    # bound on the share of elements off); outputs and parameters stay at TOL.
     t.set_num_threads(1)
     got = sc.sac_scenario(sc.OracleSAC, "walker", 256, 350, True, 3)
-    print("sac-tune worst", sc.compare(got, sc.load_golden("sac_walker_tune_b256"), TOL))
+    print("sac-tune worst", sc.compare(got, sc.load_golden("sac_walker_tune_b256"), TOL, moment_tol=1e-3))
 
 
 def test_tqc_matches_reference():
