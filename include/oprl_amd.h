@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define OPRL_ABI_VERSION 1
+#define OPRL_ABI_VERSION 2
 #define OPRL_MAX_LAYERS 4   /* linear layers per MLP (TQC critic has 4) */
 #define OPRL_MAX_CRITICS 5  /* TQC n_nets */
 
@@ -246,12 +246,14 @@ int oprl_learner_set_counters(oprl_learner* h, const int64_t in_host[OPRL_N_COUN
 int oprl_learner_check(oprl_learner* h);
 int oprl_learner_clear_error(oprl_learner* h);
 int oprl_learner_debug_expire(oprl_learner* h, int32_t site);
-/* Which launch form an update of batch size B would take right now (tests/test_gpu_forms.py holds the selection —
- * csrc/learner.hip ddpg_args / critic_phase — against a table).  out[12]: [0] 1 fused phase kernels / 0 the generic launch
+/* Which launch form an update of batch size B would take right now (tests/test_gpu_forms.py holds the decision —
+ * csrc/learner.hip fused_form — against a table; the learner is only read).  out[13]: [0] 1 fused phase kernels / 0 the generic launch
  * sequence, [1] lean (tp4.h) passes, [2] form 4 whole updates per launch (k_ddpg_chain) / 3 both merged launches / 2 merged
  * phase 1 / 1 plain phase + dW launches / 0, [3] updates per chain launch, [4] wide bits (1 role A, 2 the critic pass on
  * clusters of eight), [5] cluster size of the other roles, [6] twin_split, [7] p2_pair, [8] arithmetic 0 exact fp32 /
- * 1 bf16 / 2 x2, [9] XCD-local cluster exchanges, [10] demoted to the shared-chip forms, [11] 0.  Reference: none (the
+ * 1 bf16 / 2 x2, [9] XCD-local cluster exchanges, [10] demoted to the shared-chip forms, [11] gradient-exporting
+ * learners: the form (as [2]) of a data-parallel update whose exchange runs inside the dW tiles, others 0, [12] rt2 (1 phase
+ * 1's B roles on two row tiles per cluster, 2 ... and SAC's role A carries role C's pass).  Reference: none (the
  * reference has one path, autograd). */
 int oprl_learner_debug_form(oprl_learner* h, int32_t B, int32_t* out);
 /* Key of the learner's device-side noise streams (TD3 target smoothing, the SAC / TQC

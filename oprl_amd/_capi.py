@@ -10,7 +10,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-OPRL_ABI_VERSION = 1
+OPRL_ABI_VERSION = 2
 OPRL_MAX_LAYERS = 4
 OPRL_MAX_CRITICS = 5
 ALGO = {"ddpg": 0, "td3": 1, "sac": 2, "tqc": 3}

@@ -353,12 +353,12 @@ class HipLearner:
         _capi.check(self.lib.oprl_learner_clear_error(self.handle), "oprl_learner_clear_error")
 
     DEBUG_FORM_FIELDS = ("fused", "lean", "form", "updates_per_chain_launch", "wide", "nc", "twin_split", "p2_pair", "arith",
-                         "xcd_local", "shared_chip", "dp_inline_form")
+                         "xcd_local", "shared_chip", "dp_inline_form", "rt2")
 
     def debug_form(self, batch_size: int) -> dict[str, int]:
         """Which launch form this learner takes for `batch_size` (include/oprl_amd.h, oprl_learner_debug_form): the
         decision tests/golden/launch_forms.json pins, under that table's field names."""
-        out = (C.c_int32 * 12)()
+        out = (C.c_int32 * len(self.DEBUG_FORM_FIELDS))()
         _capi.check(self.lib.oprl_learner_debug_form(self.handle, int(batch_size), out), "oprl_learner_debug_form")
         return dict(zip(self.DEBUG_FORM_FIELDS, (int(x) for x in out)))
 

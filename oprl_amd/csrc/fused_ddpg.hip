@@ -1948,9 +1948,10 @@ hipError_t launch_ddpg_phase2_group(const DdpgArgs& a0, const DdpgArgs* batch_de
 static bool lean_ok(const DdpgArgs& a) { return fused_ddpg_is_lean(a); }
 // (the twin-critic variant, TD3, exists in the lean form only: learner.hip falls back to the
 // generic launch sequence when this returns false)
-bool fused_ddpg_is_lean(const DdpgArgs& a) {
-  return a.nc == 4 && !a.no_lean && tp4_shape_ok(256, a.S + a.A, 1) && tp4_shape_ok(256, a.S, a.sac ? 2 * a.A : a.A);
+bool fused_ddpg_is_lean(int nc, int no_lean, int S, int A, bool sac) {
+  return nc == 4 && !no_lean && tp4_shape_ok(256, S + A, 1) && tp4_shape_ok(256, S, sac ? 2 * A : A);
 }
+bool fused_ddpg_is_lean(const DdpgArgs& a) { return fused_ddpg_is_lean(a.nc, a.no_lean, a.S, a.A, a.sac != 0); }
 
 // phase 1 with the critic's dW + Adam tiles as extra grid rows (DdpgArgs::merged bit 0; `d` = fill_dw_kargs of
 // that launch with its gate filled in)

@@ -398,11 +398,10 @@ hipError_t launch_dw_adam(const DwArgs& a0, hipStream_t st) {
   if (a0.n_items < 1 || a0.n_items > kDwMaxItems) return hipErrorInvalidValue;
   static const PrefetchJob no_prefetch = [] { PrefetchJob j; memset((void*)&j, 0, sizeof j); j.z0 = -1; return j; }();
   // wide layers (TQC's 512x512) go to the 64x64-tile kernel (csrc/dw_wide.hip), the rest stay here
-  static const bool no_wide = [] { const char* e = getenv("OPRL_AMD_NO_RIDE"); return e != nullptr && (atoi(e) & 16) != 0; }();   // (bit 16: learner.hip)
   DwItem rest[kDwMaxItems], wide[kDwMaxItems];
   int n_rest = 0, n_wide = 0;
   for (int j = 0; j < a0.n_items; ++j) {
-    if (!no_wide && n_wide < 10 && dw_wide_item_ok(a0.items[j], a0)) {
+    if (!a0.no_wide && n_wide < 10 && dw_wide_item_ok(a0.items[j], a0)) {
       wide[n_wide] = a0.items[j];
       // (16-bit learners: nothing of the update reads these layers' fp32 packs — a third of the launch's stores;
       // whoever does read them later rebuilds them first: fresh32, learner.hip)

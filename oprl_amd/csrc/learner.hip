@@ -375,7 +375,8 @@ int launch(const MlpArgs& a0, int width, hipStream_t st) {
   return OPRL_OK;
 }
 
-hipError_t launch_dw_prof(const DwArgs& a, hipStream_t st) {
+hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st) {
+  if (h != nullptr) a.no_wide = h->sw.no_wide_dw ? 1 : 0;
   prof_begin(1, st);
   hipError_t e = launch_dw_adam(a, st);
   prof_end(st);
@@ -413,7 +414,7 @@ int for_each_net(oprl_learner* h, int n, hipStream_t st, F&& launch_j) {
     h->pair_n = 0;
     return OPRL_OK;
   }
-  if (n > 2 && n <= kMaxMulti && !h->no_multi) {
+  if (n > 2 && n <= kMaxMulti) {
     // equal nets on the same slices (TQC's quantile critics): one launch, grid (slices, nets)
     h->multi_collect = true;
     h->multi_n = 0;
@@ -428,7 +429,7 @@ int for_each_net(oprl_learner* h, int n, hipStream_t st, F&& launch_j) {
     // wide nets go layer by layer over the whole chip (csrc/layerwise.hip); launches that keep no
     // activations (target nets, the actor phase's critics) borrow the nets' dW exchange buffers,
     // which nobody reads until the next storing launch overwrites them
-    if (same && !h->no_layerwise && h->multi_width == 512 && h->multi_n <= h->nc) {
+    if (same && !h->sw.no_layerwise && h->multi_width == 512 && h->multi_n <= h->nc) {
       for (int k = 0; k < h->multi_n; ++k) {
         MlpArgs& a = h->multi_args[k];
         const NetWs& ws = h->ws_critic[k];
@@ -441,7 +442,7 @@ int for_each_net(oprl_learner* h, int n, hipStream_t st, F&& launch_j) {
           if (a.dYg[l] == nullptr) a.dYg[l] = ws.dY[l];
       }
     }
-    if (same && !h->no_layerwise && mlp_layerwise_ok(h->multi_args, h->multi_n, h->multi_width)) {
+    if (same && !h->sw.no_layerwise && mlp_layerwise_ok(h->multi_args, h->multi_n, h->multi_width)) {
       // bf16 learners: the hidden layers (all but the first and the last) through their bf16 packs
       bool lw16 = h->bf16 || h->x2;
       for (int k = 0; k < h->multi_n; ++k) {
@@ -578,8 +579,115 @@ int chain_rows(const oprl_learner* h, int B) {
   return 16 + chain_tile_rows(mt, sl);
 }
 
+// The launch form of a fused update of batch B, read off the learner (dp_inline: this update's gradient exchange runs
+// inside the dW tiles — debug_form also asks it of a learner not set up for that).  Each condition is named once, in order.
+FusedForm fused_form(const oprl_learner* h, int B, bool dp_inline) {
+  const oprl_learner_config& c = h->cfg;
+  const Switches& sw = h->sw;
+  const int slices = (B + kR - 1) / kR;
+  const bool sac = c.algo == OPRL_SAC;
+  FusedForm f;
+  f.nc = h->nc_cluster(B);
+  f.xnc = h->xnc;
+  f.lean = fused_ddpg_is_lean(f.nc, sw.no_lean, h->S, h->A, sac);
+  f.x2 = h->x2 && f.lean;       // the PrecX2 instances: every net through its packs of two fp16 planes
+  f.bf16 = h->bf16 && f.lean;   // the PrecBF16 instances of the (lean) phase kernels: every net through its bf16 packs
+  const bool side_by_side = !sw.no_side_by_side && !h->group_member;
+  // role A and the role-C cluster wait for each other: only with all four roles of a slice resident
+  f.twin_split = (h->nc == 2 && f.nc == 4 && !sw.no_lean && side_by_side && (2 + h->nc) * 4 * slices <= h->n_cus) ? 1 : 0;
+  // (SAC) both phase-2 clusters of a slice must be co-resident: cluster 0 waits for cluster 1's result
+  f.p2_pair = (sac && h->ncl == 4 && 2 * 4 * slices <= h->n_cus && side_by_side) ? 1 : 0;
+  if (!f.lean) return f;
+  const bool x2_tiles = f.x2 && fused_x2_tiles();   // the 16 x 64 PrecX2 tiles
+  // (one update's workgroups wait for each other in the whole-update launch: all must fit the chip)
+  const bool fits = chain_rows(h, B) * slices <= h->n_cus;
+
+  // clusters of EIGHT for role A (DDPG: the roles then fill the chip exactly at B = 256) and for phase 2's
+  // critic pass (DDPG / TD3), while the launch still fits the chip; exact-fp32 lean passes only
+  // A property of the LEARNER (oprl_learner_set_cluster(h, 8) = the default / (h, 4) = never), not of the
+  // moment: results differ in the last bits between cluster sizes (summation order of the exchanges).  A wide
+  // launch wants the whole chip; FOUR such launches each cut in the middle of role A (64 members resident, 64
+  // waiting for a CU) fill it with workgroups that spin for each other — measured with eight learners on eight
+  // streams: every wait ran into its bound and was reported.  Learners that share a GPU with more than two
+  // others (packed seeds on streams, one process per seed on one GPU) turn it off: set_cluster(h, 4) or
+  // OPRL_AMD_NO_WIDE=1; up to three cannot dead-lock (the B roles always finish and free their CUs).
+  const bool wide_ok = h->xnc >= 8 && !h->shared_chip && !sw.no_wide && !sac && (!f.bf16 || h->bchain) && h->A <= 8;   // (narrow exchanges)
+  const bool wide_a = wide_ok && h->nc == 1 && (f.nc + 8 + f.nc) * slices <= h->n_cus;
+  const bool wide_p2 = wide_ok && (8 + 1) * slices <= h->n_cus;
+
+  // the whole update per launch with the exact-fp32 tiles (learners with mirrored packs: k_ddpg_chain<PrecF32>) or the
+  // bf16 ones (k_ddpg_chain<PrecBF16>: learner_internal.h bchain), when that form is possible at all (a gradient-exporting
+  // learner takes it only when its tiles exchange the gradients themselves: dp_inline)
+  const bool whole_ok = fused_x2_tiles() && !sw.no_whole && !sw.no_merge && !sw.no_merge2 && !h->shared_chip &&
+                        (!c.export_grads || dp_inline) && B <= 256 && wide_a && wide_p2 && h->chain_flags != nullptr &&
+                        h->du_granules != nullptr && fits;
+  const bool whole_f32 = whole_ok && h->fchain && !f.x2 && !f.bf16;
+  const bool whole_bf16 = whole_ok && h->bchain && f.bf16;
+  const bool own_tiles = x2_tiles || whole_f32 || whole_bf16;     // tiles that take role A on eight beside them
+
+  // (dp_inline: the gradient exchange inside the dW tiles — the 16 x 32 tiles of k_dw_adam<true> as launches of their own,
+  // or the 16 x 64 tiles of the merged / whole-update launches themselves: dw_tile_x2.h — PrecX2 learners in both forms,
+  // exact-fp32 and bf16 learners in the whole-update form, round 6)
+  const bool inline_tiles = dp_inline && fused_x2_tiles() && h->nc == 1 && (f.x2 || whole_f32 || whole_bf16);
+  const bool dp_ok = !dp_inline || inline_tiles;
+
+  // merged phase 1 (DDPG, lean passes, one 256-row chunk, this rank's own Adam step): the critic's dW tiles ride on phase
+  // 1 — whose role A then stays on a cluster of four unless the tiles are the 16 x 64 ones: 64 CUs must be free for tile
+  // workgroups from the start (a gradient-exporting learner — data parallel over RCCL — merges only with the PrecX2
+  // tiles, which know how to leave dW in the gradient arena instead of running Adam: four launches per data-parallel
+  // update instead of six).  TD3: both critics' tiles ride — roles A | B1 | B2 | C are the whole chip at B = 256, the
+  // 2 x 84 / 2 x 152 tiles take the compute units the roles leave; this rank's own Adam step only
+  const bool merge_twin = h->nc == 2 && c.algo == OPRL_TD3 && !c.export_grads && !dp_inline && !sw.no_merge_twin;
+  const bool xport_ok = !c.export_grads || x2_tiles || inline_tiles;
+  const bool merged1 = !sw.no_merge && !h->shared_chip && (h->nc == 1 || merge_twin) && !sac && B <= 256 && xport_ok && dp_ok;
+  // merged phase 2: the ACTOR's tiles on phase 2 (DDPG / TD3: the tanh head, action_dim <= kDuLd): the tiles form their
+  // dY from du, the first layer's comes from one more backward step of the critic pass's members (csrc/fused_ddpg.hip);
+  // the pass on clusters of eight.  PrecX2 learners, or inside the whole form: with the exact-fp32 tiles on its own the
+  // merged form measured no faster than the two launches (34.9 vs 34.7 us)
+  const bool merged2 = !sw.no_merge2 && !h->shared_chip && own_tiles && h->du_granules != nullptr && !sac && B <= 256 &&
+                       dp_ok && c.actor.theta_target != nullptr && wide_p2;
+
+  // the whole update as ONE launch: both merged forms, role A and the critic pass on eight, the 16 x 64 tiles, and
+  // everything the roles hand to each other in uncached memory
+  f.whole = (!sw.no_whole && (!c.export_grads || inline_tiles) && own_tiles && h->nc == 1 && merged1 && merged2 &&
+             wide_a && wide_p2 && h->uc_pool && (h->uc_base != nullptr || h->bchain) && h->w_flags != nullptr &&
+             h->chain_flags != nullptr && fits) ? 1 : 0;
+  const bool merged2_on = merged2 && (f.x2 || f.whole);           // (exact fp32: no merged phase 2 outside the whole form)
+  // (an exchanging rank outside PrecX2 has the in-tile exchange in the whole-update form only: whatever kept that form
+  // away, its merged phase launch — 16 x 32 tiles that exchange nothing — must not run either)
+  const bool merges = !dp_inline || f.x2 || f.whole;
+  f.merged = merges ? ((merged1 ? 1 : 0) | (merged2_on ? 2 : 0)) : 0;
+  // (outside the whole form a bf16 learner's passes stay on clusters of four, as before; role A stays on four beside
+  // tiles other than the 16 x 64 ones, and beside the exact-fp32 tiles outside the whole form)
+  const bool wide_on = !h->bchain || whole_bf16;
+  const bool a_on_four = (merged1 && !own_tiles) || (merged2 && !merged2_on);
+  f.wide = wide_on ? ((wide_a && !a_on_four ? 1 : 0) | (wide_p2 ? 2 : 0)) : 0;
+  f.chain_max = f.whole ? sw.chain_max : 1;
+
+  // Over-subscribed plain phase-1 launches (B >= 512: the roles' clusters need more compute units than the chip has, the
+  // launch is several dispatch rounds): the B roles carry TWO row tiles per cluster — half the workgroups, one fetch of the
+  // critic's fragments per 32 rows (tp4.h tp4_scalar_fb2; bit-identical to the one-tile form).  Slices a multiple of 16: a
+  // cluster's members then sit on one XCD (fused_ddpg.hip role_b2).
+  // (twin critics only — TD3, SAC: their two B roles then share the first dispatch round; measured, r06-6: SAC humanoid
+  // B = 1024 - 3.7 us per update in every mode, TD3 B = 512 - 4.7, SAC B = 512 - 5; a single critic's one B role on half the
+  // workgroups only lengthens the wait of role A behind it: DDPG B = 512 + 1.8 us, B = 1024 + 2.4 .. 4)
+  // (!prefetch_p1 never decides: step_n sets it only where `merged` != 0, and it sets it FROM `merged` — so nothing
+  // above may read prefetch_p1)
+  f.rt2 = (sw.no_rt2 != 1 && h->nc == 2 && f.merged == 0 && (f.wide & 1) == 0 && f.nc == 4 && (slices & 15) == 0 &&
+           (2 + h->nc) * 4 * slices > h->n_cus && !h->prefetch_p1) ? 1 : 0;
+  // SAC there: role A's first pass — the online actor on s' — also carries role C's pass, the same actor on s (tp4_forward2;
+  // bit-identical): role C's dispatch round is not launched (r06-13; OPRL_AMD_NO_RT2=2 keeps role C)
+  // (where role A alone fills the chip — humanoid B = 1024: -3.1 us x2, -2.1 f32 / bf16 per update; at B = 512 role C ran
+  // beside role A's second half and the merged pass is 3.5 us SLOWER: a tile's pass is bound by instruction issue, not by
+  // its fragments, so the second tile costs a pass's 6.4 us, not the 2 - 3 us the B roles' shared fragments suggested)
+  if (f.rt2 == 1 && sac && !f.twin_split && sw.no_rt2 == 0 && 4 * slices >= h->n_cus) f.rt2 = 2;
+  return f;
+}
+
+// The kernel's arguments of a fused update of batch B: the form (fused_form) and the pointers and scalars it needs.
 DdpgArgs ddpg_args(oprl_learner* h, int B) {
   const oprl_learner_config& c = h->cfg;
+  const FusedForm f = fused_form(h, B, h->dp_inline);
   DdpgArgs a;
   memset(&a, 0, sizeof a);
   a.actor = net_view(eff(h, c.actor), false);
@@ -610,13 +718,10 @@ DdpgArgs ddpg_args(oprl_learner* h, int B) {
     a.alpha_const = (float)c.hp.alpha_init;
     a.raw = h->raw;
     a.logp = h->logp;
-    // both phase-2 clusters of a slice must be co-resident: cluster 0 waits for cluster 1's result
-    a.p2_pair = (h->ncl == 4 && 2 * 4 * ((B + kR - 1) / kR) <= h->n_cus && !h->no_p2_pair) ? 1 : 0;
   }
   a.B = B; a.S = h->S; a.A = h->A;
   a.src = h->src;
   a.next = h->next_src;
-  a.prefetch_next = 0;
   a.gamma = (float)c.hp.gamma;
   a.inv_B = 1.0f / (float)B;
   for (int l = 0; l < kMaxLayers; ++l) {
@@ -630,15 +735,9 @@ DdpgArgs ddpg_args(oprl_learner* h, int B) {
   a.y_granules = h->y_granules; a.gran_stride = h->Bmax;
   a.gate_flags = h->y_granules + (size_t)3 * h->Bmax;   // 256 flag granules behind the TD / q granules
   a.seed2_granules = h->y_granules + (size_t)3 * h->Bmax + 256;
-  a.merged = 0;
   a.epoch = h->epoch;
-  a.trace = nullptr;
-  a.nc = h->nc_cluster(B);
-  a.no_lean = h->no_lean;
+  a.no_lean = h->sw.no_lean;
   a.xcd_local = h->xcd_local ? 1 : 0;
-  // role A and the role-C cluster wait for each other: only with all four roles of a slice resident
-  a.twin_split = (h->nc == 2 && a.nc == 4 && !h->no_lean && !h->no_twin_split &&
-                  (2 + h->nc) * 4 * ((B + kR - 1) / kR) <= h->n_cus) ? 1 : 0;
   a.xbuf = h->xbuf;
   a.cdY0_stride = h->ws_critic[0].dY0_stride;
   a.adY0_stride = h->ws_actor.dY0_stride;
@@ -646,121 +745,30 @@ DdpgArgs ddpg_args(oprl_learner* h, int B) {
   a.err = h->err_dev;
   a.debug_expire = h->debug_expire;
   a.w3_src = c.actor.theta + w_off(c.actor, c.actor.n_layers - 1);
-  if (h->x2 && fused_ddpg_is_lean(a)) {     // the PrecX2 instances: every net through its packs of two fp16 planes
-    a.x2 = 1;
-    a.actor = net_view16(c.actor, false, h->pack16[0], 2);
-    if (c.actor.theta_target) a.actor_t = net_view16(c.actor, true, h->pack16_t[0], 2);
-    a.critic = net_view16(c.critics[0], false, h->pack16[1], 2);
-    a.critic_t = net_view16(c.critics[0], true, h->pack16_t[1], 2);
+  a.nc = f.nc; a.xnc = f.xnc; a.x2 = f.x2; a.bf16 = f.bf16; a.wide = f.wide; a.twin_split = f.twin_split;
+  a.p2_pair = f.p2_pair; a.merged = f.merged; a.whole = f.whole; a.rt2 = f.rt2;
+  if (f.x2 || f.bf16) {     // every net through its 16-bit packs (x2: two fp16 planes per block)
+    const int pl = f.x2 ? 2 : 1;
+    a.actor = net_view16(c.actor, false, h->pack16[0], pl);
+    if (c.actor.theta_target) a.actor_t = net_view16(c.actor, true, h->pack16_t[0], pl);
+    a.critic = net_view16(c.critics[0], false, h->pack16[1], pl);
+    a.critic_t = net_view16(c.critics[0], true, h->pack16_t[1], pl);
     if (h->nc == 2) {
-      a.critic2 = net_view16(c.critics[1], false, h->pack16[2], 2);
-      a.critic2_t = net_view16(c.critics[1], true, h->pack16_t[2], 2);
+      a.critic2 = net_view16(c.critics[1], false, h->pack16[2], pl);
+      a.critic2_t = net_view16(c.critics[1], true, h->pack16_t[2], pl);
     }
   }
-  if (h->bf16 && fused_ddpg_is_lean(a)) {   // the PrecBF16 instances of the (lean) phase kernels: every net through its bf16 packs
-    a.bf16 = 1;
-    a.actor = net_view16(c.actor, false, h->pack16[0]);
-    if (c.actor.theta_target) a.actor_t = net_view16(c.actor, true, h->pack16_t[0]);
-    a.critic = net_view16(c.critics[0], false, h->pack16[1]);
-    a.critic_t = net_view16(c.critics[0], true, h->pack16_t[1]);
-    if (h->nc == 2) {
-      a.critic2 = net_view16(c.critics[1], false, h->pack16[2]);
-      a.critic2_t = net_view16(c.critics[1], true, h->pack16_t[2]);
-    }
-  }
-  // clusters of EIGHT for role A (DDPG: the roles then fill the chip exactly at B = 256) and for phase 2's
-  // critic pass (DDPG / TD3), while the launch still fits the chip; exact-fp32 lean passes only
-  // A property of the LEARNER (oprl_learner_set_cluster(h, 8) = the default / (h, 4) = never), not of the
-  // moment: results differ in the last bits between cluster sizes (summation order of the exchanges).  A wide
-  // launch wants the whole chip; FOUR such launches each cut in the middle of role A (64 members resident, 64
-  // waiting for a CU) fill it with workgroups that spin for each other — measured with eight learners on eight
-  // streams: every wait ran into its bound and was reported.  Learners that share a GPU with more than two
-  // others (packed seeds on streams, one process per seed on one GPU) turn it off: set_cluster(h, 4) or
-  // OPRL_AMD_NO_WIDE=1; up to three cannot dead-lock (the B roles always finish and free their CUs).
-  a.xnc = h->xnc;
-  a.wide = 0;
-  if (h->xnc >= 8 && !h->no_wide && !a.sac && (!a.bf16 || h->bchain) && a.A <= 8 && fused_ddpg_is_lean(a)) {   // (narrow exchanges: <= 8 action columns)
-    const int slices = (B + kR - 1) / kR;
-    if (h->nc == 1 && (a.nc + 8 + a.nc) * slices <= h->n_cus) a.wide |= 1;
-    if ((8 + 1) * slices <= h->n_cus) a.wide |= 2;
-  }
-  // merged launches (DDPG, lean passes, one 256-row chunk, this rank's own Adam step): the critic's dW tiles ride
-  // on phase 1 — whose role A then stays on a cluster of four: 64 CUs must be free for tile workgroups from the start
-  // (a gradient-exporting learner — data parallel over RCCL — merges only with the PrecX2 tiles, which know how to leave
-  // dW in the gradient arena instead of running Adam: four launches per data-parallel update instead of six)
-  // exact-fp32 learners with mirrored packs: the whole update as k_ddpg_chain<PrecF32> when that form is possible at all
-  // (there is no merged phase 2 with the fp32 tiles on its own: with the whole form out of reach the two bits below stay
-  // what they were — merged phase 1 with role A on four, phase 2 and the actor's dW as launches)
-  // (a gradient-exporting learner takes the whole form only when its tiles exchange the gradients themselves: dp_inline)
-  const bool dp_whole_ok = !h->cfg.export_grads || h->dp_inline;
-  const bool whole_f32 = h->fchain && fused_x2_tiles() && !a.x2 && !a.bf16 && !h->no_whole && !h->no_merge && !h->no_merge2 && !h->shared_chip &&
-                         dp_whole_ok && B <= 256 && fused_ddpg_is_lean(a) && (a.wide & 3) == 3 && h->chain_flags != nullptr && h->du_granules != nullptr &&
-                         chain_rows(h, B) * ((B + kR - 1) / kR) <= h->n_cus;
-  // ... and bf16 learners (k_ddpg_chain<PrecBF16>: learner_internal.h bchain)
-  const bool whole_bf16 = h->bchain && fused_x2_tiles() && a.bf16 && !h->no_whole && !h->no_merge && !h->no_merge2 && !h->shared_chip &&
-                          dp_whole_ok && B <= 256 && fused_ddpg_is_lean(a) && (a.wide & 3) == 3 && h->chain_flags != nullptr && h->du_granules != nullptr &&
-                          chain_rows(h, B) * ((B + kR - 1) / kR) <= h->n_cus;
-  // (dp_inline: the gradient exchange inside the dW tiles — the 16 x 32 tiles of k_dw_adam<true> as launches of their own,
-  // or the 16 x 64 tiles of the merged / whole-update launches themselves: dw_tile_x2.h — PrecX2 learners in both forms,
-  // exact-fp32 and bf16 learners in the whole-update form, round 6)
-  const bool inline_tiles = h->dp_inline && fused_x2_tiles() && h->nc == 1 && (a.x2 || whole_f32 || whole_bf16);
-  const bool xport_ok = !h->cfg.export_grads || (a.x2 && fused_x2_tiles()) || inline_tiles;
-  // (TD3: both critics' tiles ride — roles A | B1 | B2 | C are the whole chip at B = 256, the 2 x 84 / 2 x 152 tiles take the
-  // compute units the roles leave; this rank's own Adam step only)
-  const bool merge_twin = h->nc == 2 && c.algo == OPRL_TD3 && !h->cfg.export_grads && !h->dp_inline && !h->no_merge_twin;
-  if (h->bchain && !whole_bf16) a.wide = 0;      // (outside the whole form a bf16 learner's passes stay on clusters of four, as before)
-  if (whole_bf16) a.actor_pb1_f32 = net_view(c.actor, false).pb[1];
-  if (!h->no_merge && !h->shared_chip && (h->nc == 1 || merge_twin) && !a.sac && B <= 256 && xport_ok && (!h->dp_inline || inline_tiles) && fused_ddpg_is_lean(a)) {
-    a.merged |= 1;
-    if (!(a.x2 && fused_x2_tiles()) && !whole_f32 && !whole_bf16) a.wide &= ~1;     // (the 84 16 x 64 tiles of a PrecX2 learner get along with role A on eight)
-  }
-  // ... and the ACTOR's tiles on phase 2 (DDPG / TD3: the tanh head, action_dim <= kDuLd): the tiles form their dY from
-  // du, the first layer's comes from one more backward step of the critic pass's members (csrc/fused_ddpg.hip).
-  // PrecX2 learners only, the pass on clusters of eight: with the exact-fp32 tiles the merged form measured no faster
-  // than the two launches (34.9 vs 34.7 us)
-  if (!h->no_merge2 && !h->shared_chip && ((a.x2 && fused_x2_tiles()) || whole_f32 || whole_bf16) && h->du_granules != nullptr && !a.sac && B <= 256 && (!h->dp_inline || inline_tiles) &&
-      fused_ddpg_is_lean(a) && c.actor.theta_target != nullptr && (a.wide & 2) != 0) {
-    a.merged |= 2;
+  if (f.whole && f.bf16) a.actor_pb1_f32 = net_view(c.actor, false).pb[1];
+  if ((f.merged & 2) != 0) {
     a.du_granules = h->du_granules;
     a.g1_granules = h->g1_granules;
     a.w3_snap = h->w3_snap;
   }
-  // the whole update as ONE launch (k_ddpg_update): both merged forms, role A and the critic pass on eight, the 16 x 64
-  // tiles, and everything the roles hand to each other in uncached memory
-  if (!h->no_whole && (!h->cfg.export_grads || inline_tiles) && ((a.x2 && fused_x2_tiles()) || whole_f32 || whole_bf16) && h->nc == 1 && (a.merged & 3) == 3 && (a.wide & 3) == 3 && h->uc_pool &&
-      (h->uc_base != nullptr || h->bchain) && h->w_flags != nullptr && h->chain_flags != nullptr &&
-      chain_rows(h, B) * ((B + kR - 1) / kR) <= h->n_cus) {      // (one update's workgroups wait for each other: all must fit the chip)
-    a.whole = 1;
+  if (f.whole) {
     a.w_flags = h->w_flags;
     a.ct_done = h->w_flags + 64;
     for (int l = 0; l < c.critics[0].n_layers; ++l) a.critic_b16[l] = h->critic_b16 + 256 * l;
   }
-  if (!a.x2 && (a.merged & 2) != 0 && !a.whole) {     // (exact fp32: no merged phase 2 outside the whole form)
-    a.merged &= ~2;
-    a.wide &= ~1;
-    a.du_granules = nullptr; a.g1_granules = nullptr; a.w3_snap = nullptr;
-  }
-  // Over-subscribed plain phase-1 launches (B >= 512: the roles' clusters need more compute units than the chip has, the
-  // launch is several dispatch rounds): the B roles carry TWO row tiles per cluster — half the workgroups, one fetch of the
-  // critic's fragments per 32 rows (tp4.h tp4_scalar_fb2; bit-identical to the one-tile form).  Slices a multiple of 16: a
-  // cluster's members then sit on one XCD (fused_ddpg.hip role_b2).
-  {
-    const int slices = (B + kR - 1) / kR;
-    // (twin critics only — TD3, SAC: their two B roles then share the first dispatch round; measured, r06-6: SAC humanoid
-    // B = 1024 - 3.7 us per update in every mode, TD3 B = 512 - 4.7, SAC B = 512 - 5; a single critic's one B role on half the
-    // workgroups only lengthens the wait of role A behind it: DDPG B = 512 + 1.8 us, B = 1024 + 2.4 .. 4)
-    a.rt2 = (h->no_rt2 != 1 && h->nc == 2 && a.merged == 0 && (a.wide & 1) == 0 && a.nc == 4 && fused_ddpg_is_lean(a) && (slices & 15) == 0 &&
-             (2 + h->nc) * 4 * slices > h->n_cus && !a.prefetch_p1) ? 1 : 0;
-    // SAC there: role A's first pass — the online actor on s' — also carries role C's pass, the same actor on s (tp4_forward2;
-    // bit-identical): role C's dispatch round is not launched (r06-13; OPRL_AMD_NO_RT2=2 keeps role C)
-    // (where role A alone fills the chip — humanoid B = 1024: -3.1 us x2, -2.1 f32 / bf16 per update; at B = 512 role C ran
-    // beside role A's second half and the merged pass is 3.5 us SLOWER: a tile's pass is bound by instruction issue, not by
-    // its fragments, so the second tile costs a pass's 6.4 us, not the 2 - 3 us the B roles' shared fragments suggested)
-    if (a.rt2 == 1 && a.sac && !a.twin_split && a.do_actor && h->no_rt2 == 0 && 4 * slices >= h->n_cus) a.rt2 = 2;
-  }
-  // (an exchanging rank outside PrecX2 has the in-tile exchange in the whole-update form only: whatever kept that form
-  // away, its merged phase launch — 16 x 32 tiles that exchange nothing — must not run either)
-  if (h->dp_inline && !a.x2 && !a.whole) a.merged = 0;
   return a;
 }
 
@@ -769,7 +777,7 @@ DdpgArgs ddpg_args(oprl_learner* h, int B) {
 bool use_fused(oprl_learner* h, int B) {
   if (!h->fused) return false;
   if (h->cfg.algo == OPRL_DDPG) return true;
-  return fused_ddpg_is_lean(ddpg_args(h, B));
+  return fused_form(h, B, h->dp_inline).lean;
 }
 
 // The temperature step of this update as a job for the actor's dW launch (one more workgroup), when nothing
@@ -812,7 +820,7 @@ DwArgs dw_build(oprl_learner* h, bool critic, int B, bool polyak, bool with_alph
   dw.apply_only = 0;
   // the lean phase 1 leaves unit-seed dz rows (tp4_scalar_fb): each critic's TD-error seed, dY of
   // its output layer, is applied per row (DwItem::rs)
-  const bool lean = fused && fused_ddpg_is_lean(ddpg_args(h, B));
+  const bool lean = fused && fused_form(h, B, h->dp_inline).lean;
   dw.use_row_scale = (critic && lean) ? 1 : 0;
   dw.dy_tiled = (lean && dw.n_part > 1) ? 1 : 0;      // the lean passes leave tile-major dz1 partials
   if (h->x2 && lean && !c.export_grads) {             // the PrecX2 kernels read the fp16 packs only (fresh32)
@@ -841,7 +849,7 @@ int dw_step(oprl_learner* h, bool critic, int B, bool polyak, hipStream_t st, bo
     dw.ad.do_adam = 1;
     dw.ad.grad_scale = 1.0f / (float)P.world;
   }
-  HIPC(launch_dw_prof(dw, st));
+  HIPC(launch_dw_prof(h, dw, st));
   return OPRL_OK;
 }
 
@@ -879,6 +887,7 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
         HIPC(hipMemsetAsync(h->chain_flags, 0, (192 + 192 + 64 + 128 + 1024) * sizeof(unsigned long long), st));
       }
     }
+    const FusedForm form = fused_form(h, B, h->dp_inline);
     DdpgArgs fa = ddpg_args(h, B);
     if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));     // (a batch the lean kernels do not take: fp32 packs)
     fa.noise = noise0;
@@ -889,9 +898,9 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
     if (h->trace != nullptr) fa.trace = h->trace;   // roles use slots 0 .. 1 + n_critics
     h->whole_done = false;
-    if (fa.whole && B <= 256) {
-      // the whole update as ONE launch (k_ddpg_update): phase 1's roles, the critic's tiles, role U + the actor's
-      // tiles, the critic pass
+    if (form.whole) {
+      // the whole update as k_ddpg_chain launches: phase 1's roles, the critic's tiles, role U + the actor's tiles, the
+      // critic pass, of U updates (step_n: chain_u) per launch
       RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag2));
       if (h->trace != nullptr && c.algo == OPRL_DDPG) fa.trace2 = h->trace + (size_t)3 * 64 * kTraceStamps * 2;   // slot 3
       fa.prefetch_next = 0;
@@ -938,9 +947,9 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
       // (every tile must find a role-B / role-C workgroup to be the continuation of: 8 per slice)
       const int max_tiles = kc.tile_end[kDwFusedItems - 1] > ka.tile_end[kDwFusedItems - 1] ? kc.tile_end[kDwFusedItems - 1] : ka.tile_end[kDwFusedItems - 1];
       const int t_rows = chain_tile_rows(max_tiles, slices);
-      // (one update's workgroups — 16 role rows per slice + the tile-only rows — wait for each other: all must fit the chip)
-      const bool chain_fits = (16 + t_rows) * slices <= h->n_cus;
-      const int U = (h->no_chain || h->chain_flags == nullptr || !chain_fits) ? 1 : h->chain_u;
+      // (the form's fit test counted the same 16 x 64 tiles from the learner's item table: chain_rows)
+      if (16 + t_rows != chain_rows(h, B)) { undo(); set_err("internal: whole update of %d grid rows, the form counted %d", 16 + t_rows, chain_rows(h, B)); return OPRL_ERR_STATE; }
+      const int U = h->chain_u < form.chain_max ? h->chain_u : form.chain_max;
       memset((void*)&kc.xchg, 0, sizeof kc.xchg);
       memset((void*)&ka.xchg, 0, sizeof ka.xchg);
       if (h->dp_inline) {
@@ -961,72 +970,67 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
         kc.ad.grad_scale = 1.0f / (float)P.world; ka.ad.grad_scale = 1.0f / (float)P.world;
         h->stale32[0] = true; h->stale32[1] = true;  // (the tiles write the fp16 packs only)
       }
-      if (!h->no_chain && h->chain_flags != nullptr && chain_fits) {
-        // SEVERAL updates as one launch (k_ddpg_chain): the tables above are update 0's; what changes per update — Adam's
-        // bias-correction terms, epochs, exchange tags, the staging set — is in ChainArgs
-        ChainArgs ca;
-        memset((void*)&ca, 0, sizeof ca);
-        ca.n_upd = U;
-        ca.first_gather = fa.src.gather;
-        ca.pf_last = h->chain_pf_last ? 1 : 0;
-        ca.trace_u = U - 1;
-        ca.rows = 16 + t_rows;
-        { static const int order = [] { const char* e = getenv("OPRL_AMD_CHAIN_ORDER"); return e != nullptr ? atoi(e) & 3 : 0; }(); ca.order = order; }
-        ca.c_step[0] = kc.ad.step_size_host; ca.c_bc2[0] = kc.ad.bc2_sqrt_host;
-        ca.a_step[0] = ka.ad.step_size_host; ca.a_bc2[0] = ka.ad.bc2_sqrt_host;
-        for (int u = 1; u < U; ++u) {          // (the optimisers' step counts advance once per update and net, as dw_build does;
-          h->opt_step_critic += 1;             // only Adam's bias-correction terms change from update to update: a call of
-          h->opt_step_actor += 1;              // dw_build per update and net was 8 of the 17 us a step_n(20) call took to enqueue)
-          AdamScalars sc_, sa_;
-          memset(&sc_, 0, sizeof sc_); memset(&sa_, 0, sizeof sa_);
-          set_adam(sc_, c.hp.lr_critic, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, c.hp.tau); set_step(sc_, h->opt_step_critic);
-          set_adam(sa_, c.hp.lr_actor, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, c.hp.tau); set_step(sa_, h->opt_step_actor);
-          ca.c_step[u] = sc_.step_size_host; ca.c_bc2[u] = sc_.bc2_sqrt_host;
-          ca.a_step[u] = sa_.step_size_host; ca.a_bc2[u] = sa_.bc2_sqrt_host;
-        }
-        ca.set0[0] = fa.src.s; ca.set0[1] = fa.src.a; ca.set0[2] = fa.src.r; ca.set0[3] = fa.src.d; ca.set0[4] = fa.src.s2;
-        for (int i = 0; i < 5; ++i) ca.set1[i] = h->chain_set1[i];
-        if ((U > 1 || ca.pf_last) && ca.set1[0] == nullptr) { undo(); set_err("chain launch: no second staging set"); return OPRL_ERR_STATE; }
-        ca.ct_fin = h->chain_flags; ca.at_fin = h->chain_flags + 192; ca.pf_done = h->chain_flags + 384;
-        for (int w = 0; w < 4; ++w)
-          for (int l = 0; l < kMaxLayers; ++l) ca.b16[w][l] = h->chain_b16 + ((size_t)w * kMaxLayers + l) * 256;
-        ca.w3buf[0] = h->w3_snap; ca.w3buf[1] = h->w3buf1;
-        // the first hidden layer's dY from the unit-seed rows the pass's members leave before the pass (DwGate kind 3)
-        ca.qp = h->chain_flags + 576;
-        fa.gu = h->gu; fa.gu_flags = h->chain_flags + 448;
-        ka.gate.kind[0] = 3; ka.gate.gu = h->gu; ka.gate.gu_flags = fa.gu_flags; ka.gate.n_gu_flags = 8 * slices;
-        if (kc.tile_end[kDwFusedItems - 1] > 192 || ka.tile_end[kDwFusedItems - 1] > 192 || slices > 64) { undo(); set_err("chain launch: too many tiles"); return OPRL_ERR_INVALID; }
-        // exchange tags: two per update (the roles', the critic pass's), consecutive: cluster_tag = the first
-        {
-          unsigned& ctr = h->tp_tag;
-          if ((ctr & 0x03FFFFFFu) + 2u * (unsigned)U + 2u >= 0x03FFFFFFu) {      // (would wrap inside the launch: wrap now)
-            ctr = (ctr | 0x03FFFFFFu) + 1u;
-            HIPC(hipMemsetAsync(h->xbuf, 0, h->xbuf_granules * sizeof(unsigned long long), st));
-          }
-          fa.cluster_tag = (ctr + 1u) & 0x03FFFFFFu;
-          ctr += 2u * (unsigned)U;
-        }
-        fa.prefetch_p1 = 0;
-        fa.trace2 = fa.trace != nullptr ? h->trace + (size_t)3 * 64 * kTraceStamps * 2 : nullptr;
-        h->epoch += (unsigned)(U - 1);
-        prof_begin(4, st);
-        hipError_t e;
-        {
-          std::lock_guard<std::mutex> lk(g_turn.mu);
-          int dev = 0;
-          e = chip_turn_begin(st, &dev);
-          if (e == hipSuccess) e = launch_ddpg_chain(fa, kc, ka, ca, st);
-          if (e == hipSuccess) chip_turn_end(st, dev);
-        }
-        prof_end(st);
-        if (e != hipSuccess) undo();
-        HIPC(e);
-        h->whole_done = true;
-        return OPRL_OK;
+      // SEVERAL updates as one launch (k_ddpg_chain): the tables above are update 0's; what changes per update — Adam's
+      // bias-correction terms, epochs, exchange tags, the staging set — is in ChainArgs
+      ChainArgs ca;
+      memset((void*)&ca, 0, sizeof ca);
+      ca.n_upd = U;
+      ca.first_gather = fa.src.gather;
+      ca.pf_last = h->chain_pf_last ? 1 : 0;
+      ca.trace_u = U - 1;
+      ca.rows = 16 + t_rows;
+      ca.order = h->sw.chain_order;
+      ca.c_step[0] = kc.ad.step_size_host; ca.c_bc2[0] = kc.ad.bc2_sqrt_host;
+      ca.a_step[0] = ka.ad.step_size_host; ca.a_bc2[0] = ka.ad.bc2_sqrt_host;
+      for (int u = 1; u < U; ++u) {          // (the optimisers' step counts advance once per update and net, as dw_build does;
+        h->opt_step_critic += 1;             // only Adam's bias-correction terms change from update to update: a call of
+        h->opt_step_actor += 1;              // dw_build per update and net was 8 of the 17 us a step_n(20) call took to enqueue)
+        AdamScalars sc_, sa_;
+        memset(&sc_, 0, sizeof sc_); memset(&sa_, 0, sizeof sa_);
+        set_adam(sc_, c.hp.lr_critic, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, c.hp.tau); set_step(sc_, h->opt_step_critic);
+        set_adam(sa_, c.hp.lr_actor, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, c.hp.tau); set_step(sa_, h->opt_step_actor);
+        ca.c_step[u] = sc_.step_size_host; ca.c_bc2[u] = sc_.bc2_sqrt_host;
+        ca.a_step[u] = sa_.step_size_host; ca.a_bc2[u] = sa_.bc2_sqrt_host;
       }
-      undo();
-      set_err("whole update: one update's workgroups do not fit this device (%d compute units)", h->n_cus);
-      return OPRL_ERR_STATE;
+      ca.set0[0] = fa.src.s; ca.set0[1] = fa.src.a; ca.set0[2] = fa.src.r; ca.set0[3] = fa.src.d; ca.set0[4] = fa.src.s2;
+      for (int i = 0; i < 5; ++i) ca.set1[i] = h->chain_set1[i];
+      if ((U > 1 || ca.pf_last) && ca.set1[0] == nullptr) { undo(); set_err("chain launch: no second staging set"); return OPRL_ERR_STATE; }
+      ca.ct_fin = h->chain_flags; ca.at_fin = h->chain_flags + 192; ca.pf_done = h->chain_flags + 384;
+      for (int w = 0; w < 4; ++w)
+        for (int l = 0; l < kMaxLayers; ++l) ca.b16[w][l] = h->chain_b16 + ((size_t)w * kMaxLayers + l) * 256;
+      ca.w3buf[0] = h->w3_snap; ca.w3buf[1] = h->w3buf1;
+      // the first hidden layer's dY from the unit-seed rows the pass's members leave before the pass (DwGate kind 3)
+      ca.qp = h->chain_flags + 576;
+      fa.gu = h->gu; fa.gu_flags = h->chain_flags + 448;
+      ka.gate.kind[0] = 3; ka.gate.gu = h->gu; ka.gate.gu_flags = fa.gu_flags; ka.gate.n_gu_flags = 8 * slices;
+      if (kc.tile_end[kDwFusedItems - 1] > 192 || ka.tile_end[kDwFusedItems - 1] > 192 || slices > 64) { undo(); set_err("chain launch: too many tiles"); return OPRL_ERR_INVALID; }
+      // exchange tags: two per update (the roles', the critic pass's), consecutive: cluster_tag = the first
+      {
+        unsigned& ctr = h->tp_tag;
+        if ((ctr & 0x03FFFFFFu) + 2u * (unsigned)U + 2u >= 0x03FFFFFFu) {      // (would wrap inside the launch: wrap now)
+          ctr = (ctr | 0x03FFFFFFu) + 1u;
+          HIPC(hipMemsetAsync(h->xbuf, 0, h->xbuf_granules * sizeof(unsigned long long), st));
+        }
+        fa.cluster_tag = (ctr + 1u) & 0x03FFFFFFu;
+        ctr += 2u * (unsigned)U;
+      }
+      fa.prefetch_p1 = 0;
+      fa.trace2 = fa.trace != nullptr ? h->trace + (size_t)3 * 64 * kTraceStamps * 2 : nullptr;
+      h->epoch += (unsigned)(U - 1);
+      prof_begin(4, st);
+      hipError_t e;
+      {
+        std::lock_guard<std::mutex> lk(g_turn.mu);
+        int dev = 0;
+        e = chip_turn_begin(st, &dev);
+        if (e == hipSuccess) e = launch_ddpg_chain(fa, kc, ka, ca, st);
+        if (e == hipSuccess) chip_turn_end(st, dev);
+      }
+      prof_end(st);
+      if (e != hipSuccess) undo();
+      HIPC(e);
+      h->whole_done = true;
+      return OPRL_OK;
     }
     if ((fa.merged & 1) != 0) {
       // phase 1 and the critic's dW + Adam tiles as ONE launch: the tiles wait for the roles' flag granules
@@ -1079,7 +1083,7 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     h->fin_done = false;
     h->fin_l2_done = false;
     h->fin_tail0 = -1;
-    if (algo == OPRL_TQC && !h->no_fin_ride && !h->no_layerwise && !h->no_multi && nc > 2 && nc <= kMaxMulti &&
+    if (algo == OPRL_TQC && !h->sw.no_fin_ride && !h->sw.no_layerwise && nc > 2 && nc <= kMaxMulti &&
         h->lw_scratch != nullptr && h->w_critic == 512 && f.tp_xbuf != nullptr) {
       fin16 = h->bf16 || h->x2;
       for (int j = 0; j < nc; ++j) {
@@ -1112,7 +1116,7 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     }
   }
   // 2. target critics on (s', a')   (independent: one stream each)
-  if (algo == OPRL_TQC && h->tqc_counter != nullptr && !h->no_tqc_ride) {
+  if (algo == OPRL_TQC && h->tqc_counter != nullptr && !h->sw.no_tqc_ride) {
     TqcJob& J = h->tqc_job;
     J.counter = h->tqc_counter;
     J.z = h->qn; J.net_stride = (long)h->Bmax * h->ldq; J.ldz = h->ldq;
@@ -1140,7 +1144,7 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     const int Q = c.hp.n_quantiles, drop = c.hp.top_quantiles_to_drop;
     HIPC(launch_tqc_target(h->qn, (long)h->Bmax * h->ldq, h->ldq, nc, Q, drop, r, d, h->logp2,
                            c.log_alpha, (float)c.hp.gamma, B, h->target, st));
-  } else if (algo == OPRL_TQC && (h->tqc_counter == nullptr || h->no_tqc_ride)) {
+  } else if (algo == OPRL_TQC && (h->tqc_counter == nullptr || h->sw.no_tqc_ride)) {
     const int Q = c.hp.n_quantiles, drop = c.hp.top_quantiles_to_drop;
     HIPC(launch_tqc_target(h->qn, (long)h->Bmax * h->ldq, h->ldq, nc, Q, drop, r, d, h->logp2,
                            c.log_alpha, (float)c.hp.gamma, B, h->target, st));
@@ -1150,7 +1154,7 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
   // heads (k_lw_head: 80 workgroups on 256 CUs), with the noise and the counter actor_phase would give it
   h->rider_pending = false;
   h->rider_done = false;
-  if (algo == OPRL_TQC && !h->no_af_ride && !c.export_grads && actor_due(h)) {
+  if (algo == OPRL_TQC && !h->sw.no_af_ride && !c.export_grads && actor_due(h)) {
     MlpArgs f = actor_forward_args(h, s, B, h->noise1_pending);
     if (f.tp_xbuf != nullptr) {
       RC(next_tp_tag(f.tp_tag_counter, f.tp_xbuf, f.tp_xbuf_bytes, st, &f.tp_tag));
@@ -1200,11 +1204,11 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     dw.ad = adam_scalars(h, c.hp.lr_critic, h->opt_step_critic, polyak, 1.0f);
     // TQC in a 16-bit mode: the critics' 512 x 512 layers run through the 16-bit packs (layerwise.hip); their fp32
     // packs — a third of the wide dW launch's stores — are left stale and rebuilt by whoever reads them (fresh32)
-    if (algo == OPRL_TQC && (h->x2 || h->bf16) && h->lazy_wide && !c.export_grads && !h->no_layerwise) {
+    if (algo == OPRL_TQC && (h->x2 || h->bf16) && h->lazy_wide && !c.export_grads && !h->sw.no_layerwise) {
       dw.skip32_wide = 1;
       h->stale_wide = true;
     }
-    HIPC(launch_dw_prof(dw, st));
+    HIPC(launch_dw_prof(h, dw, st));
   }
   return OPRL_OK;
 }
@@ -1344,7 +1348,7 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
     // offered as a rider of that launch (r06-16; the tag its launch would draw, now)
     h->bwd_rider_pending = false;
     h->bwd_rider_done = false;
-    if (algo == OPRL_TQC && gauss && !c.export_grads && !h->no_bwd_ride) {
+    if (algo == OPRL_TQC && gauss && !c.export_grads && !h->sw.no_bwd_ride) {
       MlpArgs f = actor_backward_args();
       if (f.tp_xbuf != nullptr && mlp_slice_tp_shape_ok(f, h->w_actor)) {
         RC(next_tp_tag(f.tp_tag_counter, f.tp_xbuf, f.tp_xbuf_bytes, st, &f.tp_tag));
@@ -1354,7 +1358,7 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
         // them): built with THIS update's step count; if the launch does not take them, step 9 launches the same table
         h->bwd_tiles_pending = false;
         h->bwd_tiles_done = false;
-        if (!h->no_bwd_tiles && alpha_rides(h) && h->n_items_actor <= kDwMaxItems) {
+        if (!h->sw.no_bwd_tiles && alpha_rides(h) && h->n_items_actor <= kDwMaxItems) {
           actor_dw = actor_dw_args();
           actor_dw_built = true;
           const int total = fill_dw_kargs(actor_dw, &h->bwd_tiles, 32);
@@ -1390,7 +1394,7 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
     h->bwd_tiles_done = false;
   } else {
     if (!actor_dw_built) actor_dw = actor_dw_args();
-    HIPC(launch_dw_prof(actor_dw, st));
+    HIPC(launch_dw_prof(h, actor_dw, st));
   }
   // 10. temperature (when it did not ride on the actor's dW launch)
   if (alpha_ptr(h) != nullptr && !alpha_rides(h)) {
@@ -1515,9 +1519,7 @@ extern "C" int oprl_learner_clear_error(oprl_learner* h) {
     // set_cluster(< 8) semantics, as for learners that share a GPU by design.
     const unsigned code = *(volatile unsigned*)h->err_host, w = code & 0xff;
     if (code != 0 && w != 9 /* SITE_X2_RANGE */ && w != 5 && w != 6 /* data-parallel peers */ && !h->debug_expire && !h->shared_chip) {
-      h->shared_chip = true;
-      h->no_whole = 1;
-      h->no_wide = 1;
+      h->shared_chip = true;     // (and so: no merged or whole-update form, no clusters of eight)
     }
     // (an expired wait of any kind: the cluster exchanges go back to agent-scope publishes as well — if a member sat on an
     // XCD the others did not expect, the demoted forms must not repeat it)
@@ -1613,7 +1615,7 @@ extern "C" int oprl_learner_apply(oprl_learner* h, int32_t phase, double grad_sc
     dw.ad = adam_scalars(h, c.hp.lr_critic, h->opt_step_critic, polyak, (float)grad_scale);
     dw.ad.do_adam = 1;
     if (h->fchain) h->stale32[0] = true;      // (the launch writes the mirrors: the caller's packs fall behind)
-    HIPC(launch_dw_prof(dw, st));
+    HIPC(launch_dw_prof(h, dw, st));
     return OPRL_OK;
   }
   if (phase == 1) {
@@ -1626,7 +1628,7 @@ extern "C" int oprl_learner_apply(oprl_learner* h, int32_t phase, double grad_sc
     dw.ad = adam_scalars(h, c.hp.lr_actor, h->opt_step_actor, n.theta_target != nullptr, (float)grad_scale);
     dw.ad.do_adam = 1;
     if (h->fchain) h->stale32[1] = true;
-    HIPC(launch_dw_prof(dw, st));
+    HIPC(launch_dw_prof(h, dw, st));
     if (alpha_ptr(h) != nullptr)
       HIPC(launch_alpha_step(c.log_alpha, c.log_alpha_m, c.log_alpha_v, nullptr, 1, (float)c.hp.target_entropy,
                              c.hp.lr_alpha, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, h->opt_step_alpha,
@@ -1646,7 +1648,7 @@ int chain_loop(oprl_learner* h, int K, int B, float* (*set)[5], void* stream) {
   int rc = OPRL_OK;
   h->staged_ready = false;
   for (int k = 0; k < K && rc == OPRL_OK;) {
-    const int U = K - k < h->chain_max ? K - k : h->chain_max;
+    const int U = K - k < h->sw.chain_max ? K - k : h->sw.chain_max;
     float** b = set[cur];
     float** nb = set[cur ^ 1];
     for (int i = 0; i < 5; ++i) h->chain_set1[i] = nb[i];
@@ -1675,7 +1677,7 @@ int chain_loop(oprl_learner* h, int K, int B, float* (*set)[5], void* stream) {
 
 // does step_n at this batch run as chain launches?
 bool chain_ok(oprl_learner* h, int B) {
-  return ddpg_args(h, B).whole && B <= 256 && h->batch_alt != nullptr;
+  return fused_form(h, B, h->dp_inline).whole && h->batch_alt != nullptr;
 }
 }  // namespace oprl_host
 
@@ -1708,11 +1710,11 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
                         {alt, alt + Bm * h->S, alt + Bm * (h->S + h->A), alt + Bm * (h->S + h->A + 1), alt + Bm * (h->S + h->A + 2)}};
     // k_ddpg_chain: up to chain_max updates per launch, the rows of update u + 1 staged by update u inside the launch
     const bool chain = chain_ok(h, B);
-    const DdpgArgs probe = ddpg_args(h, B);
+    const FusedForm probe = fused_form(h, B, h->dp_inline);     // (prefetch_p1 is false here: the form's merged bits never read it)
     // (... and TD3's merged twin launches in every arithmetic, r06-15: without the merged phase 2 — exact fp32, bf16 — a
     // critic-only update had no launch that staged the next rows, and the update behind it gathered its own inside the roles'
     // first stage: 4.8 us against 2.9 before the first barrier of every role of every second launch)
-    const bool td3_p1 = h->cfg.algo == OPRL_TD3 && (probe.merged & 1) != 0 && !h->no_p1_rows;
+    const bool td3_p1 = h->cfg.algo == OPRL_TD3 && (probe.merged & 1) != 0 && !h->sw.no_p1_rows;
     h->prefetch_p1 = !chain && alt != nullptr && ((probe.merged & 2) != 0 || td3_p1);
     int cur = 0;
     int rc = OPRL_OK;
@@ -1738,7 +1740,7 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
     h->staged_ready = false;
     return rc;
   }
-  if (h->cfg.algo == OPRL_TQC && h->batch_alt != nullptr && !h->no_gather_ride && K > 1) {
+  if (h->cfg.algo == OPRL_TQC && h->batch_alt != nullptr && !h->sw.no_gather_ride && K > 1) {
     // the rows of update k + 1 are gathered by riders of update k's k_lw_dact launch (same draw as k_replay_gather)
     // into the other of two sets of batch rows; only the first update's rows are a launch
     PrefetchJob base;

@@ -2,6 +2,38 @@
 // pool, the uncached areas, the tile and repack tables.  Split from learner.hip (round 4).
 #include "learner_internal.h"
 
+namespace oprl_host {
+// the one place the learner's switches are read (learner_internal.h Switches)
+Switches read_switches() {
+  auto flag = [](const char* name) { const char* e = getenv(name); return e != nullptr && atoi(e) != 0; };
+  Switches sw;
+  if (const char* e = getenv("OPRL_AMD_CLUSTER")) sw.cluster = atoi(e);
+  if (sw.cluster != 1 && sw.cluster != 2 && sw.cluster != 4) sw.cluster = kMaxCluster;
+  if (const char* f = getenv("OPRL_AMD_FORM")) {
+    if (!strcmp(f, "two")) sw.no_whole = true;
+    else if (!strcmp(f, "p2")) sw.no_whole = sw.no_merge2 = true;
+    else if (!strcmp(f, "plain")) sw.no_whole = sw.no_merge2 = sw.no_merge = true;
+  }
+  if (const char* e = getenv("OPRL_AMD_CHAIN")) { const int v = atoi(e); if (v >= 1 && v <= kChainMax) sw.chain_max = v; }
+  if (const char* e = getenv("OPRL_AMD_CHAIN_ORDER")) sw.chain_order = atoi(e) & 3;
+  const char* nr = getenv("OPRL_AMD_NO_RIDE");
+  const int no_ride = nr != nullptr ? atoi(nr) : 0;
+  bool* const ride[10] = {&sw.no_tqc_ride, &sw.no_af_ride, &sw.no_fin_ride, &sw.no_gather_ride, &sw.no_wide_dw,
+                          &sw.no_lw_pairs, &sw.no_merge_twin, &sw.no_l2_ride, &sw.no_bwd_ride, &sw.no_bwd_tiles};
+  for (int b = 0; b < 10; ++b) *ride[b] = (no_ride >> b & 1) != 0;
+  sw.no_layerwise = flag("OPRL_AMD_NO_LAYERWISE");
+  sw.no_p1_rows = flag("OPRL_AMD_NO_P1_ROWS");
+  sw.no_dp_inline = flag("OPRL_AMD_NO_DP_INLINE");
+  sw.no_side_by_side = flag("OPRL_AMD_NO_SIDE_BY_SIDE");
+  sw.no_lean = flag("OPRL_AMD_NO_LEAN") ? 1 : 0;
+  sw.no_wide = flag("OPRL_AMD_NO_WIDE");
+  if (const char* e = getenv("OPRL_AMD_NO_RT2")) { sw.no_rt2 = atoi(e); if (sw.no_rt2 < 0 || sw.no_rt2 > 2) sw.no_rt2 = 1; }
+  sw.no_xcd_local = flag("OPRL_AMD_NO_XCD_LOCAL");
+  sw.no_bf16_chain = getenv("OPRL_AMD_NO_BF16_CHAIN") != nullptr;
+  return sw;
+}
+}  // namespace oprl_host
+
 extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner** out) {
   if (!cfg || !out) { set_err("oprl_learner_create: null argument"); return OPRL_ERR_INVALID; }
   if (cfg->abi_version != OPRL_ABI_VERSION) { set_err("ABI version mismatch: caller %d, library %d", cfg->abi_version, OPRL_ABI_VERSION); return OPRL_ERR_INVALID; }
@@ -15,6 +47,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   if (cfg->max_batch < 1 || cfg->state_dim < 1 || cfg->action_dim < 1) { set_err("bad dims"); return OPRL_ERR_INVALID; }
   auto* h = new oprl_learner();
   h->cfg = *cfg;
+  h->sw = read_switches();
   h->S = cfg->state_dim; h->A = cfg->action_dim; h->Bmax = cfg->max_batch; h->nc = cfg->n_critics;
   h->bf16 = cfg->precision == OPRL_PREC_BF16;
   h->x2 = cfg->precision == OPRL_PREC_X2;
@@ -104,7 +137,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
               cfg->actor.theta_target != nullptr && cfg->critics[0].theta_target != nullptr && cfg->actor.n_layers == 3 && cfg->critics[0].n_layers == 3;
   h->bchain = h->fused && h->bf16 && cfg->algo == OPRL_DDPG && nc == 1 && merge2_bufs &&
               cfg->actor.theta_target != nullptr && cfg->critics[0].theta_target != nullptr && cfg->actor.n_layers == 3 && cfg->critics[0].n_layers == 3 &&
-              getenv("OPRL_AMD_NO_BF16_CHAIN") == nullptr;
+              !h->sw.no_bf16_chain;
   const int uc_pool = (h->x2 || h->fchain || h->bchain) ? 1 : 0;
   h->uc_pool = uc_pool != 0;
   if ((uc_pool ? uc_alloc((void**)&h->pool.base, bytes) : hipMalloc(&h->pool.base, bytes)) != hipSuccess) { set_err("hipMalloc(%zu) failed", bytes); delete h; return OPRL_ERR_NOMEM; }
@@ -241,19 +274,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
       h->n_cus = prop.multiProcessorCount;
-    const char* env = getenv("OPRL_AMD_CLUSTER");
-    h->ncl = env ? atoi(env) : kMaxCluster;
-    if (h->ncl != 1 && h->ncl != 2 && h->ncl != 4) h->ncl = kMaxCluster;
-    h->no_multi = false;
-    // OPRL_AMD_NO_RIDE = bit mask of the riders / joined launches to switch off (tests: each is bit-identical to the
-    // separate launches): 1 TD target on the target heads, 2 actor forward on the critic heads, 4 first hidden launch
-    // behind the actor's forward, 8 next rows on k_lw_dact, 16 wide dW kernel (kernels.hip), 32 hidden-layer pairs,
-    // (64: TD3's twin tiles, below) 128 the online critics' second hidden layer behind the tail on the target heads (r06-12),
-    // 256 the actor's backward on the k_lw_dact launch (r06-16), 512 its dW + Adam tiles behind it (r06-18)
-    const int no_ride = [] { const char* e = getenv("OPRL_AMD_NO_RIDE"); return e != nullptr ? atoi(e) : 0; }();
-    const char* nlw = getenv("OPRL_AMD_NO_LAYERWISE");
-    h->no_layerwise = (nlw != nullptr && atoi(nlw) != 0);
-    h->no_gather_ride = (no_ride & 8) != 0;
+    h->ncl = h->sw.cluster;
     if (cfg->algo == OPRL_TQC || h->du_granules != nullptr) {
       const size_t n = (size_t)h->Bmax * (2 * (size_t)h->S + h->A + 2);
       // (PrecX2 learners: uncached, like the first staging set in the pool — inside k_ddpg_chain an update reads rows a
@@ -261,15 +282,12 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
       if ((h->uc_pool ? uc_alloc((void**)&h->batch_alt, n * sizeof(float)) : hipMalloc(&h->batch_alt, n * sizeof(float))) != hipSuccess)
         h->batch_alt = nullptr;   // (then: a gather launch per update)
     }
-    h->no_fin_ride = (no_ride & 4) != 0;
-    h->no_bwd_ride = (no_ride & 256) != 0;
-    h->no_bwd_tiles = (no_ride & 512) != 0;
-    { const char* e = getenv("OPRL_AMD_NO_P1_ROWS"); h->no_p1_rows = e != nullptr && atoi(e) != 0; }
     if (cfg->algo == OPRL_TQC && h->w_critic == 512) {
       const size_t n = (size_t)nc * (kMaxLayers - 1) * (size_t)h->Bmax * 512;
       if (hipMalloc(&h->lw_scratch, n * sizeof(float)) != hipSuccess) h->lw_scratch = nullptr;   // (then: the nets' own buffers, no early launch)
       {
-        const int pair_env = (no_ride & 32) != 0 ? 0 : (31 & ~((no_ride & 128) != 0 ? 4 : 0) & ~((no_ride & 256) != 0 ? 8 : 0) & ~((no_ride & 512) != 0 ? 16 : 0));
+        const Switches& sw = h->sw;
+        const int pair_env = sw.no_lw_pairs ? 0 : (31 & ~(sw.no_l2_ride ? 4 : 0) & ~(sw.no_bwd_ride ? 8 : 0) & ~(sw.no_bwd_tiles ? 16 : 0));
         const int nf = kMaxMulti * ((h->Bmax + 31) / 32) * 32;
         void* fl = nullptr;
         if (pair_env != 0 && hipMalloc(&fl, (size_t)nf * sizeof(unsigned long long)) == hipSuccess) {
@@ -279,46 +297,20 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
         }
       }
     }
-    h->no_af_ride = (no_ride & 2) != 0;
-    h->no_tqc_ride = (no_ride & 1) != 0;
     if (cfg->algo == OPRL_TQC && nc * cfg->hp.n_quantiles <= 128) {
       const size_t slices = (size_t)(h->Bmax + kR - 1) / kR;
       if (hipMalloc(&h->tqc_counter, slices * sizeof(unsigned long long)) != hipSuccess) h->tqc_counter = nullptr;   // (then: the stand-alone launch)
       else (void)hipMemset(h->tqc_counter, 0, slices * sizeof(unsigned long long));
     }
-    const char* ndi = getenv("OPRL_AMD_NO_DP_INLINE");
-    h->no_dp_inline = (ndi != nullptr && atoi(ndi) != 0);
-    // OPRL_AMD_NO_SIDE_BY_SIDE: TD3 / SAC twin nets back to back instead of on clusters that wait for each other
-    const char* nsb = getenv("OPRL_AMD_NO_SIDE_BY_SIDE");
-    h->no_twin_split = (nsb != nullptr && atoi(nsb) != 0);
-    h->no_p2_pair = h->no_twin_split;
-    const char* nl = getenv("OPRL_AMD_NO_LEAN");
-    h->no_lean = (nl != nullptr && atoi(nl) != 0) ? 1 : 0;
-    // OPRL_AMD_FORM: the launch structure of the fused DDPG / TD3 update — "chain" (default: the whole update, several
-    // per launch), "two" (merged phase launches: phase 1 + the critic's tiles | phase 2 + the actor's), "p2" (phase 1
-    // merged, phase 2 and the actor's dW as launches of their own), "plain" (phases and dW launches)
-    h->no_merge = h->no_merge2 = h->no_whole = 0;
-    if (const char* f = getenv("OPRL_AMD_FORM")) {
-      if (!strcmp(f, "two")) h->no_whole = 1;
-      else if (!strcmp(f, "p2")) { h->no_whole = 1; h->no_merge2 = 1; }
-      else if (!strcmp(f, "plain")) { h->no_whole = 1; h->no_merge2 = 1; h->no_merge = 1; }
-    }
-    h->no_chain = 0;
-    if (const char* cm = getenv("OPRL_AMD_CHAIN")) { const int v = atoi(cm); if (v >= 1 && v <= kChainMax) h->chain_max = v; }
-    const char* nw = getenv("OPRL_AMD_NO_WIDE");
-    h->no_wide = (nw != nullptr && atoi(nw) != 0) ? 1 : 0;
-    h->no_merge_twin = (no_ride & 64) != 0 ? 1 : 0;
-    { const char* e = getenv("OPRL_AMD_NO_RT2"); h->no_rt2 = e != nullptr ? atoi(e) : 0; if (h->no_rt2 < 0 || h->no_rt2 > 2) h->no_rt2 = 1; }   // 1: one row tile everywhere; 2: the B roles' two tiles, but SAC's role C stays a role of its own
-    const char* nxl = getenv("OPRL_AMD_NO_XCD_LOCAL");
-    h->xcd_local = h->fused && !(nxl != nullptr && atoi(nxl) != 0) && xcd_map_ok();
+    h->xcd_local = h->fused && !h->sw.no_xcd_local && xcd_map_ok();
     // the generic per-net launches on clusters of 4 (slice_tp.hip): any net of the common shape
     // (decided per net by tp_generic(): TQC's 512-wide critics stay on k_mlp_slice, its actor moves)
-    h->tp_generic_on = !h->no_lean && h->ncl == 4;
+    h->tp_generic_on = !h->sw.no_lean && h->ncl == 4;
   }
   if (h->fused || h->tp_generic_on) {
     const size_t slices = (size_t)(h->Bmax + kR - 1) / kR;
     // (areas laid out for clusters of eight where wide clusters may run: DDPG / TD3, fp32, lean passes)
-    h->xnc = (h->fused && (!h->bf16 || h->bchain) && !h->no_lean && !h->no_wide && h->ncl == 4 &&
+    h->xnc = (h->fused && (!h->bf16 || h->bchain) && !h->sw.no_lean && !h->sw.no_wide && h->ncl == 4 &&
               (cfg->algo == OPRL_DDPG || cfg->algo == OPRL_TD3)) ? 8 : kMaxCluster;
     h->xbuf_granules = (size_t)(2 + nc) * slices * fused_xbuf_granules_per_cluster(h->xnc);
     if (hipMalloc(&h->xbuf, h->xbuf_granules * sizeof(unsigned long long)) != hipSuccess) {

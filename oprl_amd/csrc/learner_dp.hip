@@ -171,7 +171,7 @@ extern "C" int oprl_learner_dp_update(oprl_learner* h, const float* s, const flo
   const double scale = 1.0 / (double)dp_world(h);
   // Fused learners on peer windows: the two dW launches exchange their own tiles (k_dw_adam<true>) and
   // run Adam on the mean — no separate all-reduce or apply launches.
-  if (h->p2p_ok && h->p2p_inline && !h->no_dp_inline && h->p2p.tile_bytes > 0 && use_fused(h, B)) {
+  if (h->p2p_ok && h->p2p_inline && !h->sw.no_dp_inline && h->p2p.tile_bytes > 0 && use_fused(h, B)) {
     h->dp_inline = true;
     int rc = oprl_learner_update_phase(h, 0, s, a, r, d, s2, B, noise0, noise1, stream);
     if (rc == OPRL_OK) rc = oprl_learner_update_phase(h, 1, s, a, r, d, s2, B, noise0, noise1, stream);
@@ -221,7 +221,7 @@ extern "C" int oprl_learner_dp_step_n(oprl_learner* h, oprl_replay* replay, int3
     // The gradient exchange inside the tiles of the whole-update launch (peer windows, PrecX2 learners): the data-parallel
     // K-loop IS the single-GPU one — k_ddpg_chain, up to chain_max updates per launch, every tile all-reducing its
     // gradient with the other ranks' before Adam.  No all-reduce launches, no apply launches.
-    if (h->p2p_ok && h->p2p_inline && !h->no_dp_inline && h->p2p.tile_bytes > 0) {
+    if (h->p2p_ok && h->p2p_inline && !h->sw.no_dp_inline && h->p2p.tile_bytes > 0) {
       h->dp_inline = true;
       if (chain_ok(h, B)) {
         const size_t Bm = (size_t)h->Bmax;

@@ -50,19 +50,14 @@ extern "C" int oprl_group_create(oprl_learner** learners, int32_t n, oprl_group*
   }
   // The members' launch form.  Exact fp32: the generic single-CU-per-slice passes (cluster size 1) — no workgroup of such
   // a launch waits for another, and 32 members measure 71k updates/s against 58k on clusters of four.  bf16 / x2: the
-  // lean passes on clusters of four (the only form these precisions exist in).  OPRL_AMD_GROUP_NC=4: clusters of four
-  // for exact fp32 as well.  TD3 / SAC members (fused in the lean form only): clusters of four in every precision.
+  // lean passes on clusters of four (the only form these precisions exist in).  TD3 / SAC members (fused in the lean form
+  // only): clusters of four in every precision.
   int group_nc = 4;
   {
-    const int env_nc = 0;
     oprl_learner* h0 = learners[0];
-    const int keep_ncl = h0->ncl;
-    const bool keep_sc = h0->shared_chip;
-    const int keep_nw = h0->no_wide;
-    h0->ncl = 4; h0->shared_chip = true; h0->no_wide = 1;
-    const bool lean = fused_ddpg_is_lean(ddpg_args(h0, h0->Bmax));
-    h0->ncl = keep_ncl; h0->shared_chip = keep_sc; h0->no_wide = keep_nw;
-    if (!lean || (algo0 == OPRL_DDPG && !h0->bf16 && !h0->x2 && env_nc != 4)) group_nc = 1;
+    // (the lean passes on clusters of four, as the members will run them: nc_cluster with ncl = 4)
+    const bool lean = 4 * ((h0->Bmax + kR - 1) / kR) <= h0->n_cus && fused_ddpg_is_lean(4, h0->sw.no_lean, h0->S, h0->A, algo0 == OPRL_SAC);
+    if (!lean || (algo0 == OPRL_DDPG && !h0->bf16 && !h0->x2)) group_nc = 1;
     if (group_nc == 1 && (h0->bf16 || h0->x2 || algo0 != OPRL_DDPG)) {
       set_err("oprl_group_create: TD3 / SAC members and the bf16 / x2 modes need nets the lean passes take (256-wide hidden layers, narrow inputs)");
       return OPRL_ERR_INVALID;
@@ -86,7 +81,7 @@ extern "C" int oprl_group_create(oprl_learner** learners, int32_t n, oprl_group*
   }
   // (a solo run for comparison: oprl_learner_set_cluster(h, 4) — the un-merged lean launches — or (h, 1))
   // (the twin critics' side-by-side forms want all of a slice's clusters resident at once: not in a queue of members)
-  for (oprl_learner* h : g->L) { h->ncl = group_nc; h->shared_chip = true; h->no_wide = 1; h->no_twin_split = true; h->no_p2_pair = true; }
+  for (oprl_learner* h : g->L) { h->ncl = group_nc; h->shared_chip = true; h->group_member = true; }
   *out = g;
   return OPRL_OK;
 }
@@ -108,10 +103,9 @@ extern "C" int oprl_learner_set_cluster(oprl_learner* h, int32_t nc) {
   if (!h || (nc != 1 && nc != 2 && nc != 4 && nc != 8)) { set_err("oprl_learner_set_cluster: cluster size must be 1, 2, 4 or 8"); return OPRL_ERR_INVALID; }
   // 8 = clusters of four, and of eight where the fused kernels have them (the default); 4 = never eight
   h->ncl = nc == 8 ? 4 : nc;
-  static const bool env_off = [] { const char* e = getenv("OPRL_AMD_NO_WIDE"); return e != nullptr && atoi(e) != 0; }();
-  h->no_wide = (nc == 8 && !env_off) ? 0 : 1;
   // ... and a learner that shares the chip (anything but 8) keeps to the launch forms whose workgroups only wait within
-  // their cluster: no tile workgroups riding on the phase launches (measured: 8 learners on 8 streams 47k -> 60k aggregate)
+  // their cluster: no clusters of eight, no tile workgroups riding on the phase launches (measured: 8 learners on 8
+  // streams 47k -> 60k aggregate); with 8, clusters of eight unless h->sw.no_wide (fused_form)
   h->shared_chip = nc != 8;
   return OPRL_OK;
 }

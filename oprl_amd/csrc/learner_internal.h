@@ -82,7 +82,7 @@ bool fused_tile64_all();
 size_t fused_xbuf_granules_per_cluster(int nc);
 hipError_t launch_ddpg_phase1(const DdpgArgs& a, hipStream_t st);
 hipError_t launch_ddpg_phase1_dw(const DdpgArgs& a, const DwKArgs& d, hipStream_t st);
-bool fused_ddpg_is_lean(const DdpgArgs& a);
+bool fused_ddpg_is_lean(int nc, int no_lean, int S, int A, bool sac);
 hipError_t launch_ddpg_phase2(const DdpgArgs& a, hipStream_t st);
 hipError_t launch_ddpg_phase2_dw(const DdpgArgs& a, const DwKArgs& d, hipStream_t st);
 hipError_t launch_ddpg_chain(const DdpgArgs& a, const DwKArgs4& dc, const DwKArgs4& da, const ChainArgs& c, hipStream_t st);
@@ -255,11 +255,48 @@ struct Pool {  // one hipMalloc, bump allocated
   }
 };
 
+// Every OPRL_AMD_* switch that shapes a learner's launches, read once at oprl_learner_create (read_switches), never
+// written afterwards.  Each NO_* turns one form or rider off (tests / A-B: bit-identical to what it replaces).
+struct Switches {
+  int cluster = kMaxCluster;   // OPRL_AMD_CLUSTER=1 / 2 / 4: CUs per slice cluster in the fused path (ncl's start value)
+  // OPRL_AMD_FORM: "chain" (default: the whole update, several per launch), "two" (no_whole: merged phase launches, phase 1
+  // + the critic's tiles | phase 2 + the actor's), "p2" (+ no_merge2: phase 2 and the actor's dW as launches of their own),
+  // "plain" (+ no_merge: the critic's dW as a launch of its own)
+  bool no_whole = false, no_merge2 = false, no_merge = false;
+  int chain_max = kChainMax;   // OPRL_AMD_CHAIN=n: at most n updates per k_ddpg_chain launch
+  int chain_order = 0;         // OPRL_AMD_CHAIN_ORDER: dispatch order of an update's role rows (ChainArgs::order)
+  // OPRL_AMD_NO_RIDE, bit by bit: 1 TQC's TD target on the target heads, 2 its actor forward on the critic heads, 4 the
+  // online critics' first hidden launch behind that forward, 8 the next rows on k_lw_dact, 16 the 64 x 64-tile dW kernel
+  // of the 512 x 512 layers (DwArgs::no_wide), 32 hidden-layer pairs, 64 TD3's twin tiles on merged phase 1, 128 the
+  // critics' second hidden layer behind the tail on the target heads (r06-12), 256 the actor's backward on k_lw_dact
+  // (r06-16), 512 its dW + Adam tiles behind it (r06-18)
+  bool no_tqc_ride = false, no_af_ride = false, no_fin_ride = false, no_gather_ride = false, no_wide_dw = false;
+  bool no_lw_pairs = false, no_merge_twin = false, no_l2_ride = false, no_bwd_ride = false, no_bwd_tiles = false;
+  bool no_layerwise = false;   // OPRL_AMD_NO_LAYERWISE: wide nets stay on the single-CU slice kernel
+  bool no_p1_rows = false;     // OPRL_AMD_NO_P1_ROWS: TD3's exact-fp32 / bf16 merged launches carry no next-rows row (r06-15)
+  bool no_dp_inline = false;   // OPRL_AMD_NO_DP_INLINE: peer-window exchanges as separate launches
+  bool no_side_by_side = false;   // OPRL_AMD_NO_SIDE_BY_SIDE: the twin critics back to back (role A, SAC's phase 2)
+  int no_lean = 0;             // OPRL_AMD_NO_LEAN: the generic tp3.h passes, never tp4.h's (DdpgArgs::no_lean)
+  bool no_wide = false;        // OPRL_AMD_NO_WIDE: never run role A / phase 2's critic pass on clusters of eight
+  int no_rt2 = 0;              // OPRL_AMD_NO_RT2: 1 one row tile everywhere; 2 the B roles' two tiles, SAC's role C a role
+  bool no_xcd_local = false;   // OPRL_AMD_NO_XCD_LOCAL: cluster exchanges at agent scope
+  bool no_bf16_chain = false;  // OPRL_AMD_NO_BF16_CHAIN (set at all): bf16 DDPG learners without k_ddpg_chain<PrecBF16>
+};
+Switches read_switches();
+
+// The launch form of a fused DDPG / TD3 / SAC update (fused_form, learner.hip; the fields as in DdpgArgs)
+struct FusedForm {
+  bool lean = false;           // tp4.h's passes (fused_ddpg_is_lean); false: the generic tp3.h passes (DDPG)
+  int x2 = 0, bf16 = 0, nc = 1, xnc = 1, wide = 0, twin_split = 0, p2_pair = 0, merged = 0, whole = 0, rt2 = 0;
+  int chain_max = 1;           // updates per k_ddpg_chain launch at most (1 unless `whole`)
+};
+
 }  // namespace oprl_host
 
 using namespace oprl_host;
 
 struct oprl_learner {
+  Switches sw;                 // the environment switches, read by oprl_learner_create
   oprl_learner_config cfg;
   int S, A, Bmax, nc;
   int w_actor = 0, w_critic = 0;
@@ -301,22 +338,14 @@ struct oprl_learner {
   int p2p_max_tiles = 0;
   bool dp_inline = false;      // this data-parallel update exchanges inside the dW launches (k_dw_adam<true>)
   DwXchg dw_xchg;
-  bool no_dp_inline = false;   // OPRL_AMD_NO_DP_INLINE: peer-window exchanges as separate launches (tests / A-B)
-  bool no_twin_split = false;  // OPRL_AMD_NO_SIDE_BY_SIDE: role A runs both target critics back to back (tests / A-B)
-  bool no_multi = false;
   PrefetchJob prefetch;        // step_n on the generic path (TQC): the next update's rows as riders of this update's k_lw_dact launch
   bool prefetch_pending = false, prefetch_done = false;
-  bool no_gather_ride = false; // OPRL_AMD_NO_RIDE bit 8: a k_replay_gather launch per update (tests / A-B)
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)
   bool fin16 = false;
-  bool no_bwd_tiles = false;   // OPRL_AMD_NO_RIDE bit 512: the actor's dW + Adam tiles as a launch of their own (r06-18)
-  bool no_bwd_ride = false;    // OPRL_AMD_NO_RIDE bit 256: TQC's actor backward as a launch of its own instead of riders of k_lw_dact (r06-16)
-  bool no_p1_rows = false;     // OPRL_AMD_NO_P1_ROWS: TD3's exact-fp32 / bf16 merged launches carry no next-rows row (tests / A-B; r06-15)
   bool fin_l2_done = false;    // ... and the second hidden layer's forward rode on the target pass's heads behind the tail (r06-12); step 3 skips it too
   bool fin_done = false;       // TQC: the online critics' first hidden launch rode on the actor's forward on s' (critic_phase step 1); step 3 skips it
-  bool no_fin_ride = false;    // OPRL_AMD_NO_RIDE bit 4: it stays the first launch of step 3 (tests / A-B)
   LwPairBuf lw_pairs = {nullptr, 0, 1u, 1 << 20, nullptr, 3, 0};   // k_lw_mid_pair: flags (own allocation), tags; OPRL_AMD_LW_PAIR: bit 0 forward, bit 1 backward pairs (default 3)
   float* lw_scratch = nullptr; // [critics][layers 1 .. L-1][Bmax x 512]: activations of forward-only layer-by-layer launches (the target pass) — not the nets' dW exchange buffers, which the early first launch has already filled
   MlpArgs rider;               // TQC: the actor's forward on s, prepared in critic_phase to ride on the critic step's head launch ...
@@ -328,13 +357,9 @@ struct oprl_learner {
   DwKArgs bwd_tiles;           // ... and its dW + Adam tiles (the actor's step 9) behind it (r06-18): offered with the rider; taken: bwd_tiles_done
   int bwd_tile_wgs = 0;
   bool bwd_tiles_pending = false, bwd_tiles_done = false;
-  bool no_af_ride = false;     // OPRL_AMD_NO_RIDE bit 2: the forward stays a launch of actor_phase (tests / A-B)
   TqcJob tqc_job;              // TQC: the TD target as the tail of the target critics' head launch (kernels.h) ...
   bool tqc_job_pending = false; // ... offered to the next for_each_net; still set afterwards: k_tqc_target as a launch of its own
-  bool no_tqc_ride = false;    // OPRL_AMD_NO_RIDE bit 1: always that launch (tests / A-B)
   unsigned long long* tqc_counter = nullptr;   // [slices at Bmax] arrival counters, zeroed once
-  bool no_layerwise = false;   // OPRL_AMD_NO_LAYERWISE: wide nets stay on the single-CU slice kernel (tests / A-B)
-  bool no_p2_pair = false;     // OPRL_AMD_NO_SIDE_BY_SIDE: SAC phase 2 runs the twin critics back to back (tests / A-B)
   bool multi_collect = false;  // for_each_net over > 2 single-CU nets: one k_mlp_slice_multi launch
   int multi_n = 0, multi_width = 0;
   MlpArgs multi_args[kMaxMulti];
@@ -343,10 +368,8 @@ struct oprl_learner {
   unsigned epoch = 0;          // monotonically increasing, never reset
   int ncl = 1;                 // CUs per slice cluster in the fused path (csrc/tp3.h)
   int n_cus = 256;
-  int no_lean = 0;
-  bool shared_chip = false;    // oprl_learner_set_cluster(< 8): this learner is one of several on the GPU
-  int no_merge = 0;            // OPRL_AMD_FORM=plain: dW launches of their own
-  int no_merge2 = 0;           // OPRL_AMD_FORM=p2 / plain: phase 2 runs the actor's backward itself, the actor's dW is a launch of its own
+  bool shared_chip = false;    // oprl_learner_set_cluster(< 8): this learner is one of several on the GPU (no clusters of eight either)
+  bool group_member = false;   // oprl_group_create took it (and it stays so): no side-by-side twin forms, whose clusters wait for each other
   // merged phase 2 (DdpgArgs::merged bit 1): du granules [Bm][kDuLd], the first layer's dz1 granules [16][Bm][16] and the
   // snapshot of the actor's output layer (Bm = min(max_batch, 256))
   // oprl_learner_step_act: host-mapped pinned block [obs 512 floats | out 512 granules {ticket, value}] and the ticket of the pending row
@@ -357,9 +380,6 @@ struct oprl_learner {
   unsigned long long* du_granules = nullptr;
   unsigned long long* g1_granules = nullptr;
   float* w3_snap = nullptr;
-  int no_rt2 = 0;              // OPRL_AMD_NO_RT2: phase 1's B roles stay on 16-row slices in the over-subscribed launches (tests / A-B)
-  int no_wide = 0;             // OPRL_AMD_NO_WIDE: never run role A / phase 2's critic pass on clusters of eight
-  int no_merge_twin = 0;       // OPRL_AMD_NO_RIDE bit 64: TD3's critics' tiles as a launch of their own
   bool xcd_local = false;      // XCD-local cluster exchanges (DdpgArgs::xcd_local): probed dispatcher, not OPRL_AMD_NO_XCD_LOCAL, cleared by an expired wait
   int xnc = kMaxCluster;       // members an exchange area of xbuf is laid out for
   unsigned long long* xbuf = nullptr;
@@ -430,9 +450,6 @@ struct oprl_learner {
   int chain_u = 1;             // step_n: updates the next whole-update launch runs (k_ddpg_chain)
   bool chain_pf_last = false;  // ... and whether its last update stages the rows of the update after it
   const float* chain_set1[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the other staging set (set 0 = the update's rows)
-  int no_chain = 0;            // (always 0: every whole update goes through k_ddpg_chain)
-  int chain_max = kChainMax;   // OPRL_AMD_CHAIN=n: at most n updates per launch
-  int no_whole = 0;            // OPRL_AMD_FORM=two / p2 / plain: two launches per update (merged phase 1, merged phase 2)
   bool whole_done = false;     // this update's actor phase was part of the critic phase's launch
   float* pack16[OPRL_MAX_CRITICS + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   float* pack16_t[OPRL_MAX_CRITICS + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -449,6 +466,7 @@ bool actor_due(const oprl_learner* h);
 hipError_t uc_alloc(void** out, size_t bytes);
 size_t net_ws_floats(const oprl_net& n, int B);
 int fresh32(const oprl_net* net, hipStream_t st);
+FusedForm fused_form(const oprl_learner* h, int B, bool dp_inline);
 DdpgArgs ddpg_args(oprl_learner* h, int B);
 int chain_rows(const oprl_learner* h, int B);
 void build_repack_items(const oprl_net* const* nets, int n_nets, int which,
@@ -462,7 +480,7 @@ int next_tp_tag(unsigned* counter, unsigned long long* xbuf, size_t xbuf_bytes, 
 const oprl_net& eff(const oprl_learner* h, const oprl_net& n);
 int check_device_error(const oprl_learner* h);
 void with_store(MlpArgs& a, const NetWs& ws, bool x, bool dy);
-hipError_t launch_dw_prof(const DwArgs& a, hipStream_t st);
+hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st);
 void fill_items(const oprl_net& n, const NetWs& ws, std::vector<DwItem>& v, int* tiles, bool small_partial_tiles = false,
                 float* pk16 = nullptr, float* pk16_t = nullptr, int pl = 1);
 DwArgs dw_build(oprl_learner* h, bool critic, int B, bool polyak, bool with_alpha);

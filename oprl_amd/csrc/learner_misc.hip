@@ -129,10 +129,10 @@ extern "C" int oprl_learner_debug_view(oprl_learner* h, int32_t which, const voi
   return OPRL_OK;
 }
 
-// Which LAUNCH FORM would an update of batch size B take right now?  The selection (learner.hip ddpg_args / critic_phase:
-// a dozen interacting conditions — precision, algorithm, batch size, cluster size, gradient export, the data-parallel
-// exchange, a shared chip, the environment switches) as numbers a test can hold against a table
-// (tests/test_gpu_forms.py), so that a mode falling off its fast form is a red test and not a line in a benchmark.
+// Which LAUNCH FORM would an update of batch size B take right now?  The decision (learner.hip fused_form: a dozen
+// interacting conditions — precision, algorithm, batch size, cluster size, gradient export, the data-parallel exchange, a
+// shared chip, the environment switches) as numbers a test can hold against a table (tests/test_gpu_forms.py), so that a
+// mode falling off its fast form is a red test and not a line in a benchmark.  Reads the learner only.
 //   out[0]  fused: 1 the fused phase kernels (DDPG / TD3 / SAC), 0 the generic launch sequence (TQC, no_fuse, odd shapes)
 //   out[1]  lean: 1 tp4.h's passes, 0 the generic tp3.h passes
 //   out[2]  form: 4 whole updates per launch (k_ddpg_chain), 3 both merged launches (phase 1 + critic tiles | phase 2 +
@@ -143,33 +143,24 @@ extern "C" int oprl_learner_debug_view(oprl_learner* h, int32_t which, const voi
 //   out[9]  XCD-local cluster exchanges    out[10] the learner was demoted to the shared-chip forms
 //   out[11] gradient-exporting learners: the form (as out[2]) of a data-parallel update whose exchange runs inside the dW
 //           tiles (peer windows, level 2) — 4 = the rank runs the single-GPU whole-update launch; others: 0
+//   out[12] rt2: 1 phase 1's B roles carry two row tiles per cluster, 2 ... and SAC's role A carries role C's pass, 0 neither
 extern "C" int oprl_learner_debug_form(oprl_learner* h, int32_t B, int32_t* out) {
   if (!h || !out || B < 1 || B > h->Bmax) { set_err("oprl_learner_debug_form: invalid argument"); return OPRL_ERR_INVALID; }
-  for (int i = 0; i < 12; ++i) out[i] = 0;
+  auto form_code = [](const FusedForm& f) { return f.whole ? 4 : ((f.merged & 3) == 3 ? 3 : ((f.merged & 1) ? 2 : 1)); };
+  for (int i = 0; i < 13; ++i) out[i] = 0;
   out[10] = h->shared_chip ? 1 : 0;
   out[8] = h->x2 ? 2 : (h->bf16 ? 1 : 0);
   if (!use_fused(h, B)) return OPRL_OK;
-  const DdpgArgs a = ddpg_args(h, B);
+  const FusedForm f = fused_form(h, B, h->dp_inline);
   out[0] = 1;
-  out[1] = fused_ddpg_is_lean(a) ? 1 : 0;
-  const bool whole = a.whole && B <= 256;
-  out[2] = whole ? 4 : ((a.merged & 3) == 3 ? 3 : ((a.merged & 1) ? 2 : 1));
-  out[3] = 1;
-  if (whole) {
-    const int slices = (B + kR - 1) / kR;
-    const bool fits = chain_rows(h, B) * slices <= h->n_cus;
-    out[3] = (h->no_chain || h->chain_flags == nullptr || !fits) ? 1 : h->chain_max;
-  }
-  out[4] = a.wide; out[5] = a.nc; out[6] = a.twin_split; out[7] = a.p2_pair;
-  out[8] = a.x2 ? 2 : (a.bf16 ? 1 : 0);
-  out[9] = a.xcd_local;
-  if (h->cfg.export_grads) {
-    const bool was = h->dp_inline;
-    h->dp_inline = true;
-    const DdpgArgs d = ddpg_args(h, B);
-    h->dp_inline = was;
-    out[11] = (d.whole && B <= 256) ? 4 : ((d.merged & 3) == 3 ? 3 : ((d.merged & 1) ? 2 : 1));
-  }
+  out[1] = f.lean ? 1 : 0;
+  out[2] = form_code(f);
+  out[3] = f.chain_max;
+  out[4] = f.wide; out[5] = f.nc; out[6] = f.twin_split; out[7] = f.p2_pair;
+  out[8] = f.x2 ? 2 : (f.bf16 ? 1 : 0);
+  out[9] = h->xcd_local ? 1 : 0;
+  if (h->cfg.export_grads) out[11] = form_code(fused_form(h, B, true));
+  out[12] = f.rt2;
   return OPRL_OK;
 }
 
@@ -299,7 +290,7 @@ extern "C" int oprl_mlp_backward(const oprl_net* net, const float* x0, int32_t k
   memset(&dw.ad, 0, sizeof dw.ad);
   set_adam(dw.ad, 0.0, 0.9, 0.999, 1e-8, 0.0);
   set_step(dw.ad, 1); dw.ad.grad_scale = 1.0f; dw.ad.do_adam = 0;
-  HIPC(launch_dw_prof(dw, st));
+  HIPC(launch_dw_prof(nullptr, dw, st));
   return OPRL_OK;
 }
 

@@ -84,7 +84,7 @@ def _ddpg_runs_whole_updates():
     from oprl_amd.logging import NullLogger
     t.manual_seed(0)
     algo = DDPG(logger=NullLogger(), state_dim=24, action_dim=6, device="cuda", max_batch=256, precision="bf16").create()
-    out = (C.c_int32 * 12)()
+    out = (C.c_int32 * 13)()
     assert algo.learner.lib.oprl_learner_debug_form(algo.learner.handle, 256, out) == 0
     return out[2] == 4
 

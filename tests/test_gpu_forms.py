@@ -2,8 +2,8 @@
 
 Which kernels an update runs — whole updates per launch (k_ddpg_chain), the merged phase launches, the plain phase + dW
 launches, the generic sequence; lean or generic passes; clusters of eight; XCD-local exchanges — is decided by a dozen
-interacting conditions in csrc/learner.hip (ddpg_args, critic_phase).  oprl_learner_debug_form reports the decision as
-twelve numbers; tests/golden/launch_forms.json (tools/form_table.py, MI355X) holds them for {DDPG, TD3, SAC, TQC} x
+interacting conditions in csrc/learner.hip (fused_form).  oprl_learner_debug_form reports the decision as
+thirteen numbers; tests/golden/launch_forms.json (tools/form_table.py, MI355X) holds them for {DDPG, TD3, SAC, TQC} x
 {f32, x2, bf16} x {plain, export_grads, set_cluster(4), five environment switches} x B in {1, 8, 100, 128, 256, 512, 1024}.
 A mode that falls off its fast form is a red test here, not a line in a benchmark table.  Reference: none (the reference
 has one path, autograd: /root/reference/src/oprl/algos/ddpg.py:61-107)."""
@@ -41,7 +41,7 @@ def test_launch_form_matches_the_table(row):
     got = form_table.form_rows(row["algo"], row["precision"], variant)
     for B, want in row["forms"].items():
         have = list(got[int(B)])
-        diff = {FIELDS[i]: (have[i], want[i]) for i in range(12) if have[i] != want[i]}
+        diff = {FIELDS[i]: (have[i], want[i]) for i in range(len(FIELDS)) if have[i] != want[i]}
         assert not diff, f"{_id(row)} B={B}: (got, table) {diff}"
 
 

@@ -574,24 +574,15 @@ def test_tqc_wide_dw_equals_small_tiles(monkeypatch, tmp_path):
     gradient up to the summation order over the minibatch, same Adam / Polyak / pack epilogue."""
     from oprl_amd.algos.tqc import TQC
     from oprl_amd.logging import NullLogger
-    import subprocess, sys, os
-    # the switch is read once per process: run the small-tile learner in a child
-    code = (
-        "import torch as t, sys; sys.path.insert(0, %r)\n"
-        "from oracle import fixtures as fx\n"
-        "from oprl_amd.algos.tqc import TQC\n"
-        "from oprl_amd.logging import NullLogger\n"
-        "t.manual_seed(0)\n"
-        "a = TQC(logger=NullLogger('/tmp/oprl_amd_test'), state_dim=24, action_dim=6, device='cuda', max_batch=256).create()\n"
-        "for step in range(3):\n"
-        "    a.update(*[x.cuda() for x in fx.make_batch(25 + step, 256, 24, 6)])\n"
-        "t.cuda.synchronize()\n"
-        "t.save({m: getattr(a, m)._oprl_arena.cpu() for m in ('actor', 'critic', 'critic_target')}, sys.argv[1])\n"
-    ) % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = str(tmp_path / "dw_small.pt")
-    env = dict(os.environ, OPRL_AMD_NO_RIDE="16")
-    subprocess.run([sys.executable, "-c", code, out], check=True, env=env, timeout=300)
-    ref = t.load(out)
+    # (the switch is read when the learner is created: the small-tile learner first, then the default one)
+    monkeypatch.setenv("OPRL_AMD_NO_RIDE", "16")
+    t.manual_seed(0)
+    small = TQC(logger=NullLogger("/tmp/oprl_amd_test"), state_dim=24, action_dim=6, device="cuda", max_batch=256).create()
+    for step in range(3):
+        small.update(*[x.cuda() for x in fx.make_batch(25 + step, 256, 24, 6)])
+    t.cuda.synchronize()
+    ref = {m: getattr(small, m)._oprl_arena.cpu() for m in ("actor", "critic", "critic_target")}
+    monkeypatch.delenv("OPRL_AMD_NO_RIDE")
     t.manual_seed(0)
     wide = TQC(logger=NullLogger("/tmp/oprl_amd_test"), state_dim=24, action_dim=6, device="cuda", max_batch=256).create()
     for step in range(3):
@@ -620,8 +611,9 @@ def test_two_row_tiles_per_cluster_equal_one_bitwise(algo, B, prec, monkeypatch)
     fragments of the pass fetched once per 32 rows, half the workgroups of that role.  Per tile the arithmetic is the one-tile
     pass's (same fragments, same accumulator chains, same member order in the exchange): the parameters after several
     updates — through update() on caller-supplied rows and through step_n (in-kernel gather, then staged rows) — are
-    bit-identical to OPRL_AMD_NO_RT2=1, and the form really is taken (the launch grid differs: checked through the rate of
-    a wrong answer, i.e. the switch must matter to debug state — here: both learners finite and equal)."""
+    bit-identical to OPRL_AMD_NO_RT2=1, and the form really is taken: debug_form's rt2 is >= 1 for the twin critics (2 for
+    SAC's role C on role A's pass) and 0 under NO_RT2=1.  DDPG's single B role keeps one tile (measured slower on two): its
+    cases pin that the form is NOT taken, rt2 = 0 with and without the switch."""
     from tests.test_gpu_callers import _filled_buffer
 
     def make():
@@ -637,6 +629,8 @@ def test_two_row_tiles_per_cluster_equal_one_bitwise(algo, B, prec, monkeypatch)
     for no_rt2 in (("1", "2", "0") if algo == "sac" else ("1", "0")):
         monkeypatch.setenv("OPRL_AMD_NO_RT2", no_rt2)
         a = make()
+        want = 0 if (algo == "ddpg" or no_rt2 == "1") else (1 if no_rt2 == "2" or algo == "td3" else 2)
+        assert a.learner.debug_form(B)["rt2"] == want, (algo, B, prec, no_rt2)
         for step in range(3):
             batch = [x.cuda() for x in fx.make_batch(610 + step, B, S, A)]
             a.update(*batch)

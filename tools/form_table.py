@@ -1,5 +1,5 @@
 """Prints the launch-form table tests/test_gpu_forms.py holds (needs a GPU): for every (algorithm, precision, variant) the
-twelve numbers of oprl_learner_debug_form at each batch size.  Variants: plain, export_grads, set_cluster(4) (a learner
+thirteen numbers of oprl_learner_debug_form at each batch size.  Variants: plain, export_grads, set_cluster(4) (a learner
 that shares the chip), and a few environment switches."""
 import ctypes as C
 import os
@@ -11,7 +11,7 @@ import bench
 
 BATCHES = (1, 8, 100, 128, 256, 512, 1024)      # (128: the batch the reference's scripts train at, trainers/base_trainer.py:28)
 FIELDS = ["fused", "lean", "form", "updates_per_chain_launch", "wide", "nc", "twin_split", "p2_pair", "arith", "xcd_local",
-          "shared_chip", "dp_inline_form"]
+          "shared_chip", "dp_inline_form", "rt2"]
 ALGOS = {"DDPG": (24, 6, {}), "TD3": (17, 6, {}), "SAC": (24, 6, {}), "TQC": (24, 6, {})}
 VARIANTS = [("plain", {}, {}, None), ("export_grads", dict(export_grads=True), {}, None), ("cluster4", {}, {}, 4),
             ("FORM=two", {}, {"OPRL_AMD_FORM": "two"}, None), ("FORM=plain", {}, {"OPRL_AMD_FORM": "plain"}, None),
@@ -37,7 +37,7 @@ def form_rows(algo_name, prec, variant):
     L = algo.learner
     if cluster is not None:
         L.set_cluster(cluster)
-    out = (C.c_int32 * 12)()
+    out = (C.c_int32 * len(FIELDS))()
     rows = {}
     for B in BATCHES:
         rc = L.lib.oprl_learner_debug_form(L.handle, B, out)
