@@ -36,7 +36,7 @@ import numpy as np
 import torch as t
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0  # nn_models.py:11
-F32 = t.float32
+F32 = t.float32       # (the updates compute in the dtype of their inputs: float32, or float64 for a high-precision run)
 
 
 # --------------------------------------------------------------------------- #
@@ -148,7 +148,7 @@ def mlp_backward(p: list[t.Tensor], acts: list[t.Tensor], dout: t.Tensor,
             else:
                 dx = _q(dz, p[2 * l]) @ _q(p[2 * l], p[2 * l])
         if l > 0:
-            mask = (acts[l] > 0).to(F32)     # threshold_backward on the ReLU output
+            mask = (acts[l] > 0).to(acts[l].dtype)     # threshold_backward on the ReLU output
             parts = None
             if row_scale is not None and n_layers == 3 and l == 1 and dz.shape[1] % 8 == 0:
                 # (members of the cluster: four — eight for the chain form's critic pass, the backward that wants dx only)
@@ -242,7 +242,7 @@ def gaussian_backward_seed(cache, d_a, d_logp, action_dim):
     d_mu = du
     d_ls = du * std * eps - d_logp
     raw = cache["log_std_raw"]
-    mask = ((raw >= LOG_STD_MIN) & (raw <= LOG_STD_MAX)).to(F32)
+    mask = ((raw >= LOG_STD_MIN) & (raw <= LOG_STD_MAX)).to(raw.dtype)
     return t.cat([d_mu, d_ls * mask], dim=1)
 
 
@@ -265,7 +265,7 @@ class DDPGOracle:
 
     def update(self, s, a, r, d, s2):
         B = s.shape[0]
-        d = d.to(F32)
+        d = d.to(s.dtype)
         a2, _ = det_policy_forward(self.actor_target, s2)
         q_next = q_forward(self.critic_target, s2, a2)[-1]
         y = r + (1.0 - d) * self.gamma * q_next
@@ -319,7 +319,7 @@ class TD3Oracle:
     def update(self, s, a, r, d, s2, noise):
         """noise: the N(0,1) draw of td3.py:98 (randn_like(action))."""
         B = s.shape[0]
-        d = d.to(F32)
+        d = d.to(s.dtype)
         acts1 = q_forward(self._q(self.critic, 0), s, a)
         acts2 = q_forward(self._q(self.critic, 1), s, a)
         q1, q2 = acts1[-1], acts2[-1]
@@ -378,7 +378,7 @@ class SACOracle:
 
     def update(self, s, a, r, d, s2, eps_next, eps_cur):
         B = s.shape[0]
-        d = d.to(F32)
+        d = d.to(s.dtype)
         acts1 = q_forward(self._q(self.critic, 0), s, a)
         acts2 = q_forward(self._q(self.critic, 1), s, a)
         q1, q2 = acts1[-1], acts2[-1]
@@ -397,7 +397,7 @@ class SACOracle:
         c2 = q_forward(self._q(self.critic, 1), s, pi)
         qa1, qa2 = c1[-1], c2[-1]
         actor_loss = self.alpha * logp.mean() - t.min(qa1, qa2).mean()
-        w1 = (qa1 < qa2).to(F32) + 0.5 * (qa1 == qa2).to(F32)
+        w1 = (qa1 < qa2).to(qa1.dtype) + 0.5 * (qa1 == qa2).to(qa1.dtype)
         _, dx1 = mlp_backward(self._q(self.critic, 0), c1, -w1 / B, need_dx=True, need_dw=False)
         _, dx2 = mlp_backward(self._q(self.critic, 1), c2, -(1 - w1) / B, need_dx=True, need_dw=False)
         d_a = dx1[:, self.S:] + dx2[:, self.S:]
@@ -429,8 +429,8 @@ def quantile_huber_loss(quantiles: t.Tensor, samples: t.Tensor):
     delta = samples[:, None, None, :] - quantiles[:, :, :, None]
     ad = delta.abs()
     huber = t.where(ad > 1, ad - 0.5, delta * delta * 0.5)
-    tau = t.arange(Q).float() / Q + 1 / 2 / Q
-    wgt = (tau[None, None, :, None] - (delta < 0).float()).abs()
+    tau = t.arange(Q, dtype=quantiles.dtype) / Q + 1 / 2 / Q
+    wgt = (tau[None, None, :, None] - (delta < 0).to(delta.dtype)).abs()
     loss = (wgt * huber).mean()
     dh = t.where(ad > 1, t.sign(delta), delta)
     dz = -(wgt * dh).sum(-1) / float(B * N * Q * M)
@@ -458,8 +458,8 @@ class TQCOracle:
 
     def update(self, s, a, r, d, s2, eps_next, eps_cur):
         B = s.shape[0]
-        d = d.to(F32)
-        alpha = self.log_alpha.exp().to(F32)
+        d = d.to(s.dtype)
+        alpha = self.log_alpha.exp().to(s.dtype)
         a2, logp2, _ = gaussian_forward(self.actor, s2, eps_next, self.A)
         next_z = t.stack([q_forward(c, s2, a2)[-1] for c in self.critics_target], dim=1)
         sorted_z, _ = t.sort(next_z.reshape(B, -1))
@@ -477,8 +477,8 @@ class TQCOracle:
 
         pi, logp, cache = gaussian_forward(self.actor, s, eps_cur, self.A)
         alpha_grad = -(logp + self.target_entropy).mean().to(t.float64)
-        d_a = t.zeros(B, self.A)
-        zsum = t.zeros(B, 1)
+        d_a = t.zeros(B, self.A, dtype=s.dtype)
+        zsum = t.zeros(B, 1, dtype=s.dtype)
         for n in range(self.N):
             acts = q_forward(self.critics[n], s, pi)
             zsum += acts[-1].mean(1, keepdim=True)

@@ -20,14 +20,18 @@ def _ddpg(**kw):
 
 
 def _filled_buffer(n_eps=6, L=50, seed=3):
+    """n_eps - 1 finished episodes of L, L - 1, ... transitions; the last transition of each is a real terminal
+    (done = True: 5 of the default 240), so the row gathers of the step_n tests that share this buffer may see done
+    rows (tests/test_gpu_bench_parity.py asserts that they do, on the benchmark's replay)."""
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
     buf = EpisodicReplayBuffer(buffer_size_transitions=n_eps * L, state_dim=24, action_dim=6,
                                max_episode_lenth=L, device="cuda", seed=seed).create()
     rs = np.random.RandomState(0)
     for e in range(n_eps - 1):
         for i in range(L - e):
+            last = i == L - e - 1
             buf.add_transition(rs.standard_normal(24).astype(np.float32), rs.uniform(-1, 1, 6),
-                               float(rs.uniform()), False, episode_done=(i == L - e - 1))
+                               float(rs.uniform()), last, episode_done=last)
     return buf
 
 
