@@ -224,18 +224,18 @@ struct TqcJob {
 };
 
 struct PrefetchJob;
-struct DwArgs {                         // host-side description of one k_dw_adam launch
-  const DwItem* items;                 // HOST array
-  int n_items; int total_tiles; int B;
-  int n_part;                          // members of the tensor-parallel cluster that wrote dz1 partials
+struct DwArgs {                         // host-side description of one k_dw_adam launch (learner.hip dw_args)
+  const DwItem* items = nullptr;       // HOST array
+  int n_items = 0, total_tiles = 0, B = 0;
+  int n_part = 1;                      // members of the tensor-parallel cluster that wrote dz1 partials
   int dy_tiled = 0;                    // 1: those partial buffers are tile-major (written by the tp4 passes, Tp3Store::dY0_tile_rows = B)
-  AdamScalars ad;
-  long long* trace;                    // debug stamps (tools/trace_slice.py) or null
-  int use_row_scale;                   // 1: the slice kernels left unit-seed dz rows (lean fused path)
+  AdamScalars ad = {};
+  long long* trace = nullptr;          // debug stamps (tools/trace_slice.py) or null
+  int use_row_scale = 0;               // 1: the slice kernels left unit-seed dz rows (lean fused path)
   int skip32 = 0;                      // 1: do not write the fp32 packs (pf / pb / tpf): a PrecX2 learner's fused update, whose kernels read the fp16 packs only
   int skip32_wide = 0;                 // 1: ... of the WIDE layers only (TQC's 512 x 512 layers in a 16-bit mode: the hidden-layer launches read the 16-bit packs)
   int no_wide = 0;                     // 1: no 64 x 64-tile launch for the wide layers (OPRL_AMD_NO_RIDE bit 16: Switches::no_wide_dw)
-  int apply_only;                      // 1: no GEMM — the gradient is read from w_g / b_g (data-parallel apply after the all-reduce)
+  int apply_only = 0;                  // 1: no GEMM — the gradient is read from w_g / b_g (data-parallel apply after the all-reduce)
   const DwXchg* xchg = nullptr;       // data-parallel: all-reduce every gradient tile over the peer windows inside this launch
   AlphaJob alpha;                      // optional: the temperature step rides on this launch (one more workgroup)
   const PrefetchJob* prefetch = nullptr;   // optional: the next update's minibatch rows as riders of this launch (batch_rows.h prefetch_rows_direct)

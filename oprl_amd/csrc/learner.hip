@@ -671,10 +671,8 @@ FusedForm fused_form(const oprl_learner* h, int B, bool dp_inline) {
   // (twin critics only — TD3, SAC: their two B roles then share the first dispatch round; measured, r06-6: SAC humanoid
   // B = 1024 - 3.7 us per update in every mode, TD3 B = 512 - 4.7, SAC B = 512 - 5; a single critic's one B role on half the
   // workgroups only lengthens the wait of role A behind it: DDPG B = 512 + 1.8 us, B = 1024 + 2.4 .. 4)
-  // (!prefetch_p1 never decides: step_n sets it only where `merged` != 0, and it sets it FROM `merged` — so nothing
-  // above may read prefetch_p1)
   f.rt2 = (sw.no_rt2 != 1 && h->nc == 2 && f.merged == 0 && (f.wide & 1) == 0 && f.nc == 4 && (slices & 15) == 0 &&
-           (2 + h->nc) * 4 * slices > h->n_cus && !h->prefetch_p1) ? 1 : 0;
+           (2 + h->nc) * 4 * slices > h->n_cus) ? 1 : 0;
   // SAC there: role A's first pass — the online actor on s' — also carries role C's pass, the same actor on s (tp4_forward2;
   // bit-identical): role C's dispatch round is not launched (r06-13; OPRL_AMD_NO_RT2=2 keeps role C)
   // (where role A alone fills the chip — humanoid B = 1024: -3.1 us x2, -2.1 f32 / bf16 per update; at B = 512 role C ran
@@ -774,7 +772,7 @@ DdpgArgs ddpg_args(oprl_learner* h, int B) {
 
 // DDPG runs fused for every batch size (generic tp3.h passes when the lean ones do not fit);
 // TD3's and SAC's fused kernels exist in the lean form only, otherwise the generic launch sequence is used
-bool use_fused(oprl_learner* h, int B) {
+bool use_fused(const oprl_learner* h, int B) {
   if (!h->fused) return false;
   if (h->cfg.algo == OPRL_DDPG) return true;
   return fused_form(h, B, h->dp_inline).lean;
@@ -782,74 +780,115 @@ bool use_fused(oprl_learner* h, int B) {
 
 // The temperature step of this update as a job for the actor's dW launch (one more workgroup), when nothing
 // but this rank's own Adam step is wanted of it; otherwise (gradient export, exchange inside the dW launch)
-// the caller launches k_alpha_step itself.
+// the caller launches k_alpha_step itself (alpha_step).
 bool alpha_rides(const oprl_learner* h) {
   return alpha_ptr(h) != nullptr && !h->cfg.export_grads && !h->dp_inline;
 }
-AlphaJob alpha_job(oprl_learner* h, int B) {
+AlphaJob alpha_job(const oprl_learner* h, int B, int step) {
   const oprl_learner_config& c = h->cfg;
-  h->opt_step_alpha += 1;
   AlphaJob j;
   j.log_alpha = c.log_alpha; j.m = c.log_alpha_m; j.v = c.log_alpha_v; j.logp = h->logp; j.B = B;
   j.target_entropy = (float)c.hp.target_entropy;
   j.lr = c.hp.lr_alpha; j.beta1 = c.hp.beta1; j.beta2 = c.hp.beta2; j.eps = c.hp.adam_eps;
-  j.bc1 = 1.0 - std::pow(c.hp.beta1, (double)h->opt_step_alpha);
-  j.bc2_sqrt = std::sqrt(1.0 - std::pow(c.hp.beta2, (double)h->opt_step_alpha));
+  j.bc1 = 1.0 - std::pow(c.hp.beta1, (double)step);
+  j.bc2_sqrt = std::sqrt(1.0 - std::pow(c.hp.beta2, (double)step));
   return j;
 }
 
-// (dw_build advances the optimiser's step count: call it once per launch, merged or not)
-DwArgs dw_build(oprl_learner* h, bool critic, int B, bool polyak, bool with_alpha) {
+// The temperature's Adam step as a launch of its own (k_alpha_step), step `step`: B > 0 from this update's log pi
+// (a gradient-exporting learner also leaves the gradient in alpha_grad), B = 0 from the all-reduced gradient in alpha_grad
+hipError_t alpha_step(const oprl_learner* h, int B, int step, float grad_scale, hipStream_t st) {
+  const oprl_learner_config& c = h->cfg;
+  const bool from_grad = B == 0;
+  return launch_alpha_step(c.log_alpha, c.log_alpha_m, c.log_alpha_v, from_grad ? nullptr : h->logp, from_grad ? 1 : B,
+                           (float)c.hp.target_entropy, c.hp.lr_alpha, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, step,
+                           !from_grad && c.export_grads ? h->alpha_grad : nullptr, from_grad ? h->alpha_grad : nullptr,
+                           grad_scale, st);
+}
+
+// this update's temperature step where it did not ride on the actor's dW launch
+int temperature_step(oprl_learner* h, int B, hipStream_t st) {
+  if (alpha_ptr(h) == nullptr || alpha_rides(h)) return OPRL_OK;
+  HIPC(alpha_step(h, B, h->opt_step_alpha + 1, 1.0f, st));
+  h->opt_step_alpha += 1;
+  return OPRL_OK;
+}
+
+// The dW + Adam (+ Polyak) launch of the critic(s) or the actor at batch B as the optimiser's step `step`.  Reads the
+// learner only: the caller commits the step (dw_commit) once the launch that carries it is out.  B = 0: the data-parallel
+// apply, fed from the all-reduced gradient arena (w_g / b_g) instead of the GEMM.
+// The critic's targets move when the actor is due (TD3: on actor steps only, td3.py:135-146), the actor's when it has any.
+DwArgs dw_args(const oprl_learner* h, bool critic, int B, int step) {
   const oprl_learner_config& c = h->cfg;
   DwArgs dw;
-  if (with_alpha) dw.alpha = alpha_job(h, B);
-  if (critic) {
-    h->opt_step_critic += 1;
-    dw.items = h->items_host.data(); dw.n_items = h->n_items_critic; dw.total_tiles = h->tiles_critic;
-    dw.ad = adam_scalars(h, c.hp.lr_critic, h->opt_step_critic, polyak, 1.0f);
-  } else {
-    h->opt_step_actor += 1;
-    dw.items = h->items_host.data() + h->n_items_critic; dw.n_items = h->n_items_actor;
-    dw.total_tiles = h->tiles_actor;
-    dw.ad = adam_scalars(h, c.hp.lr_actor, h->opt_step_actor, polyak, 1.0f);
-  }
+  dw.items = h->items_host.data() + (critic ? 0 : h->n_items_critic);
+  dw.n_items = critic ? h->n_items_critic : h->n_items_actor;
+  dw.total_tiles = critic ? h->tiles_critic : h->tiles_actor;
+  dw.ad = adam_scalars(h, critic ? c.hp.lr_critic : c.hp.lr_actor, step,
+                       critic ? actor_due(h) : c.actor.theta_target != nullptr, 1.0f);
   dw.B = B;
-  const bool fused = use_fused(h, B);
-  dw.n_part = fused ? h->nc_cluster(B) : 1;
-  dw.trace = (fused && h->trace != nullptr) ? h->trace + (size_t)(critic ? 4 : 5) * 64 * kTraceStamps * 2 : nullptr;
-  dw.apply_only = 0;
-  // the lean phase 1 leaves unit-seed dz rows (tp4_scalar_fb): each critic's TD-error seed, dY of
-  // its output layer, is applied per row (DwItem::rs)
-  const bool lean = fused && fused_form(h, B, h->dp_inline).lean;
-  dw.use_row_scale = (critic && lean) ? 1 : 0;
-  dw.dy_tiled = (lean && dw.n_part > 1) ? 1 : 0;      // the lean passes leave tile-major dz1 partials
-  if (h->x2 && lean && !c.export_grads) {             // the PrecX2 kernels read the fp16 packs only (fresh32)
-    dw.skip32 = 1;
-    h->stale32[critic ? 0 : 1] = true;
+  if (B == 0) {
+    dw.apply_only = 1;
+    return dw;
   }
-  if (h->fchain) h->stale32[critic ? 0 : 1] = true;   // (the tiles write the mirrors: the caller's packs fall behind)
+  dw.trace = h->trace != nullptr ? h->trace + (size_t)(critic ? 4 : 5) * 64 * kTraceStamps * 2 : nullptr;   // slot 4 / 5
+  if (use_fused(h, B)) {
+    // the lean phase 1 leaves unit-seed dz rows (tp4_scalar_fb): each critic's TD-error seed, dY of its output layer, is
+    // applied per row (DwItem::rs); the lean passes leave tile-major dz1 partials
+    const bool lean = fused_form(h, B, h->dp_inline).lean;
+    dw.n_part = h->nc_cluster(B);
+    dw.use_row_scale = (critic && lean) ? 1 : 0;
+    dw.dy_tiled = (lean && dw.n_part > 1) ? 1 : 0;
+    dw.skip32 = (h->x2 && lean && !c.export_grads) ? 1 : 0;     // the PrecX2 kernels read the fp16 packs only (fresh32)
+  } else {
+    dw.n_part = tp_generic(h, critic ? c.critics[0] : c.actor, B) ? 4 : 1;
+    dw.dy_tiled = dw.n_part > 1 ? 1 : 0;               // k_mlp_slice_tp runs the tp4 passes
+    // TQC in a 16-bit mode: the critics' 512 x 512 layers run through the 16-bit packs (layerwise.hip); their fp32
+    // packs — a third of the wide dW launch's stores — are left stale and rebuilt by whoever reads them (fresh32)
+    dw.skip32_wide = (critic && c.algo == OPRL_TQC && (h->x2 || h->bf16) && h->lazy_wide && !c.export_grads &&
+                      !h->sw.no_layerwise) ? 1 : 0;
+  }
   return dw;
 }
 
-int dw_step(oprl_learner* h, bool critic, int B, bool polyak, hipStream_t st, bool with_alpha = false,
-            const PrefetchJob* prefetch = nullptr) {
-  DwArgs dw = dw_build(h, critic, B, polyak, with_alpha);
+// The launch of `dw` is out: its optimiser has taken `steps` steps (and the temperature's one, if it rode), and the fp32
+// packs it did not write (skip32, skip32_wide) or wrote the uncached mirrors of (fchain) fall behind the masters
+void dw_commit(oprl_learner* h, bool critic, const DwArgs& dw, int steps) {
+  (critic ? h->opt_step_critic : h->opt_step_actor) += steps;
+  if (dw.alpha.log_alpha != nullptr) h->opt_step_alpha += 1;
+  if (dw.skip32 || h->fchain) h->stale32[critic ? 0 : 1] = true;
+  if (dw.skip32_wide) h->stale_wide = true;
+}
+
+// the peer-window exchange of a data-parallel dW launch whose (first) exchange has sequence number `seq`
+DwXchg xchg_args(const oprl_learner* h, unsigned long long seq) {
+  const P2pState& P = h->p2p;
+  DwXchg X;
+  memset((void*)&X, 0, sizeof X);
+  for (int r = 0; r < kDwXchgMaxWorld; ++r) X.peer[r] = r < P.world ? P.peer[r] + P.tile_off : nullptr;
+  X.window = P.window + P.tile_off;
+  X.world = P.world; X.rank = P.rank; X.max_tiles = h->p2p_max_tiles;
+  X.seq = seq; X.parity = (int)(seq & 1);
+  X.err = h->err_dev;
+  return X;
+}
+
+// one dW + Adam launch of its own (the actor's carries the temperature step where it rides)
+int dw_step(oprl_learner* h, bool critic, int B, hipStream_t st, const PrefetchJob* prefetch = nullptr) {
+  DwArgs dw = dw_args(h, critic, B, (critic ? h->opt_step_critic : h->opt_step_actor) + 1);
+  if (!critic && alpha_rides(h)) dw.alpha = alpha_job(h, B, h->opt_step_alpha + 1);
   dw.prefetch = prefetch;
+  const unsigned long long seq = h->p2p.tile_seq + 1;
   if (h->dp_inline) {
     // data-parallel on peer windows: this launch all-reduces its tiles itself and runs Adam on the mean
-    P2pState& P = h->p2p;
-    P.tile_seq += 1;
-    DwXchg& X = h->dw_xchg;
-    for (int r = 0; r < kDwXchgMaxWorld; ++r) X.peer[r] = r < P.world ? P.peer[r] + P.tile_off : nullptr;
-    X.window = P.window + P.tile_off;
-    X.world = P.world; X.rank = P.rank; X.parity = (int)(P.tile_seq & 1); X.max_tiles = h->p2p_max_tiles;
-    X.seq = P.tile_seq;
-    X.err = h->err_dev;
-    dw.xchg = &X;
+    h->dw_xchg = xchg_args(h, seq);
+    dw.xchg = &h->dw_xchg;
     dw.ad.do_adam = 1;
-    dw.ad.grad_scale = 1.0f / (float)P.world;
+    dw.ad.grad_scale = 1.0f / (float)h->p2p.world;
   }
   HIPC(launch_dw_prof(h, dw, st));
+  dw_commit(h, critic, dw, 1);
+  if (h->dp_inline) h->p2p.tile_seq = seq;
   return OPRL_OK;
 }
 
@@ -872,6 +911,136 @@ MlpArgs actor_forward_args(oprl_learner* h, const float* s, int B, const float* 
 }
 
 // ------------------------------------------------------------ critic phase
+// The gates of the dW tiles that ride on a phase launch (DwGate): the common fields of the critic's tiles (phase 1's
+// roles flag their rows, the TD-error seeds come as granules, one per row) ...
+void critic_gate(const oprl_learner* h, const DdpgArgs& fa, int B, DwGate& g) {
+  const int slices = (B + kR - 1) / kR;
+  g.rows = fa.gate_flags; g.n_rows = 4 * slices * h->nc;
+  g.seed = fa.y_granules; g.n_seed = B;
+  g.late_dY = h->ws_critic[0].dY[h->cfg.critics[0].n_layers - 1];
+  g.tag = h->epoch; g.spin = h->debug_expire == 7 ? 0 : (1 << 20);
+  g.err = h->err_dev; g.err_code = (1u << 8) | 7u;      // KERN_PHASE1, SITE_DW_GATE (csrc/tp3.h)
+}
+// ... and of the actor's tiles (they wait for the du granules; items = the actor's layers 0, 1, 2)
+void actor_gate(const oprl_learner* h, const DdpgArgs& fa, int B, DwGate& g) {
+  g.seed = fa.du_granules; g.n_seed = B;
+  g.tag = h->epoch; g.spin = h->debug_expire == 7 ? 0 : (1 << 20);
+  g.err = h->err_dev; g.err_code = (2u << 8) | 7u;      // KERN_PHASE2, SITE_DW_GATE (csrc/tp3.h)
+  g.kind[0] = 2; g.kind[1] = 1; g.kind[2] = 0; g.kind[3] = 0;
+  g.h2 = h->ws_actor.X[2];
+  g.w3 = fa.w3_snap;
+  g.g1 = fa.g1_granules;
+  g.n_act = h->A;
+}
+
+// The whole update as k_ddpg_chain launches: phase 1's roles, the critic's tiles, role U + the actor's tiles, the critic
+// pass, of U updates (step_n: chain_u) per launch.  What the launch advances — the optimisers' step counts, the epochs,
+// the exchange tags and, data parallel, this rank's tile sequence — is committed once it is out: after an error return
+// Adam's bias corrections and the peers' sequence numbers are where they were.
+int whole_update(oprl_learner* h, DdpgArgs& fa, const FusedForm& form, int B, hipStream_t st) {
+  const int slices = (B + kR - 1) / kR;
+  const int U = h->chain_u < form.chain_max ? h->chain_u : form.chain_max;
+  const int step_c = h->opt_step_critic + 1, step_a = h->opt_step_actor + 1;     // update 0's
+  fa.prefetch_next = 0;
+  DwKArgs kd;
+  DwKArgs4 kc, ka;
+  auto compact = [&](const DwKArgs& k, DwKArgs4* o) {
+    for (int j = 0; j < kDwFusedItems; ++j) { o->tile_end[j] = k.tile_end[j]; o->items[j] = k.items[j]; }
+    o->n_items = k.n_items; o->B = k.B; o->n_part = k.n_part; o->dy_tiled = k.dy_tiled; o->ad = k.ad; o->trace = k.trace;
+    o->gate = k.gate;
+    memset((void*)&o->xchg, 0, sizeof o->xchg);
+  };
+  const DwArgs dc = dw_args(h, true, B, step_c);
+  if (fill_dw_kargs(dc, &kd, 64) < 0 || dc.n_items > kDwFusedItems) { set_err("whole update: bad critic dW table"); return OPRL_ERR_INVALID; }
+  critic_gate(h, fa, B, kd.gate);
+  kd.gate.done = fa.ct_done; kd.gate.what_if = h->debug_expire;
+  fa.n_ct = kd.tile_end[kDwMaxItems - 1];
+  if (fa.n_ct > 192 - 64) { set_err("whole update: too many critic tiles"); return OPRL_ERR_INVALID; }
+  compact(kd, &kc);
+  const DwArgs da = dw_args(h, false, B, step_a);
+  if (fill_dw_kargs(da, &kd, 64) < 0 || da.n_items != 3) { set_err("whole update: bad actor dW table"); return OPRL_ERR_INVALID; }
+  actor_gate(h, fa, B, kd.gate);
+  kd.gate.what_if = h->debug_expire;
+  compact(kd, &ka);
+  // (every tile must find a role-B / role-C workgroup to be the continuation of: 8 per slice)
+  const int max_tiles = kc.tile_end[kDwFusedItems - 1] > ka.tile_end[kDwFusedItems - 1] ? kc.tile_end[kDwFusedItems - 1] : ka.tile_end[kDwFusedItems - 1];
+  const int t_rows = chain_tile_rows(max_tiles, slices);
+  // (the form's fit test counted the same 16 x 64 tiles from the learner's item table: chain_rows)
+  if (16 + t_rows != chain_rows(h, B)) { set_err("internal: whole update of %d grid rows, the form counted %d", 16 + t_rows, chain_rows(h, B)); return OPRL_ERR_STATE; }
+  const unsigned long long seq = h->p2p.tile_seq + 1;
+  if (h->dp_inline) {
+    // data parallel on peer windows: the tiles of this launch all-reduce their gradients themselves and run Adam on
+    // the mean (dw_tile_x2.h): exchange sequence numbers seq + 2 u (critic) / + 1 (actor) for update u of the launch
+    if (max_tiles > h->p2p_max_tiles) { set_err("data-parallel whole update: the windows hold %d tiles, the launch has %d", h->p2p_max_tiles, max_tiles); return OPRL_ERR_STATE; }
+    kc.xchg = xchg_args(h, seq);
+    kc.xchg.parity = 0;           // (parity = the exchange's sequence number & 1, formed in the tile)
+    ka.xchg = kc.xchg;
+    kc.ad.do_adam = 1; ka.ad.do_adam = 1;
+    kc.ad.grad_scale = 1.0f / (float)h->p2p.world; ka.ad.grad_scale = 1.0f / (float)h->p2p.world;
+  }
+  // SEVERAL updates as one launch (k_ddpg_chain): the tables above are update 0's; what changes per update — Adam's
+  // bias-correction terms, epochs, exchange tags, the staging set — is in ChainArgs
+  ChainArgs ca;
+  memset((void*)&ca, 0, sizeof ca);
+  ca.n_upd = U;
+  ca.first_gather = fa.src.gather;
+  ca.pf_last = h->chain_pf_last ? 1 : 0;
+  ca.trace_u = U - 1;
+  ca.rows = 16 + t_rows;
+  ca.order = h->sw.chain_order;
+  // (the optimisers' step counts advance once per update and net: only Adam's bias-correction terms change from update
+  // to update — a table build per update and net was 8 of the 17 us a step_n(20) call took to enqueue)
+  AdamScalars sc_ = kc.ad, sa_ = ka.ad;
+  for (int u = 0; u < U; ++u) {
+    set_step(sc_, step_c + u);
+    set_step(sa_, step_a + u);
+    ca.c_step[u] = sc_.step_size_host; ca.c_bc2[u] = sc_.bc2_sqrt_host;
+    ca.a_step[u] = sa_.step_size_host; ca.a_bc2[u] = sa_.bc2_sqrt_host;
+  }
+  ca.set0[0] = fa.src.s; ca.set0[1] = fa.src.a; ca.set0[2] = fa.src.r; ca.set0[3] = fa.src.d; ca.set0[4] = fa.src.s2;
+  for (int i = 0; i < 5; ++i) ca.set1[i] = h->chain_set1[i];
+  if ((U > 1 || ca.pf_last) && ca.set1[0] == nullptr) { set_err("chain launch: no second staging set"); return OPRL_ERR_STATE; }
+  ca.ct_fin = h->chain_flags; ca.at_fin = h->chain_flags + 192; ca.pf_done = h->chain_flags + 384;
+  for (int w = 0; w < 4; ++w)
+    for (int l = 0; l < kMaxLayers; ++l) ca.b16[w][l] = h->chain_b16 + ((size_t)w * kMaxLayers + l) * 256;
+  ca.w3buf[0] = h->w3_snap; ca.w3buf[1] = h->w3buf1;
+  // the first hidden layer's dY from the unit-seed rows the pass's members leave before the pass (DwGate kind 3)
+  ca.qp = h->chain_flags + 576;
+  fa.gu = h->gu; fa.gu_flags = h->chain_flags + 448;
+  ka.gate.kind[0] = 3; ka.gate.gu = h->gu; ka.gate.gu_flags = fa.gu_flags; ka.gate.n_gu_flags = 8 * slices;
+  if (kc.tile_end[kDwFusedItems - 1] > 192 || ka.tile_end[kDwFusedItems - 1] > 192 || slices > 64) { set_err("chain launch: too many tiles"); return OPRL_ERR_INVALID; }
+  // exchange tags: two per update (the roles', the critic pass's), consecutive: cluster_tag = the first
+  unsigned tag = h->tp_tag;
+  if ((tag & 0x03FFFFFFu) + 2u * (unsigned)U + 2u >= 0x03FFFFFFu) {      // (would wrap inside the launch: wrap now)
+    tag = (tag | 0x03FFFFFFu) + 1u;
+    HIPC(hipMemsetAsync(h->xbuf, 0, h->xbuf_granules * sizeof(unsigned long long), st));
+  }
+  fa.cluster_tag = (tag + 1u) & 0x03FFFFFFu;
+  fa.prefetch_p1 = 0;
+  fa.trace2 = fa.trace != nullptr ? h->trace + (size_t)3 * 64 * kTraceStamps * 2 : nullptr;   // slot 3
+  prof_begin(4, st);
+  hipError_t e;
+  {
+    std::lock_guard<std::mutex> lk(g_turn.mu);
+    int dev = 0;
+    e = chip_turn_begin(st, &dev);
+    if (e == hipSuccess) e = launch_ddpg_chain(fa, kc, ka, ca, st);
+    if (e == hipSuccess) chip_turn_end(st, dev);
+  }
+  prof_end(st);
+  HIPC(e);
+  dw_commit(h, true, dc, U);
+  dw_commit(h, false, da, U);
+  if (h->dp_inline) {
+    h->p2p.tile_seq += 2ull * (unsigned long long)U;
+    h->stale32[0] = true; h->stale32[1] = true;  // (the tiles write the fp16 packs only)
+  }
+  h->tp_tag = tag + 2u * (unsigned)U;
+  h->epoch += (unsigned)(U - 1);
+  h->whole_done = true;
+  return OPRL_OK;
+}
+
 int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
                  const float* s2, int B, const float* noise0, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
@@ -892,175 +1061,38 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));     // (a batch the lean kernels do not take: fp32 packs)
     fa.noise = noise0;
     if (h->prefetch_p1 && h->prefetch_next) {
+      // (step_n sets prefetch_p1 only for a form with merged bits, which the rt2 form never has)
+      if (fa.rt2 != 0) { set_err("internal: phase 1 asked to stage the next rows in the rt2 form"); return OPRL_ERR_STATE; }
       fa.prefetch_p1 = 1;
       h->staged_ready = true;
     }
-    RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
     if (h->trace != nullptr) fa.trace = h->trace;   // roles use slots 0 .. 1 + n_critics
     h->whole_done = false;
-    if (form.whole) {
-      // the whole update as k_ddpg_chain launches: phase 1's roles, the critic's tiles, role U + the actor's tiles, the
-      // critic pass, of U updates (step_n: chain_u) per launch
-      RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag2));
-      if (h->trace != nullptr && c.algo == OPRL_DDPG) fa.trace2 = h->trace + (size_t)3 * 64 * kTraceStamps * 2;   // slot 3
-      fa.prefetch_next = 0;
-      const int slices = (B + kR - 1) / kR;
-      // (what this block advances — the optimisers' step counts, the exchange sequence numbers, the tags — is put back by
-      // every error return below: after a failed call Adam's bias corrections and, data parallel, this rank's tile sequence
-      // must not be ahead of the parameters / of the peers: ADVICE r4)
-      const struct { int c, a; unsigned long long seq; unsigned tag, epoch; } snap{h->opt_step_critic, h->opt_step_actor, h->p2p.tile_seq, h->tp_tag, h->epoch};
-      auto undo = [&]() { h->opt_step_critic = snap.c; h->opt_step_actor = snap.a; h->p2p.tile_seq = snap.seq; h->tp_tag = snap.tag; h->epoch = snap.epoch; };
-      DwKArgs kd;
-      DwKArgs4 kc, ka;
-      auto compact = [&](const DwKArgs& k, DwKArgs4* o) {
-        for (int j = 0; j < kDwFusedItems; ++j) { o->tile_end[j] = k.tile_end[j]; o->items[j] = k.items[j]; }
-        o->n_items = k.n_items; o->B = k.B; o->n_part = k.n_part; o->dy_tiled = k.dy_tiled; o->ad = k.ad; o->trace = k.trace;
-        o->gate = k.gate;
-        memset((void*)&o->xchg, 0, sizeof o->xchg);
-      };
-      {
-        DwArgs dw = dw_build(h, true, B, true, false);
-        if (fill_dw_kargs(dw, &kd, 64) < 0 || dw.n_items > kDwFusedItems) { undo(); set_err("whole update: bad critic dW table"); return OPRL_ERR_INVALID; }
-        kd.gate.rows = fa.gate_flags; kd.gate.n_rows = 4 * slices;
-        kd.gate.seed = fa.y_granules; kd.gate.n_seed = B;
-        kd.gate.late_dY = h->ws_critic[0].dY[c.critics[0].n_layers - 1];
-        kd.gate.tag = h->epoch; kd.gate.spin = h->debug_expire == 7 ? 0 : (1 << 20);
-        kd.gate.err = h->err_dev; kd.gate.err_code = (1u << 8) | 7u;
-        kd.gate.done = fa.ct_done; kd.gate.what_if = h->debug_expire;
-        fa.n_ct = kd.tile_end[kDwMaxItems - 1];
-        if (fa.n_ct > 192 - 64) { undo(); set_err("whole update: too many critic tiles"); return OPRL_ERR_INVALID; }
-        compact(kd, &kc);
-      }
-      {
-        DwArgs dw = dw_build(h, false, B, true, false);
-        if (fill_dw_kargs(dw, &kd, 64) < 0 || dw.n_items != 3) { undo(); set_err("whole update: bad actor dW table"); return OPRL_ERR_INVALID; }
-        kd.gate.seed = fa.du_granules; kd.gate.n_seed = B;
-        kd.gate.tag = h->epoch; kd.gate.spin = h->debug_expire == 7 ? 0 : (1 << 20);
-        kd.gate.err = h->err_dev; kd.gate.err_code = (2u << 8) | 7u;
-        kd.gate.kind[0] = 2; kd.gate.kind[1] = 1; kd.gate.kind[2] = 0; kd.gate.kind[3] = 0; kd.gate.what_if = h->debug_expire;
-        kd.gate.h2 = h->ws_actor.X[2];
-        kd.gate.w3 = fa.w3_snap;
-        kd.gate.g1 = fa.g1_granules;
-        kd.gate.n_act = h->A;
-        compact(kd, &ka);
-      }
-      // (every tile must find a role-B / role-C workgroup to be the continuation of: 8 per slice)
-      const int max_tiles = kc.tile_end[kDwFusedItems - 1] > ka.tile_end[kDwFusedItems - 1] ? kc.tile_end[kDwFusedItems - 1] : ka.tile_end[kDwFusedItems - 1];
-      const int t_rows = chain_tile_rows(max_tiles, slices);
-      // (the form's fit test counted the same 16 x 64 tiles from the learner's item table: chain_rows)
-      if (16 + t_rows != chain_rows(h, B)) { undo(); set_err("internal: whole update of %d grid rows, the form counted %d", 16 + t_rows, chain_rows(h, B)); return OPRL_ERR_STATE; }
-      const int U = h->chain_u < form.chain_max ? h->chain_u : form.chain_max;
-      memset((void*)&kc.xchg, 0, sizeof kc.xchg);
-      memset((void*)&ka.xchg, 0, sizeof ka.xchg);
-      if (h->dp_inline) {
-        // data parallel on peer windows: the tiles of this launch all-reduce their gradients themselves and run Adam on
-        // the mean (dw_tile_x2.h): exchange sequence numbers seq0 + 2 u (critic) / + 1 (actor) for update u of the launch
-        P2pState& P = h->p2p;
-        if (max_tiles > h->p2p_max_tiles) { undo(); set_err("data-parallel whole update: the windows hold %d tiles, the launch has %d", h->p2p_max_tiles, max_tiles); return OPRL_ERR_STATE; }
-        DwXchg X;
-        memset((void*)&X, 0, sizeof X);
-        for (int r = 0; r < kDwXchgMaxWorld; ++r) X.peer[r] = r < P.world ? P.peer[r] + P.tile_off : nullptr;
-        X.window = P.window + P.tile_off;
-        X.world = P.world; X.rank = P.rank; X.max_tiles = h->p2p_max_tiles;
-        X.seq = P.tile_seq + 1; X.parity = 0;        // (parity = the exchange's sequence number & 1, formed in the tile)
-        X.err = h->err_dev;
-        P.tile_seq += 2ull * (unsigned long long)U;
-        kc.xchg = X; ka.xchg = X;
-        kc.ad.do_adam = 1; ka.ad.do_adam = 1;
-        kc.ad.grad_scale = 1.0f / (float)P.world; ka.ad.grad_scale = 1.0f / (float)P.world;
-        h->stale32[0] = true; h->stale32[1] = true;  // (the tiles write the fp16 packs only)
-      }
-      // SEVERAL updates as one launch (k_ddpg_chain): the tables above are update 0's; what changes per update — Adam's
-      // bias-correction terms, epochs, exchange tags, the staging set — is in ChainArgs
-      ChainArgs ca;
-      memset((void*)&ca, 0, sizeof ca);
-      ca.n_upd = U;
-      ca.first_gather = fa.src.gather;
-      ca.pf_last = h->chain_pf_last ? 1 : 0;
-      ca.trace_u = U - 1;
-      ca.rows = 16 + t_rows;
-      ca.order = h->sw.chain_order;
-      ca.c_step[0] = kc.ad.step_size_host; ca.c_bc2[0] = kc.ad.bc2_sqrt_host;
-      ca.a_step[0] = ka.ad.step_size_host; ca.a_bc2[0] = ka.ad.bc2_sqrt_host;
-      for (int u = 1; u < U; ++u) {          // (the optimisers' step counts advance once per update and net, as dw_build does;
-        h->opt_step_critic += 1;             // only Adam's bias-correction terms change from update to update: a call of
-        h->opt_step_actor += 1;              // dw_build per update and net was 8 of the 17 us a step_n(20) call took to enqueue)
-        AdamScalars sc_, sa_;
-        memset(&sc_, 0, sizeof sc_); memset(&sa_, 0, sizeof sa_);
-        set_adam(sc_, c.hp.lr_critic, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, c.hp.tau); set_step(sc_, h->opt_step_critic);
-        set_adam(sa_, c.hp.lr_actor, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, c.hp.tau); set_step(sa_, h->opt_step_actor);
-        ca.c_step[u] = sc_.step_size_host; ca.c_bc2[u] = sc_.bc2_sqrt_host;
-        ca.a_step[u] = sa_.step_size_host; ca.a_bc2[u] = sa_.bc2_sqrt_host;
-      }
-      ca.set0[0] = fa.src.s; ca.set0[1] = fa.src.a; ca.set0[2] = fa.src.r; ca.set0[3] = fa.src.d; ca.set0[4] = fa.src.s2;
-      for (int i = 0; i < 5; ++i) ca.set1[i] = h->chain_set1[i];
-      if ((U > 1 || ca.pf_last) && ca.set1[0] == nullptr) { undo(); set_err("chain launch: no second staging set"); return OPRL_ERR_STATE; }
-      ca.ct_fin = h->chain_flags; ca.at_fin = h->chain_flags + 192; ca.pf_done = h->chain_flags + 384;
-      for (int w = 0; w < 4; ++w)
-        for (int l = 0; l < kMaxLayers; ++l) ca.b16[w][l] = h->chain_b16 + ((size_t)w * kMaxLayers + l) * 256;
-      ca.w3buf[0] = h->w3_snap; ca.w3buf[1] = h->w3buf1;
-      // the first hidden layer's dY from the unit-seed rows the pass's members leave before the pass (DwGate kind 3)
-      ca.qp = h->chain_flags + 576;
-      fa.gu = h->gu; fa.gu_flags = h->chain_flags + 448;
-      ka.gate.kind[0] = 3; ka.gate.gu = h->gu; ka.gate.gu_flags = fa.gu_flags; ka.gate.n_gu_flags = 8 * slices;
-      if (kc.tile_end[kDwFusedItems - 1] > 192 || ka.tile_end[kDwFusedItems - 1] > 192 || slices > 64) { undo(); set_err("chain launch: too many tiles"); return OPRL_ERR_INVALID; }
-      // exchange tags: two per update (the roles', the critic pass's), consecutive: cluster_tag = the first
-      {
-        unsigned& ctr = h->tp_tag;
-        if ((ctr & 0x03FFFFFFu) + 2u * (unsigned)U + 2u >= 0x03FFFFFFu) {      // (would wrap inside the launch: wrap now)
-          ctr = (ctr | 0x03FFFFFFu) + 1u;
-          HIPC(hipMemsetAsync(h->xbuf, 0, h->xbuf_granules * sizeof(unsigned long long), st));
-        }
-        fa.cluster_tag = (ctr + 1u) & 0x03FFFFFFu;
-        ctr += 2u * (unsigned)U;
-      }
-      fa.prefetch_p1 = 0;
-      fa.trace2 = fa.trace != nullptr ? h->trace + (size_t)3 * 64 * kTraceStamps * 2 : nullptr;
-      h->epoch += (unsigned)(U - 1);
-      prof_begin(4, st);
-      hipError_t e;
-      {
-        std::lock_guard<std::mutex> lk(g_turn.mu);
-        int dev = 0;
-        e = chip_turn_begin(st, &dev);
-        if (e == hipSuccess) e = launch_ddpg_chain(fa, kc, ka, ca, st);
-        if (e == hipSuccess) chip_turn_end(st, dev);
-      }
-      prof_end(st);
-      if (e != hipSuccess) undo();
-      HIPC(e);
-      h->whole_done = true;
-      return OPRL_OK;
-    }
+    if (form.whole) return whole_update(h, fa, form, B, st);
+    RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
     if ((fa.merged & 1) != 0) {
       // phase 1 and the critic's dW + Adam tiles as ONE launch: the tiles wait for the roles' flag granules
-      // TD3 moves its targets only on actor steps (td3.py:135-146)
-      DwArgs dw = dw_build(h, true, B, c.algo == OPRL_TD3 ? actor_due(h) : true, false);
+      const DwArgs dw = dw_args(h, true, B, h->opt_step_critic + 1);
       DwKArgs kd;
       if (fill_dw_kargs(dw, &kd, ((fa.x2 && fused_x2_tiles()) || (h->nc == 2 && fused_tile64_all())) ? 64 : 32) < 0) { set_err("merged phase 1: bad dW table"); return OPRL_ERR_INVALID; }
-      const int slices = (B + kR - 1) / kR;
-      kd.gate.rows = fa.gate_flags; kd.gate.n_rows = 4 * slices * h->nc;
-      kd.gate.seed = fa.y_granules; kd.gate.n_seed = B;      // the seeds come as granules, one per row
-      kd.gate.late_dY = h->ws_critic[0].dY[c.critics[0].n_layers - 1];
+      critic_gate(h, fa, B, kd.gate);
       if (h->nc == 2) {      // (twin critics: the second one's items, seeds and output-layer dY)
         kd.gate.item_split = c.critics[0].n_layers;
         kd.gate.seed2 = fa.seed2_granules;
         kd.gate.late_dY2 = h->ws_critic[1].dY[c.critics[1].n_layers - 1];
       }
-      kd.gate.tag = h->epoch; kd.gate.spin = h->debug_expire == 7 ? 0 : (1 << 20);
-      kd.gate.err = h->err_dev; kd.gate.err_code = (1u << 8) | 7u;      // KERN_PHASE1, SITE_DW_GATE (csrc/tp3.h)
       prof_begin(4, st);
       hipError_t e = launch_ddpg_phase1_dw(fa, kd, st);
       prof_end(st);
       HIPC(e);
+      dw_commit(h, true, dw, 1);
       return OPRL_OK;
     }
     prof_begin(4, st);
     hipError_t e = launch_ddpg_phase1(fa, st);
     prof_end(st);
     HIPC(e);
-    // TD3 moves its targets only on actor steps (td3.py:135-146)
-    return dw_step(h, true, B, c.algo == OPRL_TD3 ? actor_due(h) : true, st);
+    return dw_step(h, true, B, st);
   }
   RC(fresh32_tables(h, 3, st));      // (a PrecX2 learner's generic launches read the fp32 packs)
   const int S = h->S, A = h->A, nc = h->nc;
@@ -1139,12 +1171,9 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     HIPC(e);
     h->fin_tail0 = -1;
   }
-  if (algo == OPRL_TQC && h->tqc_job_pending) {     // (the job did not ride: not the layer-by-layer path)
+  // (the job did not ride — not the layer-by-layer path — or was never offered)
+  if (algo == OPRL_TQC && (h->tqc_job_pending || h->tqc_counter == nullptr || h->sw.no_tqc_ride)) {
     h->tqc_job_pending = false;
-    const int Q = c.hp.n_quantiles, drop = c.hp.top_quantiles_to_drop;
-    HIPC(launch_tqc_target(h->qn, (long)h->Bmax * h->ldq, h->ldq, nc, Q, drop, r, d, h->logp2,
-                           c.log_alpha, (float)c.hp.gamma, B, h->target, st));
-  } else if (algo == OPRL_TQC && (h->tqc_counter == nullptr || h->sw.no_tqc_ride)) {
     const int Q = c.hp.n_quantiles, drop = c.hp.top_quantiles_to_drop;
     HIPC(launch_tqc_target(h->qn, (long)h->Bmax * h->ldq, h->ldq, nc, Q, drop, r, d, h->logp2,
                            c.log_alpha, (float)c.hp.gamma, B, h->target, st));
@@ -1193,24 +1222,7 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     return OPRL_ERR_STATE;
   }
   // 4. dW + Adam (+ Polyak where the reference does it every step)
-  {
-    const bool polyak = (algo == OPRL_TD3) ? (h->update_count % c.hp.policy_freq == 0) : true;
-    h->opt_step_critic += 1;
-    DwArgs dw;
-    dw.items = h->items_host.data(); dw.n_items = h->n_items_critic; dw.total_tiles = h->tiles_critic;
-    dw.B = B; dw.n_part = tp_generic(h, c.critics[0], B) ? 4 : 1; dw.use_row_scale = 0; dw.apply_only = 0;
-    dw.dy_tiled = dw.n_part > 1 ? 1 : 0;               // k_mlp_slice_tp runs the tp4 passes
-    dw.trace = h->trace != nullptr ? h->trace + (size_t)4 * 64 * kTraceStamps * 2 : nullptr;   // slot 4
-    dw.ad = adam_scalars(h, c.hp.lr_critic, h->opt_step_critic, polyak, 1.0f);
-    // TQC in a 16-bit mode: the critics' 512 x 512 layers run through the 16-bit packs (layerwise.hip); their fp32
-    // packs — a third of the wide dW launch's stores — are left stale and rebuilt by whoever reads them (fresh32)
-    if (algo == OPRL_TQC && (h->x2 || h->bf16) && h->lazy_wide && !c.export_grads && !h->sw.no_layerwise) {
-      dw.skip32_wide = 1;
-      h->stale_wide = true;
-    }
-    HIPC(launch_dw_prof(h, dw, st));
-  }
-  return OPRL_OK;
+  return dw_step(h, true, B, st);
 }
 
 // ------------------------------------------------------------- actor phase
@@ -1245,44 +1257,34 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
     if (h->prefetch_next && !h->prefetch_p1) h->staged_ready = true;
     if ((fa.merged & 2) != 0 && !pf_on_dw) {
       // phase 2 and the actor's dW + Adam tiles as ONE launch: the tiles wait for the du (first layer: dz1) granules
-      DwArgs dw = dw_build(h, false, B, true, false);
+      const DwArgs dw = dw_args(h, false, B, h->opt_step_actor + 1);
       DwKArgs kd;
       if (fill_dw_kargs(dw, &kd, (fa.x2 && fused_x2_tiles()) ? 64 : 32) < 0 || dw.n_items != 3) { set_err("merged phase 2: bad dW table"); return OPRL_ERR_INVALID; }
-      kd.gate.seed = fa.du_granules; kd.gate.n_seed = B;
-      kd.gate.tag = h->epoch; kd.gate.spin = h->debug_expire == 7 ? 0 : (1 << 20);
-      kd.gate.err = h->err_dev; kd.gate.err_code = (2u << 8) | 7u;      // KERN_PHASE2, SITE_DW_GATE (csrc/tp3.h)
-      kd.gate.kind[0] = 2; kd.gate.kind[1] = 1; kd.gate.kind[2] = 0; kd.gate.kind[3] = 0;   // items = the actor's layers 0, 1, 2
-      kd.gate.h2 = h->ws_actor.X[2];
-      kd.gate.w3 = fa.w3_snap;
-      kd.gate.g1 = fa.g1_granules;
-      kd.gate.n_act = h->A;
+      actor_gate(h, fa, B, kd.gate);
       prof_begin(5, st);
       hipError_t e = launch_ddpg_phase2_dw(fa, kd, st);
       prof_end(st);
       HIPC(e);
+      dw_commit(h, false, dw, 1);
       return OPRL_OK;
     }
     prof_begin(5, st);
     hipError_t e = launch_ddpg_phase2(fa, st);
     prof_end(st);
     HIPC(e);
-    const bool rides = alpha_rides(h);      // SAC temperature (sac.py:129-141), from role C's log pi
-    RC(dw_step(h, false, B, c.actor.theta_target != nullptr, st, rides, pf_on_dw ? &pj : nullptr));
-    if (alpha_ptr(h) != nullptr && !rides) {
-      h->opt_step_alpha += 1;
-      HIPC(launch_alpha_step(c.log_alpha, c.log_alpha_m, c.log_alpha_v, h->logp, B,
-                             (float)c.hp.target_entropy, c.hp.lr_alpha, c.hp.beta1, c.hp.beta2,
-                             c.hp.adam_eps, h->opt_step_alpha,
-                             c.export_grads ? h->alpha_grad : nullptr, nullptr, 1.0f, st));
-    }
-    return OPRL_OK;
+    RC(dw_step(h, false, B, st, pf_on_dw ? &pj : nullptr));
+    return temperature_step(h, B, st);      // SAC temperature (sac.py:129-141), from role C's log pi
   }
   RC(fresh32_tables(h, 3, st));
   const int S = h->S, A = h->A, nc = h->nc;
   const int algo = c.algo;
   const bool gauss = (algo == OPRL_SAC || algo == OPRL_TQC);
-  const int n_slices = (B + kR - 1) / kR;
-  const int n_q_all = (algo == OPRL_TD3 || algo == OPRL_DDPG) ? 1 : nc;   // TD3 uses Q1 only
+  const int n_q = (algo == OPRL_TD3 || algo == OPRL_DDPG) ? 1 : nc;   // TD3 uses Q1 only
+  // (the offers to the riding launches below never outlive this update: after an error return the next must not find one)
+  struct ClearOffers {
+    oprl_learner* h;
+    ~ClearOffers() { h->bwd_rider_pending = false; h->bwd_rider_done = false; h->bwd_tiles_pending = false; h->bwd_tiles_done = false; }
+  } clear_offers{h};
   auto actor_backward_args = [&]() {      // step 8's launch
     MlpArgs f = base_args(h, c.actor, false, B);
     f.do_bwd = 1;
@@ -1290,7 +1292,7 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
     SeedArgs& sd = f.seed;
     if (gauss) {
       f.seed_mode = SEED_GAUSS;
-      sd.p0 = h->da; sd.ld0 = A; sd.n_da = n_q_all; sd.da_stride = (long)h->Bmax * A;
+      sd.p0 = h->da; sd.ld0 = A; sd.n_da = n_q; sd.da_stride = (long)h->Bmax * A;
       sd.p1 = h->raw;
       seed_rng(f, h, noise1, 2);   // backward re-reads (or re-draws) the forward's eps
       sd.log_alpha = alpha_ptr(h); sd.alpha_const = (float)c.hp.alpha_init;
@@ -1301,19 +1303,7 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
     }
     return f;
   };
-  DwArgs actor_dw;
-  bool actor_dw_built = false;
-  auto actor_dw_args = [&]() {            // step 9's launch (advances the actor's and — riding — the temperature's step counts: once per update)
-    h->opt_step_actor += 1;
-    DwArgs dw;
-    dw.items = h->items_host.data() + h->n_items_critic; dw.n_items = h->n_items_actor;
-    dw.total_tiles = h->tiles_actor; dw.B = B; dw.n_part = tp_generic(h, c.actor, B) ? 4 : 1; dw.use_row_scale = 0; dw.apply_only = 0;
-    dw.dy_tiled = dw.n_part > 1 ? 1 : 0;
-    dw.trace = h->trace != nullptr ? h->trace + (size_t)5 * 64 * kTraceStamps * 2 : nullptr;   // slot 5
-    dw.ad = adam_scalars(h, c.hp.lr_actor, h->opt_step_actor, c.actor.theta_target != nullptr, 1.0f);
-    if (alpha_rides(h)) dw.alpha = alpha_job(h, B);
-    return dw;
-  };
+  DwArgs actor_dw;                        // step 9's table where it rides (built with this update's step counts)
   // 5. actor forward (activations kept for its backward) — unless it rode on the critic step's heads (critic_phase)
   if (h->rider_done) {
     h->rider_done = false;
@@ -1322,7 +1312,6 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
     RC(launch(f, h->w_actor, st));
   }
   // 6./7. critics on (s, pi): gradient wrt the action columns
-  const int n_q = (algo == OPRL_TD3 || algo == OPRL_DDPG) ? 1 : nc;   // TD3 uses Q1 only
   if (algo == OPRL_SAC) {
     RC(for_each_net(h, nc, st, [&](int j, hipStream_t sj) {   // both q's before either seed (min)
       MlpArgs f = base_args(h, c.critics[j], false, B);
@@ -1355,12 +1344,13 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
         h->bwd_rider = f;
         h->bwd_rider_pending = true;
         // ... and step 9's tiles behind it (the 16 x 32 tiles of k_dw_adam, the temperature's step as the workgroup one past
-        // them): built with THIS update's step count; if the launch does not take them, step 9 launches the same table
+        // them): built with THIS update's step counts, committed once they have ridden; if the launch does not take them,
+        // step 9 launches the same table
         h->bwd_tiles_pending = false;
         h->bwd_tiles_done = false;
         if (!h->sw.no_bwd_tiles && alpha_rides(h) && h->n_items_actor <= kDwMaxItems) {
-          actor_dw = actor_dw_args();
-          actor_dw_built = true;
+          actor_dw = dw_args(h, false, B, h->opt_step_actor + 1);
+          actor_dw.alpha = alpha_job(h, B, h->opt_step_alpha + 1);
           const int total = fill_dw_kargs(actor_dw, &h->bwd_tiles, 32);
           if (total > 0) {
             h->bwd_tile_wgs = total + (actor_dw.alpha.log_alpha != nullptr ? 1 : 0);
@@ -1390,22 +1380,10 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
   }
   // 9. dW + Adam (+ Polyak of the actor target for DDPG / TD3) — unless the tiles rode behind the riding backward
   h->bwd_tiles_pending = false;
-  if (h->bwd_tiles_done) {
-    h->bwd_tiles_done = false;
-  } else {
-    if (!actor_dw_built) actor_dw = actor_dw_args();
-    HIPC(launch_dw_prof(h, actor_dw, st));
-  }
+  if (h->bwd_tiles_done) dw_commit(h, false, actor_dw, 1);
+  else RC(dw_step(h, false, B, st));
   // 10. temperature (when it did not ride on the actor's dW launch)
-  if (alpha_ptr(h) != nullptr && !alpha_rides(h)) {
-    h->opt_step_alpha += 1;
-    HIPC(launch_alpha_step(c.log_alpha, c.log_alpha_m, c.log_alpha_v, h->logp, B,
-                           (float)c.hp.target_entropy, c.hp.lr_alpha, c.hp.beta1, c.hp.beta2,
-                           c.hp.adam_eps, h->opt_step_alpha,
-                           c.export_grads ? h->alpha_grad : nullptr, nullptr, 1.0f, st));
-  }
-  (void)n_slices;
-  return OPRL_OK;
+  return temperature_step(h, B, st);
 }
 
 // master -> packs for a list of nets (which: bit0 online, bit1 target).  The item
@@ -1602,41 +1580,20 @@ extern "C" int oprl_learner_apply(oprl_learner* h, int32_t phase, double grad_sc
   if (!h) { set_err("null learner handle"); return OPRL_ERR_INVALID; }
   if (!h->cfg.export_grads) { set_err("oprl_learner_apply: learner was not created with export_grads"); return OPRL_ERR_STATE; }
   RC(check_device_error(h));
+  if (phase != 0 && phase != 1) { set_err("phase must be 0 or 1"); return OPRL_ERR_INVALID; }
+  const bool critic = phase == 0;
+  if (!critic && !h->actor_updated_last) return OPRL_OK;
   hipStream_t st = (hipStream_t)stream;
-  const oprl_learner_config& c = h->cfg;
-  if (phase == 0) {
-    // update_count was not advanced yet for this update (phase 1 does that)
-    const bool polyak = (c.algo == OPRL_TD3) ? (h->update_count % c.hp.policy_freq == 0) : true;
-    // one launch: k_dw_adam's epilogue (Adam, Polyak, packs written in pack order) fed from the
-    // all-reduced gradient arena instead of the GEMM — replaces k_adam_flat + k_repack
-    DwArgs dw;
-    dw.items = h->items_host.data(); dw.n_items = h->n_items_critic; dw.total_tiles = h->tiles_critic;
-    dw.B = 0; dw.n_part = 1; dw.trace = nullptr; dw.use_row_scale = 0; dw.apply_only = 1;
-    dw.ad = adam_scalars(h, c.hp.lr_critic, h->opt_step_critic, polyak, (float)grad_scale);
-    dw.ad.do_adam = 1;
-    if (h->fchain) h->stale32[0] = true;      // (the launch writes the mirrors: the caller's packs fall behind)
-    HIPC(launch_dw_prof(h, dw, st));
-    return OPRL_OK;
-  }
-  if (phase == 1) {
-    if (!h->actor_updated_last) return OPRL_OK;
-    const oprl_net& n = c.actor;
-    DwArgs dw;
-    dw.items = h->items_host.data() + h->n_items_critic; dw.n_items = h->n_items_actor;
-    dw.total_tiles = h->tiles_actor;
-    dw.B = 0; dw.n_part = 1; dw.trace = nullptr; dw.use_row_scale = 0; dw.apply_only = 1;
-    dw.ad = adam_scalars(h, c.hp.lr_actor, h->opt_step_actor, n.theta_target != nullptr, (float)grad_scale);
-    dw.ad.do_adam = 1;
-    if (h->fchain) h->stale32[1] = true;
-    HIPC(launch_dw_prof(h, dw, st));
-    if (alpha_ptr(h) != nullptr)
-      HIPC(launch_alpha_step(c.log_alpha, c.log_alpha_m, c.log_alpha_v, nullptr, 1, (float)c.hp.target_entropy,
-                             c.hp.lr_alpha, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, h->opt_step_alpha,
-                             nullptr, h->alpha_grad, (float)grad_scale, st));
-    return OPRL_OK;
-  }
-  set_err("phase must be 0 or 1");
-  return OPRL_ERR_INVALID;
+  // one launch: k_dw_adam's epilogue (Adam, Polyak, packs written in pack order) fed from the all-reduced gradient arena
+  // instead of the GEMM — replaces k_adam_flat + k_repack — at the step update_phase counted when it took the gradient
+  // (dw_args' Polyak test for the critic: update_count is not advanced before phase 1)
+  DwArgs dw = dw_args(h, critic, 0, critic ? h->opt_step_critic : h->opt_step_actor);
+  dw.ad.do_adam = 1;
+  dw.ad.grad_scale = (float)grad_scale;
+  HIPC(launch_dw_prof(h, dw, st));
+  dw_commit(h, critic, dw, 0);
+  if (!critic && alpha_ptr(h) != nullptr) HIPC(alpha_step(h, 0, h->opt_step_alpha, (float)grad_scale, st));
+  return OPRL_OK;
 }
 
 namespace oprl_host {
@@ -1675,6 +1632,14 @@ int chain_loop(oprl_learner* h, int K, int B, float* (*set)[5], void* stream) {
   return rc;
 }
 
+// step_n's two sets of batch rows {s, a, r, d, s2}: the learner's own and batch_alt
+void staging_sets(const oprl_learner* h, float* set[2][5]) {
+  const size_t Bm = (size_t)h->Bmax;
+  const size_t off[5] = {0, Bm * h->S, Bm * (h->S + h->A), Bm * (h->S + h->A + 1), Bm * (h->S + h->A + 2)};
+  float* const own[5] = {h->bs, h->ba, h->br, h->bd, h->bs2};
+  for (int i = 0; i < 5; ++i) { set[0][i] = own[i]; set[1][i] = h->batch_alt + off[i]; }
+}
+
 // does step_n at this batch run as chain launches?
 bool chain_ok(oprl_learner* h, int B) {
   return fused_form(h, B, h->dp_inline).whole && h->batch_alt != nullptr;
@@ -1704,18 +1669,16 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
     h->next_src = sc;
     // With the merged phase 2 (whose roles fill the chip) PHASE 1 carries the next update's rows — every update, TD3's
     // critic-only ones included — into the other of two staging sets, since its own roles are still reading theirs
-    const size_t Bm = (size_t)h->Bmax;
-    float* alt = h->batch_alt;
-    float* set[2][5] = {{h->bs, h->ba, h->br, h->bd, h->bs2},
-                        {alt, alt + Bm * h->S, alt + Bm * (h->S + h->A), alt + Bm * (h->S + h->A + 1), alt + Bm * (h->S + h->A + 2)}};
+    float* set[2][5];
+    staging_sets(h, set);
     // k_ddpg_chain: up to chain_max updates per launch, the rows of update u + 1 staged by update u inside the launch
     const bool chain = chain_ok(h, B);
-    const FusedForm probe = fused_form(h, B, h->dp_inline);     // (prefetch_p1 is false here: the form's merged bits never read it)
+    const FusedForm probe = fused_form(h, B, h->dp_inline);
     // (... and TD3's merged twin launches in every arithmetic, r06-15: without the merged phase 2 — exact fp32, bf16 — a
     // critic-only update had no launch that staged the next rows, and the update behind it gathered its own inside the roles'
     // first stage: 4.8 us against 2.9 before the first barrier of every role of every second launch)
     const bool td3_p1 = h->cfg.algo == OPRL_TD3 && (probe.merged & 1) != 0 && !h->sw.no_p1_rows;
-    h->prefetch_p1 = !chain && alt != nullptr && ((probe.merged & 2) != 0 || td3_p1);
+    h->prefetch_p1 = !chain && h->batch_alt != nullptr && ((probe.merged & 2) != 0 || td3_p1);
     int cur = 0;
     int rc = OPRL_OK;
     h->staged_ready = false;
@@ -1754,10 +1717,8 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
     base.next.seed = seed;
     base.next.gather = 1;
     base.S = h->S; base.A = h->A; base.B = B; base.z0 = -1;
-    const size_t Bm = (size_t)h->Bmax;
-    float* alt = h->batch_alt;
-    float* set[2][5] = {{h->bs, h->ba, h->br, h->bd, h->bs2},
-                        {alt, alt + Bm * h->S, alt + Bm * (h->S + h->A), alt + Bm * (h->S + h->A + 1), alt + Bm * (h->S + h->A + 2)}};
+    float* set[2][5];
+    staging_sets(h, set);
     int cur = 0;
     bool staged = false;
     int rc = OPRL_OK;

@@ -179,9 +179,7 @@ extern "C" int oprl_learner_dp_update(oprl_learner* h, const float* s, const flo
     RC(rc);
     if (h->actor_updated_last && alpha_ptr(h) != nullptr) {   // the temperature: one double, exchanged on its own
       RC(dp_all_reduce(h, h->alpha_grad, 1, true, st));
-      HIPC(launch_alpha_step(c.log_alpha, c.log_alpha_m, c.log_alpha_v, nullptr, 1, (float)c.hp.target_entropy,
-                             c.hp.lr_alpha, c.hp.beta1, c.hp.beta2, c.hp.adam_eps, h->opt_step_alpha,
-                             nullptr, h->alpha_grad, (float)scale, st));
+      HIPC(alpha_step(h, 0, h->opt_step_alpha, (float)scale, st));
     }
     return OPRL_OK;
   }

@@ -183,7 +183,6 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
       due[j] = actor_due(g->L[0]);
       for (int l = 0; l < n; ++l) {
         oprl_learner* h = g->L[l];
-        const oprl_learner_config& cf = h->cfg;
         if (actor_due(h) != due[j]) { roll_back(); set_err("oprl_group_step_n: the members' delayed actor steps are out of phase (update counts differ modulo policy_freq)"); return OPRL_ERR_STATE; }
         h->src.counter = (unsigned long long)h->update_count;
         h->next_src.counter = h->src.counter + 1;
@@ -196,9 +195,10 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
         p1[l].group_span = g->span;
         RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &p1[l].cluster_tag));
         DwKArgs kd;
-        // (as the un-merged launches of a solo learner; TD3 moves its targets on actor steps only)
-        DwArgs dw = dw_build(h, true, B, cf.algo == OPRL_TD3 ? due[j] : true, false);
+        // (as the un-merged launches of a solo learner; the step counts move with the blocks, roll_back puts them back)
+        DwArgs dw = dw_args(h, true, B, h->opt_step_critic + 1);
         const int tc = fill_dw_kargs(dw, &kd) < 0 ? -1 : compact_dw_kargs(kd, dc + (size_t)l * dc_bytes, g->ni_c);
+        dw_commit(h, true, dw, 1);
         int ta = tiles_a;
         if (due[j]) {
           p2[l] = ddpg_args(h, B);
@@ -206,8 +206,10 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
           RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &p2[l].cluster_tag));   // (a launch, a tag)
           p2[l].prefetch_next = prefetch;
           h->staged_ready = prefetch != 0;
-          dw = dw_build(h, false, B, cf.actor.theta_target != nullptr, alpha_rides(h));    // (SAC: the temperature step rides)
+          dw = dw_args(h, false, B, h->opt_step_actor + 1);
+          if (alpha_rides(h)) dw.alpha = alpha_job(h, B, h->opt_step_alpha + 1);    // (SAC: the temperature step rides)
           ta = fill_dw_kargs(dw, &kd) < 0 ? -1 : compact_dw_kargs(kd, da + (size_t)l * da_bytes, kDwGroupItems);
+          dw_commit(h, false, dw, 1);
           if (l == 0 && tiles_a == 0) tiles_a = ta;
           if (ta < 0 || ta != tiles_a || p2[l].nc != p1[l].nc || p2[l].merged || p2[l].wide || p2[l].whole || p2[l].p2_pair) ta = -1;
         }

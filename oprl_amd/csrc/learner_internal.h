@@ -473,7 +473,7 @@ void build_repack_items(const oprl_net* const* nets, int n_nets, int which,
                         std::vector<RepackItem>& items, int* blocks_out,
                         float* const* pk16 = nullptr, float* const* pk16_t = nullptr, int pl = 1);
 void alloc_net_ws(Pool& p, const oprl_net& n, int B, NetWs* ws);
-bool use_fused(oprl_learner* h, int B);
+bool use_fused(const oprl_learner* h, int B);
 void set_step(AdamScalars& ad, int step);
 void set_adam(AdamScalars& ad, double lr, double beta1, double beta2, double eps, double tau);
 int next_tp_tag(unsigned* counter, unsigned long long* xbuf, size_t xbuf_bytes, hipStream_t st, unsigned* out);
@@ -483,8 +483,11 @@ void with_store(MlpArgs& a, const NetWs& ws, bool x, bool dy);
 hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st);
 void fill_items(const oprl_net& n, const NetWs& ws, std::vector<DwItem>& v, int* tiles, bool small_partial_tiles = false,
                 float* pk16 = nullptr, float* pk16_t = nullptr, int pl = 1);
-DwArgs dw_build(oprl_learner* h, bool critic, int B, bool polyak, bool with_alpha);
+DwArgs dw_args(const oprl_learner* h, bool critic, int B, int step);
+void dw_commit(oprl_learner* h, bool critic, const DwArgs& dw, int steps);
 bool alpha_rides(const oprl_learner* h);
+AlphaJob alpha_job(const oprl_learner* h, int B, int step);
+hipError_t alpha_step(const oprl_learner* h, int B, int step, float grad_scale, hipStream_t st);
 int launch(const MlpArgs& a0, int width, hipStream_t st);
 // learners with lazily maintained fp32 packs (fresh32)
 extern std::mutex g_lazy_mu;
