@@ -30,9 +30,9 @@
 extern "C" {
 #endif
 
-#define OPRL_ABI_VERSION 2
+#define OPRL_ABI_VERSION 3
 #define OPRL_MAX_LAYERS 4   /* linear layers per MLP (TQC critic has 4) */
-#define OPRL_MAX_CRITICS 5  /* TQC n_nets */
+#define OPRL_MAX_CRITICS 10 /* TQC n_nets (5), REDQ ensemble (10) */
 
 typedef enum oprl_status {
   OPRL_OK = 0,
@@ -42,7 +42,11 @@ typedef enum oprl_status {
   OPRL_ERR_NOMEM = -4
 } oprl_status;
 
-typedef enum oprl_algo { OPRL_DDPG = 0, OPRL_TD3 = 1, OPRL_SAC = 2, OPRL_TQC = 3 } oprl_algo;
+/* OPRL_REDQ: an ensemble of n_critics scalar critics (<= OPRL_MAX_CRITICS) with SAC's tanh-Gaussian actor; the TD
+ * target takes the minimum over hp.n_min target critics drawn afresh for every update (oprl_redq_subset), the critic
+ * targets move on every update and the actor (+ temperature) steps on every hp.policy_freq-th (Chen et al., ICLR 2021;
+ * DESIGN.md "REDQ").  F32 only, no gradient export, never a fused form. */
+typedef enum oprl_algo { OPRL_DDPG = 0, OPRL_TD3 = 1, OPRL_SAC = 2, OPRL_TQC = 3, OPRL_REDQ = 4 } oprl_algo;
 
 /* Arithmetic mode of the MLP GEMMs.
  *   F32  = exact-fp32 MFMA (v_mfma_f32_16x16x4_f32), the parity mode: Q-values and gradients within
@@ -112,9 +116,10 @@ typedef struct oprl_hparams {
   double policy_noise, noise_clip, max_action;   /* TD3 (td3.py:98-103) */
   double alpha_init;                             /* SAC fixed alpha (sac.py:64) */
   double target_entropy;                         /* -action_dim */
-  int32_t policy_freq;                           /* TD3 (td3.py:81) */
+  int32_t policy_freq;                           /* TD3 (td3.py:81); REDQ: updates per actor step (G) */
   int32_t tune_alpha;                            /* SAC (sac.py:65-70); TQC always 1 */
   int32_t n_quantiles, top_quantiles_to_drop;    /* TQC (tqc.py:71-73) */
+  int32_t n_min;                                 /* REDQ: target critics in the minimum (M, 1..n_critics) */
 } oprl_hparams;
 
 typedef struct oprl_learner_config {
@@ -123,7 +128,7 @@ typedef struct oprl_learner_config {
   int32_t precision;        /* oprl_precision */
   int32_t state_dim, action_dim;
   int32_t max_batch;        /* workspace is sized for this many rows */
-  int32_t n_critics;        /* 1 DDPG, 2 TD3/SAC, n_nets TQC */
+  int32_t n_critics;        /* 1 DDPG, 2 TD3/SAC, n_nets TQC, the ensemble's size REDQ */
   int32_t no_fuse;          /* 1: always use the generic per-net launch sequence (DDPG
                                otherwise runs the fused two-kernel path, csrc/fused_ddpg.hip) */
   int32_t export_grads;     /* 1: update() stops before Adam and leaves grads in
@@ -212,7 +217,8 @@ int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, int32_t B, 
  * the exchange sums); a setting is part of a run's configuration like the seed. */
 int oprl_learner_set_cluster(oprl_learner* h, int32_t nc);
 /* Diagnostics of the most recent update, read without forcing a sync inside
- * update(): out_host[0]=critic_loss, [1]=-mean q(s, pi) (DDPG / TD3 actor loss; min over twins for SAC),
+ * update(): out_host[0]=critic_loss, [1]=-mean q(s, pi) (DDPG / TD3 actor loss; min over twins for SAC; mean over the
+ * ensemble for REDQ),
  * [2]=mean q over all critics, [3]=mean target, [4]=alpha, [5]=update_step, and (n up to 10) [6]=mean q of
  * critic 0 (the reference's "q1"), [7]=mean log pi of the actor step, [8]=SAC / TQC actor loss
  * alpha * mean(log pi) - mean(min q), [9]=temperature loss.  Synchronises `stream`. */
@@ -268,6 +274,13 @@ int oprl_learner_set_seed(oprl_learner* h, uint64_t seed, int32_t rank);
  * row, action dimension), under the learner's current seed and rank (oprl_learner_set_seed). */
 int oprl_debug_noise(oprl_learner* h, int32_t stream_id, uint64_t counter, int32_t rows, int32_t cols,
                      float* out_dev, void* stream);
+/* REDQ's target subset of update `counter` (the learner's update_count before the update) under noise key (seed, rank)
+ * as oprl_learner_set_seed takes them: m distinct indices in [0, n) into out_host[0 .. m).  Philox4x32-10 (csrc/philox.h)
+ * keyed like the device noise's stream 3 (key = that stream's 64-bit key, low word first), counter words {counter low,
+ * counter high, block, 0}: the four 32-bit words of block k are words 4k .. 4k+3, and a partial Fisher-Yates shuffle of 0 .. n-1
+ * takes, for i < m, j = i + bounded_u32(word_i, n - i) (the high 32 bits of word_i * (n - i)) and swaps perm[i], perm[j].  Host only (no GPU needed); the learner calls the same function.
+ * OPRL_ERR_INVALID unless 1 <= m <= n <= OPRL_MAX_CRITICS. */
+int oprl_redq_subset(uint64_t seed, int32_t rank, uint64_t counter, int32_t n, int32_t m, int32_t* out_host);
 /* device pointer to the per-row Q / TD-target of the last critic step ([B] each,
  * critic 0), for parity tests. */
 int oprl_learner_debug_ptrs(oprl_learner* h, const float** q, const float** y);

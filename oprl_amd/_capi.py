@@ -10,10 +10,10 @@ import ctypes as C
 import os
 from pathlib import Path
 
-OPRL_ABI_VERSION = 2
+OPRL_ABI_VERSION = 3
 OPRL_MAX_LAYERS = 4
-OPRL_MAX_CRITICS = 5
-ALGO = {"ddpg": 0, "td3": 1, "sac": 2, "tqc": 3}
+OPRL_MAX_CRITICS = 10
+ALGO = {"ddpg": 0, "td3": 1, "sac": 2, "tqc": 3, "redq": 4}
 PRECISION = {"f32": 0, "bf16": 1, "x2": 2}
 ACT_NONE, ACT_TANH, ACT_GAUSS_MEAN = 0, 1, 4
 
@@ -45,6 +45,7 @@ class OprlHparams(C.Structure):
         ("policy_freq", C.c_int32),
         ("tune_alpha", C.c_int32),
         ("n_quantiles", C.c_int32), ("top_quantiles_to_drop", C.c_int32),
+        ("n_min", C.c_int32),
     ]
 
 
@@ -94,6 +95,7 @@ SIGNATURES = {
     "oprl_learner_debug_form": (C.c_int, [_P, _I32, _P]),
     "oprl_debug_noise": (C.c_int, [_P, _I32, _U64, _I32, _I32, _P, _P]),
     "oprl_learner_set_seed": (C.c_int, [_P, _U64, _I32]),
+    "oprl_redq_subset": (C.c_int, [_U64, _I32, _U64, _I32, _I32, C.POINTER(C.c_int32)]),
     "oprl_learner_debug_ptrs": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "oprl_learner_debug_view": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "oprl_net_pack_floats": (_I64, [C.POINTER(OprlNet)]),

@@ -510,4 +510,24 @@ hipError_t launch_tqc_target(const float* z, long net_stride, int ldz, int n_net
   return hipGetLastError();
 }
 
+// REDQ's TD-target minimum over M > 2 target critics (M <= 2: SEED_MSE_TD takes the two rows itself):
+// out[b] = min_{j<M} q[j * net_stride + b * ldq] for b < B.  One lane per row (wave64, 256-thread blocks): with scalar
+// critics (ldq = 1) a wave's 64 loads of one net's row block are consecutive words.  The comparison order is the
+// subset's slot order; a minimum is exact in any order.
+__global__ __launch_bounds__(256) void k_redq_min(const float* __restrict__ q, long net_stride, int ldq, int M, int B,
+                                                  float* __restrict__ out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const float* p = q + (size_t)b * ldq;
+  float m = p[0];
+  for (int j = 1; j < M; ++j) m = fminf(m, p[(size_t)j * net_stride]);
+  out[b] = m;
+}
+
+hipError_t launch_redq_min(const float* q, long net_stride, int ldq, int M, int B, float* out, hipStream_t st) {
+  if (M < 1 || B < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_redq_min, dim3((B + 255) / 256), dim3(256), 0, st, q, net_stride, ldq, M, B, out);
+  return hipGetLastError();
+}
+
 }  // namespace oprl

@@ -7,6 +7,7 @@
 //   DDPG  algos/ddpg.py:61-107      TD3  algos/td3.py:71-146
 //   SAC   algos/sac.py:75-155       TQC  algos/tqc.py:116-189
 #include "learner_internal.h"
+#include "philox.h"
 
 namespace oprl {
 
@@ -383,6 +384,33 @@ hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st) {
   return e;
 }
 
+// launch_j(j0, st) and launch_j(j0 + 1, st): twin nets on the same slices — their cluster launches (slice_tp.hip) go
+// out as ONE launch
+template <class F>
+int pair_launch(oprl_learner* h, int j0, hipStream_t st, F& launch_j) {
+  h->pair_collect = true;
+  h->pair_n = 0;
+  int rc = launch_j(j0, st);
+  if (rc == OPRL_OK) rc = launch_j(j0 + 1, st);
+  h->pair_collect = false;
+  RC(rc);
+  if (h->pair_n == 2 && h->pair_args[0].B == h->pair_args[1].B) {
+    prof_begin(0, st);
+    hipError_t e = launch_mlp_slice_tp2(h->pair_args[0], h->pair_args[1], h->n_cus, st);
+    prof_end(st);
+    HIPC(e);
+  } else {
+    for (int k = 0; k < h->pair_n; ++k) {
+      prof_begin(0, st);
+      hipError_t e = launch_mlp_slice_tp(h->pair_args[k], st);
+      prof_end(st);
+      HIPC(e);
+    }
+  }
+  h->pair_n = 0;
+  return OPRL_OK;
+}
+
 // Run launch_j(j, stream) for j in [0, n): net 0 on the caller's stream, the others on
 // side streams forked from / joined back into it, so independent nets overlap on the GPU
 // (each k_mlp_slice launch occupies only ceil(B/16) of the 256 CUs).
@@ -390,30 +418,7 @@ template <class F>
 int for_each_net(oprl_learner* h, int n, hipStream_t st, F&& launch_j) {
   // measured: the event fork/join costs more than it saves for 2 nets (TD3 8.8k -> 7.7k/s),
   // pays for the 5 quantile critics of TQC (673 -> 1206/s)
-  if (n == 2) {
-    // twin nets on the same slices: their cluster launches (slice_tp.hip) go out as ONE launch
-    h->pair_collect = true;
-    h->pair_n = 0;
-    int rc = launch_j(0, st);
-    if (rc == OPRL_OK) rc = launch_j(1, st);
-    h->pair_collect = false;
-    RC(rc);
-    if (h->pair_n == 2 && h->pair_args[0].B == h->pair_args[1].B) {
-      prof_begin(0, st);
-      hipError_t e = launch_mlp_slice_tp2(h->pair_args[0], h->pair_args[1], h->n_cus, st);
-      prof_end(st);
-      HIPC(e);
-    } else {
-      for (int k = 0; k < h->pair_n; ++k) {
-        prof_begin(0, st);
-        hipError_t e = launch_mlp_slice_tp(h->pair_args[k], st);
-        prof_end(st);
-        HIPC(e);
-      }
-    }
-    h->pair_n = 0;
-    return OPRL_OK;
-  }
+  if (n == 2) return pair_launch(h, 0, st, launch_j);
   if (n > 2 && n <= kMaxMulti) {
     // equal nets on the same slices (TQC's quantile critics): one launch, grid (slices, nets)
     h->multi_collect = true;
@@ -528,6 +533,16 @@ int for_each_net(oprl_learner* h, int n, hipStream_t st, F&& launch_j) {
     h->multi_n = 0;
     return OPRL_OK;
   }
+  if (n > kMaxMulti && h->tp_generic_on) {
+    // more nets than a multi launch takes (REDQ's ensemble): in pairs on the caller's stream, each pair one k_mlp_slice_tp2
+    // launch (side by side, each net in its own exchange area, while both fit the chip).  Not on the side streams: every
+    // cluster launch of a learner exchanges through the same area of xbuf, and two such launches running at once would
+    // overwrite each other's granules
+    for (int j0 = 0; j0 < n; j0 += 2) {
+      RC(j0 + 1 == n ? launch_j(j0, st) : pair_launch(h, j0, st, launch_j));
+    }
+    return OPRL_OK;
+  }
   if (n <= 2 || !h->have_side) {
     for (int j = 0; j < n; ++j) RC(launch_j(j, st));
     return OPRL_OK;
@@ -544,14 +559,19 @@ int for_each_net(oprl_learner* h, int n, hipStream_t st, F&& launch_j) {
 }
 
 const double* alpha_ptr(const oprl_learner* h) {
-  const bool learned = h->cfg.algo == OPRL_TQC || (h->cfg.algo == OPRL_SAC && h->cfg.hp.tune_alpha);
+  const bool learned = h->cfg.algo == OPRL_TQC || ((h->cfg.algo == OPRL_SAC || h->cfg.algo == OPRL_REDQ) && h->cfg.hp.tune_alpha);
   return learned ? h->cfg.log_alpha : nullptr;
 }
 
-// Philox key of noise stream `stream_id` (1: next-state draw / TD3 smoothing, 2: actor-step draw).
+// the tanh-Gaussian actor (output 2A, reparameterised draws, entropy term): SAC, TQC, REDQ
+bool gauss_actor(const oprl_learner* h) {
+  return h->cfg.algo == OPRL_SAC || h->cfg.algo == OPRL_TQC || h->cfg.algo == OPRL_REDQ;
+}
+
+// Philox key of noise stream `stream_id` (1: next-state draw / TD3 smoothing, 2: actor-step draw, 3: REDQ's target subset).
 // Seed 0 on rank 0 is the bare stream constant; anything else is mixed in (splitmix64 finaliser).
-unsigned long long noise_key(const oprl_learner* h, uint64_t stream_id) {
-  uint64_t x = h->noise_seed ^ ((uint64_t)h->noise_rank * 0x9E3779B97F4A7C15ULL);
+unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id) {
+  uint64_t x = seed ^ ((uint64_t)rank * 0x9E3779B97F4A7C15ULL);
   if (x != 0) {
     x += 0x9E3779B97F4A7C15ULL;
     x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
@@ -559,6 +579,25 @@ unsigned long long noise_key(const oprl_learner* h, uint64_t stream_id) {
     x ^= x >> 31;
   }
   return 0x0b5e55edULL + stream_id + x;
+}
+unsigned long long noise_key(const oprl_learner* h, uint64_t stream_id) { return noise_key(h->noise_seed, h->noise_rank, stream_id); }
+
+// REDQ's target subset (include/oprl_amd.h oprl_redq_subset): a partial Fisher-Yates shuffle of 0 .. n-1 driven by the
+// words of Philox blocks (stream 3, counter `counter`, block index in the third counter word)
+void redq_subset(uint64_t seed, int rank, uint64_t counter, int n, int m, int* out) {
+  const unsigned long long key = noise_key(seed, rank, 3);
+  int perm[OPRL_MAX_CRITICS];
+  for (int i = 0; i < n; ++i) perm[i] = i;
+  u32x4 blk = {0, 0, 0, 0};
+  for (int i = 0; i < m; ++i) {
+    if ((i & 3) == 0)
+      blk = philox4x32_10(u32x4{(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)(i >> 2), 0u}, (uint32_t)key,
+                          (uint32_t)(key >> 32));
+    const uint32_t w = (i & 3) == 0 ? blk.x : (i & 3) == 1 ? blk.y : (i & 3) == 2 ? blk.z : blk.w;
+    const int j = i + (int)bounded_u32(w, (uint32_t)(n - i));
+    const int t = perm[i]; perm[i] = perm[j]; perm[j] = t;
+    out[i] = perm[i];
+  }
 }
 
 void seed_rng(MlpArgs& a, const oprl_learner* h, const float* noise, uint64_t stream_id) {
@@ -817,7 +856,7 @@ int temperature_step(oprl_learner* h, int B, hipStream_t st) {
 // The dW + Adam (+ Polyak) launch of the critic(s) or the actor at batch B as the optimiser's step `step`.  Reads the
 // learner only: the caller commits the step (dw_commit) once the launch that carries it is out.  B = 0: the data-parallel
 // apply, fed from the all-reduced gradient arena (w_g / b_g) instead of the GEMM.
-// The critic's targets move when the actor is due (TD3: on actor steps only, td3.py:135-146), the actor's when it has any.
+// The critic's targets move when critic_targets_due (TD3: on actor steps only, td3.py:135-146), the actor's when it has any.
 DwArgs dw_args(const oprl_learner* h, bool critic, int B, int step) {
   const oprl_learner_config& c = h->cfg;
   DwArgs dw;
@@ -825,7 +864,7 @@ DwArgs dw_args(const oprl_learner* h, bool critic, int B, int step) {
   dw.n_items = critic ? h->n_items_critic : h->n_items_actor;
   dw.total_tiles = critic ? h->tiles_critic : h->tiles_actor;
   dw.ad = adam_scalars(h, critic ? c.hp.lr_critic : c.hp.lr_actor, step,
-                       critic ? actor_due(h) : c.actor.theta_target != nullptr, 1.0f);
+                       critic ? critic_targets_due(h) : c.actor.theta_target != nullptr, 1.0f);
   dw.B = B;
   if (B == 0) {
     dw.apply_only = 1;
@@ -886,7 +925,20 @@ int dw_step(oprl_learner* h, bool critic, int B, hipStream_t st, const PrefetchJ
     dw.ad.do_adam = 1;
     dw.ad.grad_scale = 1.0f / (float)h->p2p.world;
   }
-  HIPC(launch_dw_prof(h, dw, st));
+  if (dw.n_items > kDwMaxItems) {
+    // (REDQ's ensemble: more layers than one launch's table holds — launches of at most kDwMaxItems layers, each with the
+    // same step count and so the same Adam scalars; a riding job goes with the last)
+    if (h->dp_inline || dw.prefetch != nullptr) { set_err("internal: a split dW table with an exchange or riders"); return OPRL_ERR_STATE; }
+    DwArgs part = dw;
+    for (int i0 = 0; i0 < dw.n_items; i0 += kDwMaxItems) {
+      part.items = dw.items + i0;
+      part.n_items = std::min(kDwMaxItems, dw.n_items - i0);
+      part.alpha = i0 + kDwMaxItems >= dw.n_items ? dw.alpha : AlphaJob{};
+      HIPC(launch_dw_prof(h, part, st));
+    }
+  } else {
+    HIPC(launch_dw_prof(h, dw, st));
+  }
   dw_commit(h, critic, dw, 1);
   if (h->dp_inline) h->p2p.tile_seq = seq;
   return OPRL_OK;
@@ -895,7 +947,7 @@ int dw_step(oprl_learner* h, bool critic, int B, hipStream_t st, const PrefetchJ
 // the actor's forward on s with the activations kept for its backward (actor_phase step 5)
 MlpArgs actor_forward_args(oprl_learner* h, const float* s, int B, const float* noise1) {
   const oprl_learner_config& c = h->cfg;
-  const bool gauss = (c.algo == OPRL_SAC || c.algo == OPRL_TQC);
+  const bool gauss = gauss_actor(h);
   MlpArgs f = base_args(h, c.actor, false, B);
   f.do_fwd = 1;
   f.x0 = s; f.k0 = h->S;
@@ -1157,13 +1209,19 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
     J.target = h->target;
     h->tqc_job_pending = true;
   }
-  RC(for_each_net(h, nc, st, [&](int j, hipStream_t sj) {
-    MlpArgs f = base_args(h, c.critics[j], true, B);
+  // REDQ: only the M target critics of this update's subset run, net redq_subset[j] into slot j of qn
+  const bool redq = algo == OPRL_REDQ;
+  const int n_min = redq ? c.hp.n_min : 0;
+  if (redq) redq_subset(h->noise_seed, h->noise_rank, (uint64_t)h->update_count, nc, n_min, h->redq_subset);
+  RC(for_each_net(h, redq ? n_min : nc, st, [&](int j, hipStream_t sj) {
+    MlpArgs f = base_args(h, c.critics[redq ? h->redq_subset[j] : j], true, B);
     f.do_fwd = 1;
     f.x0 = s2; f.k0 = S; f.x1 = h->a2; f.k1 = A;
     f.out = h->qn + (size_t)j * h->Bmax * h->ldq; f.ldo = h->ldq;
     return launch(f, h->w_critic, sj);
   }));
+  // (M > 2: their minimum as one row, k_redq_min, into the TQC target's buffer, which REDQ does not use)
+  if (redq && n_min > 2) HIPC(launch_redq_min(h->qn, (long)h->Bmax * h->ldq, h->ldq, n_min, B, h->target, st));
   if (h->fin_tail0 >= 0) {                           // (the rest of the early first launch found no head launch to ride on)
     prof_begin(0, st);
     hipError_t e = launch_mlp_layerwise_first(h->fin_args, nc, h->fin_tail0, h->w_critic, h->n_cus, st, h->fin16 ? (h->x2 ? 2 : 1) : 0);
@@ -1207,7 +1265,11 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
       f.seed_mode = SEED_MSE_TD;
       sd.p0 = h->qn;
       sd.p1 = nc > 1 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
-      sd.p2 = (algo == OPRL_SAC) ? h->logp2 : nullptr;
+      if (redq) {      // the minimum over the subset's slots: one or two rows here, else k_redq_min's row
+        sd.p0 = n_min > 2 ? h->target : h->qn;
+        sd.p1 = n_min == 2 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
+      }
+      sd.p2 = (algo == OPRL_SAC || redq) ? h->logp2 : nullptr;
       sd.log_alpha = alpha_ptr(h); sd.alpha_const = (float)c.hp.alpha_init;
       sd.r = r; sd.d = d; sd.gamma = (float)c.hp.gamma;
       sd.cval = 1.0f / (float)B;
@@ -1278,7 +1340,7 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
   RC(fresh32_tables(h, 3, st));
   const int S = h->S, A = h->A, nc = h->nc;
   const int algo = c.algo;
-  const bool gauss = (algo == OPRL_SAC || algo == OPRL_TQC);
+  const bool gauss = gauss_actor(h);
   const int n_q = (algo == OPRL_TD3 || algo == OPRL_DDPG) ? 1 : nc;   // TD3 uses Q1 only
   // (the offers to the riding launches below never outlive this update: after an error return the next must not find one)
   struct ClearOffers {
@@ -1365,9 +1427,11 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
       f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
       f.seed_mode = SEED_CONST;
       f.seed.cval = (algo == OPRL_TQC) ? -1.0f / ((float)B * (float)nc * (float)c.hp.n_quantiles)
-                                       : -1.0f / (float)B;
+                    : (algo == OPRL_REDQ) ? -1.0f / ((float)B * (float)nc)      // the mean over the ensemble
+                                          : -1.0f / (float)B;
       f.dact_col0 = S; f.dact_cols = A; f.dact = h->da + (size_t)j * h->Bmax * A; f.lddact = A;
       if (j == 0) f.partials = h->part_a;
+      if (algo == OPRL_REDQ) f.partials = h->part_a + (size_t)j * ((B + kR - 1) / kR) * 4;   // (read_scalars: mean over all N)
       return launch(f, h->w_critic, sj);
     }));
   }
@@ -1435,8 +1499,16 @@ int repack_nets(const oprl_net* const* nets, int n_nets, int which, hipStream_t 
   return OPRL_OK;
 }
 
+// Does this update take an actor step?  TD3: on every policy_freq-th, counted from the first (td3.py:135); REDQ: on the
+// last of every G = policy_freq updates, (u + 1) % G == 0
 bool actor_due(const oprl_learner* h) {
+  if (h->cfg.algo == OPRL_REDQ) return (h->update_count + 1) % h->cfg.hp.policy_freq == 0;
   return h->cfg.algo != OPRL_TD3 || (h->update_count % h->cfg.hp.policy_freq == 0);
+}
+
+// Do the critic targets take their Polyak step in this update?  TD3: with the actor (td3.py:135-146); REDQ: on every update
+bool critic_targets_due(const oprl_learner* h) {
+  return h->cfg.algo == OPRL_REDQ || actor_due(h);
 }
 
 int check_batch(const oprl_learner* h, const void* s, const void* a, const void* r, const void* d,
@@ -1504,6 +1576,17 @@ extern "C" int oprl_learner_clear_error(oprl_learner* h) {
     if (code != 0 && w != 9 && !h->debug_expire) h->xcd_local = false;
     *(volatile unsigned*)h->err_host = 0;
   }
+  return OPRL_OK;
+}
+
+extern "C" int oprl_redq_subset(uint64_t seed, int32_t rank, uint64_t counter, int32_t n, int32_t m, int32_t* out_host) {
+  if (!out_host || rank < 0 || m < 1 || n < m || n > OPRL_MAX_CRITICS) {
+    set_err("oprl_redq_subset: need 1 <= m <= n <= %d (n=%d, m=%d), rank >= 0 and an output array", OPRL_MAX_CRITICS, n, m);
+    return OPRL_ERR_INVALID;
+  }
+  int out[OPRL_MAX_CRITICS];
+  redq_subset(seed, rank, counter, n, m, out);
+  for (int i = 0; i < m; ++i) out_host[i] = out[i];
   return OPRL_OK;
 }
 

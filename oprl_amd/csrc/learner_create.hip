@@ -37,14 +37,25 @@ Switches read_switches() {
 extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner** out) {
   if (!cfg || !out) { set_err("oprl_learner_create: null argument"); return OPRL_ERR_INVALID; }
   if (cfg->abi_version != OPRL_ABI_VERSION) { set_err("ABI version mismatch: caller %d, library %d", cfg->abi_version, OPRL_ABI_VERSION); return OPRL_ERR_INVALID; }
-  if (cfg->algo < OPRL_DDPG || cfg->algo > OPRL_TQC) { set_err("unknown algo %d", cfg->algo); return OPRL_ERR_INVALID; }
+  if (cfg->algo < OPRL_DDPG || cfg->algo > OPRL_REDQ) { set_err("unknown algo %d", cfg->algo); return OPRL_ERR_INVALID; }
   if (cfg->precision != OPRL_PREC_F32 && cfg->precision != OPRL_PREC_BF16 && cfg->precision != OPRL_PREC_X2) { set_err("precision %d unknown", cfg->precision); return OPRL_ERR_INVALID; }
-  const int nc_expect = cfg->algo == OPRL_DDPG ? 1 : (cfg->algo == OPRL_TQC ? cfg->n_critics : 2);
+  const int nc_expect = cfg->algo == OPRL_DDPG ? 1 : ((cfg->algo == OPRL_TQC || cfg->algo == OPRL_REDQ) ? cfg->n_critics : 2);
   if (cfg->n_critics != nc_expect || cfg->n_critics < 1 || cfg->n_critics > OPRL_MAX_CRITICS) {
     set_err("n_critics=%d invalid for algo %d", cfg->n_critics, cfg->algo);
     return OPRL_ERR_INVALID;
   }
   if (cfg->max_batch < 1 || cfg->state_dim < 1 || cfg->action_dim < 1) { set_err("bad dims"); return OPRL_ERR_INVALID; }
+  if (cfg->algo == OPRL_REDQ) {
+    // (the generic launch sequence only: outside the fused kernels a 16-bit mode would silently compute in fp32)
+    if (cfg->hp.n_min < 1 || cfg->hp.n_min > cfg->n_critics) { set_err("REDQ: n_min=%d outside [1, n_critics=%d]", cfg->hp.n_min, cfg->n_critics); return OPRL_ERR_INVALID; }
+    if (cfg->hp.policy_freq < 1) { set_err("REDQ: policy_freq (updates per actor step) %d < 1", cfg->hp.policy_freq); return OPRL_ERR_INVALID; }
+    if (cfg->precision != OPRL_PREC_F32) { set_err("REDQ: precision %d unsupported (f32 only)", cfg->precision); return OPRL_ERR_INVALID; }
+    if (cfg->export_grads) { set_err("REDQ: export_grads (data-parallel) unsupported"); return OPRL_ERR_INVALID; }
+    for (int j = 0; j < cfg->n_critics; ++j)
+      if (cfg->critics[j].n_layers < 1 || cfg->critics[j].n_layers > OPRL_MAX_LAYERS || cfg->critics[j].dims[cfg->critics[j].n_layers] != 1) {
+        set_err("REDQ: critic %d is not a scalar critic", j); return OPRL_ERR_INVALID;
+      }
+  }
   auto* h = new oprl_learner();
   h->cfg = *cfg;
   h->sw = read_switches();
@@ -63,7 +74,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
       set_err("critic %d: theta_target/adam_m/adam_v required", j); rc = OPRL_ERR_INVALID;
     }
   }
-  const bool gauss = cfg->algo == OPRL_SAC || cfg->algo == OPRL_TQC;
+  const bool gauss = cfg->algo == OPRL_SAC || cfg->algo == OPRL_TQC || cfg->algo == OPRL_REDQ;
   if (rc == OPRL_OK && cfg->actor.dims[0] != h->S) { set_err("actor input dim != S"); rc = OPRL_ERR_INVALID; }
   if (rc == OPRL_OK && cfg->actor.dims[cfg->actor.n_layers] != (gauss ? 2 : 1) * h->A) { set_err("actor output dim mismatch"); rc = OPRL_ERR_INVALID; }
   if (rc == OPRL_OK && (!cfg->actor.adam_m || !cfg->actor.adam_v)) { set_err("actor adam state required"); rc = OPRL_ERR_INVALID; }
@@ -75,7 +86,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
       set_err("TQC quantile configuration unsupported"); rc = OPRL_ERR_INVALID;
     }
   }
-  const bool learned_alpha = cfg->algo == OPRL_TQC || (cfg->algo == OPRL_SAC && cfg->hp.tune_alpha);
+  const bool learned_alpha = cfg->algo == OPRL_TQC || ((cfg->algo == OPRL_SAC || cfg->algo == OPRL_REDQ) && cfg->hp.tune_alpha);
   if (rc == OPRL_OK && learned_alpha && (!cfg->log_alpha || !cfg->log_alpha_m || !cfg->log_alpha_v)) {
     set_err("log_alpha and its Adam state are required"); rc = OPRL_ERR_INVALID;
   }
@@ -114,7 +125,8 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   for (int j = 0; j < nc; ++j) floats += net_ws_floats(cfg->critics[j], B);
   floats += (size_t)B * A + B + (size_t)nc * B * h->ldq + (size_t)B * A + (size_t)B * 2 * A + B +
             (size_t)nc * B * A + (size_t)nc * B + (size_t)B * 128 + 2 * (size_t)B;
-  floats += (size_t)(nc + 1) * n_slices * 4 + 16;
+  const int n_part_a = cfg->algo == OPRL_REDQ ? nc : 1;   // (REDQ: every critic's actor-step sums, the ensemble mean)
+  floats += (size_t)(nc + n_part_a) * n_slices * 4 + 16;
   floats += (size_t)B * (2 * S + A + 2);
   floats += 64 * 32 + 8 * (size_t)B + 512;      // (granule arrays: y, q1, q2, the twin's seeds; 256 gate flags)
   const int Bm = B < 256 ? B : 256;             // merged phase 2 serves one 256-row chunk
@@ -171,7 +183,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   h->ydbg = p.take<float>(B);
   h->qdbg = p.take<float>(B);
   h->part_c = p.take<float>((size_t)nc * n_slices * 4);
-  h->part_a = p.take<float>((size_t)n_slices * 4);
+  h->part_a = p.take<float>((size_t)n_part_a * n_slices * 4);
   h->scalars = p.take<float>(16);
   h->alpha_grad = cfg->log_alpha_grad ? cfg->log_alpha_grad : p.take<double>(2);
   h->y_granules = p.take<unsigned long long>((size_t)4 * B + 256);      // [TD target / seeds | q1 | q2 | 256 gate flags | the twin critic's seeds]

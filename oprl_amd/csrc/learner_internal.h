@@ -70,6 +70,7 @@ hipError_t launch_tqc_target(const float* z, long net_stride, int ldz, int n_net
                              const float* r, const float* d, const float* logp,
                              const double* log_alpha, float gamma, int B, float* target,
                              hipStream_t st);
+hipError_t launch_redq_min(const float* q, long net_stride, int ldq, int M, int B, float* out, hipStream_t st);
 int replay_dims(const oprl_replay* h, int* S, int* A);
 int replay_view(const oprl_replay* h, const float** states, const float** actions,
                 const float** rewards, const float** dones, const int** ends, int* n_eps, int* L,
@@ -314,6 +315,7 @@ struct oprl_learner {
   // step_n batch buffers
   float *bs = nullptr, *ba = nullptr, *br = nullptr, *bd = nullptr, *bs2 = nullptr;
   int64_t update_count = 0;
+  int redq_subset[OPRL_MAX_CRITICS] = {};   // REDQ: the target critics of the current update (oprl_redq_subset), slot j of qn = net redq_subset[j]
   int opt_step_critic = 0, opt_step_actor = 0, opt_step_alpha = 0;
   int last_B = 0;
   bool actor_updated_last = false;
@@ -322,8 +324,8 @@ struct oprl_learner {
   Rccl rccl;
   long n_critic_params = 0, n_actor_params = 0;
   // side streams: independent per-net launches (twin / quantile critics) run concurrently
-  hipStream_t side[OPRL_MAX_CRITICS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipEvent_t ev_fork = nullptr, ev_join[OPRL_MAX_CRITICS] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipStream_t side[OPRL_MAX_CRITICS] = {};
+  hipEvent_t ev_fork = nullptr, ev_join[OPRL_MAX_CRITICS] = {};
   bool have_side = false;
   bool fused = false;          // DDPG / TD3 / SAC two-kernel path (csrc/fused_ddpg.hip) is built for this learner
   const float* noise1_pending = nullptr;   // update()'s injected actor-phase draws: SAC's role C runs in phase 1
@@ -451,8 +453,8 @@ struct oprl_learner {
   bool chain_pf_last = false;  // ... and whether its last update stages the rows of the update after it
   const float* chain_set1[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the other staging set (set 0 = the update's rows)
   bool whole_done = false;     // this update's actor phase was part of the critic phase's launch
-  float* pack16[OPRL_MAX_CRITICS + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  float* pack16_t[OPRL_MAX_CRITICS + 1] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  float* pack16[OPRL_MAX_CRITICS + 1] = {};
+  float* pack16_t[OPRL_MAX_CRITICS + 1] = {};
   // prebuilt device repack tables: [0] critics online, [1] critics online+target, [2] actor (+target)
   RepackItem* rp_dev[3] = {nullptr, nullptr, nullptr};
   int rp_n[3] = {0, 0, 0}, rp_blocks[3] = {0, 0, 0};
@@ -463,6 +465,8 @@ namespace oprl_host {
 const double* alpha_ptr(const oprl_learner* h);
 void dev_free(void* p);
 bool actor_due(const oprl_learner* h);
+bool critic_targets_due(const oprl_learner* h);
+bool gauss_actor(const oprl_learner* h);
 hipError_t uc_alloc(void** out, size_t bytes);
 size_t net_ws_floats(const oprl_net& n, int B);
 int fresh32(const oprl_net* net, hipStream_t st);

@@ -16,10 +16,12 @@ extern "C" int oprl_learner_read_scalars(oprl_learner* h, float* out_host, int32
   // critic partials of all critics are contiguous: loss sums over critics (td1 + td2)
   HIPC(launch_reduce_partials(h->part_c, n_slices * h->nc, h->scalars, 0, loss_scale,
                               1.0f / ((float)B * (float)h->nc), st));
-  HIPC(launch_reduce_partials(h->part_a, n_slices, h->scalars, 4, 0.f, -1.0f / (float)B, st));
+  // (REDQ: the actor-step sums of every critic, -mean over the ensemble)
+  const int n_qa = c.algo == OPRL_REDQ ? h->nc : 1;
+  HIPC(launch_reduce_partials(h->part_a, n_slices * n_qa, h->scalars, 4, 0.f, -1.0f / ((float)B * (float)n_qa), st));
   // critic 0 alone (the reference logs q1, not the twin mean) and the mean log-density of the actor step
   HIPC(launch_reduce_partials(h->part_c, n_slices, h->scalars, 8, loss_scale, 1.0f / (float)B, st));
-  const bool gauss = c.algo == OPRL_SAC || c.algo == OPRL_TQC;
+  const bool gauss = gauss_actor(h);
   if (gauss) HIPC(launch_sum(h->logp, B, h->scalars, 12, 1.0f / (float)B, st));
   float host[16] = {0};
   HIPC(hipMemcpyAsync(host, h->scalars, sizeof(float) * 13, hipMemcpyDeviceToHost, st));

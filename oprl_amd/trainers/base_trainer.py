@@ -86,8 +86,10 @@ class BaseTrainer(TrainerProtocol):
                 self.algo.update_from_buffer(self.replay_buffer, self.batch_size)
             wanted = step % self.eval_interval == 0 or step % self.stdout_log_every == 0
             return self.replay_buffer.sample(self.batch_size)[2] if wanted else None
-        batch = self.replay_buffer.sample(self.batch_size)
-        self.algo.update(*batch)
+        # (an algorithm with an update-to-data ratio, REDQ: that many sample + update pairs per environment step)
+        for _ in range(int(getattr(self.algo, "utd_ratio", 1))):
+            batch = self.replay_buffer.sample(self.batch_size)
+            self.algo.update(*batch)
         return batch[2]
 
     def _quiet(self, step: int) -> bool:

@@ -1,4 +1,4 @@
-"""update() throughput of all four algorithms at the BASELINE.json configs
+"""update() throughput of the five algorithms at the BASELINE.json configs
 (parity-test cases 2-4 + DDPG), fixed synthetic minibatch resident in HBM, noise
 drawn on device — one Python call per update, so the fast paths are bound by the
 call rate — and, second column, oprl_learner_step_n (sampling from an HBM replay +
@@ -9,6 +9,7 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 import torch as t
 from oprl_amd.algos.ddpg import DDPG
+from oprl_amd.algos.redq import REDQ
 from oprl_amd.algos.sac import SAC
 from oprl_amd.algos.td3 import TD3
 from oprl_amd.algos.tqc import TQC
@@ -18,7 +19,8 @@ CASES = [("DDPG walker B=256", DDPG, 24, 6, 256, {}),
          ("TD3 cheetah B=256", TD3, 17, 6, 256, dict(log_every=10 ** 9)),
          ("SAC humanoid B=1024", SAC, 67, 21, 1024, dict(log_every=10 ** 9)),
          ("SAC walker tuned B=256", SAC, 24, 6, 256, dict(log_every=10 ** 9, tune_alpha=True)),
-         ("TQC walker B=256", TQC, 24, 6, 256, dict(log_every=10 ** 9))]
+         ("TQC walker B=256", TQC, 24, 6, 256, dict(log_every=10 ** 9)),
+         ("REDQ walker N=10 M=2 B=256", REDQ, 24, 6, 256, dict(log_every=10 ** 9))]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 only = sys.argv[2] if len(sys.argv) > 2 else ""     # substring filter on the case name
 precs = sys.argv[3].split(",") if len(sys.argv) > 3 else ["f32"]   # e.g. f32,bf16
