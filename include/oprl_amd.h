@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define OPRL_ABI_VERSION 3
+#define OPRL_ABI_VERSION 4
 #define OPRL_MAX_LAYERS 4   /* linear layers per MLP (TQC critic has 4) */
 #define OPRL_MAX_CRITICS 10 /* TQC n_nets (5), REDQ ensemble (10) */
 
@@ -412,6 +412,33 @@ int oprl_replay_set_lens(oprl_replay* h, const int32_t* ep_lens_host, int32_t ep
 int oprl_replay_sample(oprl_replay* h, int32_t B, const int64_t* idx, uint64_t seed,
                        uint64_t counter, float* out_s, float* out_a, float* out_r, float* out_d,
                        float* out_s2, int32_t* out_ep, int32_t* out_step, void* stream);
+
+/* ---- prioritized replay (Schaul et al., ICLR 2016, proportional variant) ------------------------------------------
+ * A sum tree over the E·L slots of a replay, in HBM next to it: leaf e·L + t is the priority of slot
+ * (e, t).  A slot is live when e < episodes_counter and t < ep_lens[e] (the set oprl_replay_sample draws from); every
+ * dead leaf is 0.  Every flush gives the slots it writes, and the slots that become live, p_max (the largest priority
+ * assigned so far, 1 before any update) and zeroes the slots that stop being live.  Every call below flushes first.
+ * enable: allocate the tree (once per replay) and start every live slot at p_max = 1; priorities are then
+ * (|delta| + eps)^alpha.  Replays that never call it are unchanged. */
+int oprl_replay_prio_enable(oprl_replay* h, double alpha, double eps, void* stream);
+/* B rows drawn with probability proportional to priority, stratified over B equal segments of the root's mass and
+ * keyed by (seed, counter): s, a, r, d, s2 as oprl_replay_sample writes them, the slots e·L + t in out_slot[B] (int32)
+ * and the importance weights (N·p_j / total)^-beta over their batch maximum in out_w[B].  The arithmetic of the draw is
+ * DESIGN.md §11's; a tree whose root is 0 gives slot -1 and weight 0. */
+int oprl_replay_prio_sample(oprl_replay* h, int32_t B, uint64_t seed, uint64_t counter, double beta, float* out_s,
+                            float* out_a, float* out_r, float* out_d, float* out_s2, int32_t* out_slot, float* out_w,
+                            void* stream);
+/* New priorities of the B slots slot[B] (int32, device) from td_abs[B] (device): (max(td_abs, 0) + eps)^alpha; a slot
+ * listed more than once takes the row with the largest index; p_max = max(p_max, the new priorities); slots that are no
+ * longer live stay 0. */
+int oprl_replay_prio_update(oprl_replay* h, int32_t B, const int32_t* slot, const float* td_abs, void* stream);
+/* Checkpoints and tests: the whole tree (every level, leaves first; layout in DESIGN.md §11) into tree_out[0 .. n)
+ * (device; NULL: none), its size in floats into *n_floats_host, p_max into *p_max_host (which synchronises `stream`);
+ * either host pointer may be NULL. */
+int oprl_replay_prio_read(oprl_replay* h, float* tree_out, int64_t n, int64_t* n_floats_host, float* p_max_host,
+                          void* stream);
+/* Restore leaves[E·L] (device; the entries of dead slots are taken as 0) and p_max (> 0); the nodes are rebuilt. */
+int oprl_replay_prio_load(oprl_replay* h, const float* leaves, float p_max, void* stream);
 
 #ifdef __cplusplus
 }

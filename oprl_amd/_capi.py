@@ -10,7 +10,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-OPRL_ABI_VERSION = 3
+OPRL_ABI_VERSION = 4
 OPRL_MAX_LAYERS = 4
 OPRL_MAX_CRITICS = 10
 ALGO = {"ddpg": 0, "td3": 1, "sac": 2, "tqc": 3, "redq": 4}
@@ -128,6 +128,11 @@ SIGNATURES = {
     "oprl_replay_write_flush": (C.c_int, [_P, _I32, _I32, _P, _P, _F, _F, C.POINTER(C.c_int32), _I32, _P]),
     "oprl_replay_set_lens": (C.c_int, [_P, C.POINTER(C.c_int32), _I32, _P]),
     "oprl_replay_sample": (C.c_int, [_P, _I32, _P, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oprl_replay_prio_enable": (C.c_int, [_P, _D, _D, _P]),
+    "oprl_replay_prio_sample": (C.c_int, [_P, _I32, _U64, _U64, _D, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oprl_replay_prio_update": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "oprl_replay_prio_read": (C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float), _P]),
+    "oprl_replay_prio_load": (C.c_int, [_P, _P, _F, _P]),
 }
 
 _lib = None

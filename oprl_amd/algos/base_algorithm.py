@@ -45,6 +45,7 @@ class OffPolicyAlgorithm(ABC):
         base_trainer.py:38-74).  The actor's forward for it rides behind the update in the same call
         (oprl_learner_step_act) and the next ``actor.explore(act_next)`` — with this very array — only collects the
         row: one host wait per environment step instead of update-sync, act-launch, act-sync."""
+        refuse_prioritized(self, replay_buffer)
         handle = getattr(replay_buffer, "handle", None)
         if handle is None or self.learner.export_grads:
             self.update(*replay_buffer.sample(batch_size))
@@ -79,6 +80,14 @@ class OffPolicyAlgorithm(ABC):
 
     def load_state_dict(self, sd: dict[str, Any]) -> None:
         self.learner.load_state_dict(sd)
+
+
+def refuse_prioritized(algo, replay_buffer) -> None:
+    """No learner applies importance weights yet: a prioritized buffer (buffers/prioritized_buffer.py) is refused
+    rather than sampled without them."""
+    if getattr(replay_buffer, "prioritized", False) and not getattr(algo, "prioritized", False):
+        raise ValueError(f"{type(algo).__name__} does not apply importance weights: it cannot train from a prioritized "
+                         "replay buffer (use EpisodicReplayBuffer)")
 
 
 def require_gpu(device: str) -> t.device:

@@ -20,7 +20,7 @@ import torch as t
 from torch import nn
 
 from oprl_amd import _capi
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, require_gpu
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, refuse_prioritized, require_gpu
 from oprl_amd.algos.nn_functions import disable_gradient
 from oprl_amd.algos.nn_models import MLP, GaussianActor, _forward_sa, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
@@ -139,6 +139,7 @@ class REDQ(OffPolicyAlgorithm):
         """``utd_ratio`` times ``update(*replay_buffer.sample(batch_size))`` as one ``step_n(K=utd_ratio)`` call.
         ``act_next``: the actor's forward of it rides behind the last update (``step_n(K - 1)`` + ``step_act``, the
         same updates bit for bit)."""
+        refuse_prioritized(self, replay_buffer)
         handle = getattr(replay_buffer, "handle", None)
         K = int(self.utd_ratio)
         if handle is None:

@@ -20,6 +20,7 @@
 #include "../../include/oprl_amd.h"
 #include "philox.h"
 #include "replay_index.h"
+#include "replay_internal.h"
 
 namespace oprl {
 void set_err(const char* fmt, ...);
@@ -172,31 +173,7 @@ constexpr int kDirectEnds = 2048;
 
 }  // namespace
 
-struct oprl_replay {
-  int E, L, S, A;
-  float *states, *actions, *rewards, *dones;
-  int* ends_dev = nullptr;
-  int n_eps = 0;
-  long n_transitions = 0;
-  // double-buffered pinned staging for add_transition rows and for ends uploads
-  int rowlen = 0;
-  float* stage_host[2] = {nullptr, nullptr};
-  float* stage_dev[2] = {nullptr, nullptr};
-  int* ends_host[2] = {nullptr, nullptr};
-  hipEvent_t stage_ev[2], ends_ev[2];
-  bool stage_busy[2] = {false, false}, ends_busy[2] = {false, false};
-  int cur = 0, ends_cur = 0, n_staged = 0;
-  // the device copies of the pinned buffers' addresses, and the ends-table upload oprl_replay_set_lens left for the
-  // next flush: entries [first, n) of ends_host[ends_cur] differ from what the device holds (ends_last = its mirror)
-  float* stage_map[2] = {nullptr, nullptr};
-  int* ends_map[2] = {nullptr, nullptr};
-  std::vector<int> ends_last;
-  bool ends_pending = false;
-  int ends_first = 0, ends_n = 0;
-  // the stream of the caller's most recent flush / sample / block write / table upload: where a staging buffer
-  // that fills up inside oprl_replay_write (which takes no stream) is flushed, so that the scatter stays ordered
-  // with the caller's later gathers
-};
+// (struct oprl_replay: replay_internal.h)
 
 extern "C" int oprl_replay_create(int32_t n_episodes, int32_t max_ep_len, int32_t state_dim,
                                   int32_t action_dim, float* states, float* actions,
@@ -228,6 +205,7 @@ extern "C" int oprl_replay_create(int32_t n_episodes, int32_t max_ep_len, int32_
 extern "C" int oprl_replay_destroy(oprl_replay* h) {
   if (!h) return OPRL_OK;
   (void)hipDeviceSynchronize();
+  oprl::prio_free(h->prio);
   (void)hipFree(h->ends_dev);
   for (int i = 0; i < 2; ++i) {
     (void)hipHostFree(h->stage_host[i]);
@@ -242,7 +220,7 @@ extern "C" int oprl_replay_destroy(oprl_replay* h) {
 
 extern "C" int oprl_replay_flush(oprl_replay* h, void* stream) {
   if (!h) { set_err("null replay handle"); return OPRL_ERR_INVALID; }
-  if (h->n_staged == 0 && !h->ends_pending) return OPRL_OK;
+  if (h->n_staged == 0 && !h->ends_pending && !(h->prio && h->prio->n_eps != h->n_eps)) return OPRL_OK;
   hipStream_t st = (hipStream_t)stream;
   const int c = h->cur, n = h->n_staged, ec = h->ends_cur;
   const int e_first = h->ends_pending ? h->ends_first : 0, e_n = h->ends_pending ? h->ends_n : 0;
@@ -263,6 +241,11 @@ extern "C" int oprl_replay_flush(oprl_replay* h, void* stream) {
     if (e_n > e_first)
       HIPC(hipMemcpyAsync(h->ends_dev + e_first, h->ends_host[ec] + e_first, sizeof(int) * (e_n - e_first),
                           hipMemcpyHostToDevice, st));
+  }
+  if (h->prio) {       // the sum tree of prioritized replay follows the rows and the table (replay_prio.hip)
+    const float* rows = n > 0 ? (direct ? h->stage_map[c] : h->stage_dev[c]) : nullptr;
+    int rc = oprl::prio_flush(h, rows, n, e_first, e_n, st);
+    if (rc != OPRL_OK) return rc;
   }
   if (n > 0) {
     HIPC(hipEventRecord(h->stage_ev[c], st));

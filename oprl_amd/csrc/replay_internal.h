@@ -1,0 +1,64 @@
+// replay_internal.h — the replay handle, shared by the uniform replay (replay.hip) and the sum tree of
+// prioritized replay (replay_prio.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/oprl_amd.h"
+
+namespace oprl {
+
+// Sum tree of prioritized replay.  Level 0 holds one leaf per slot (e, t) at e·L + t; level k + 1
+// holds one node per kPrioFan nodes of level k; the top level holds the root alone.  Every level is padded with zeros
+// to a multiple of kPrioFan, so a node's children are one aligned run of kPrioFan floats.  All levels live in `tree`,
+// level k at `off[k]`, the leaves first.
+constexpr int kPrioFan = 256;       // children per node: four per lane of one wave
+constexpr int kPrioMaxLevels = 8;
+struct PrioTree {
+  int n_levels = 0;                     // levels including the leaves (>= 2); the root is level n_levels - 1
+  long count[kPrioMaxLevels] = {};      // nodes per level before padding
+  long off[kPrioMaxLevels + 1] = {};    // offsets of the levels in `tree`; off[n_levels] = floats allocated
+  float* tree = nullptr;
+  int* dirty = nullptr;                 // one flag per node of levels >= 1 (level k at off[k] - off[1]): recompute it
+  int* lens = nullptr;                  // [E] the episode lengths the leaves stand for (0 = dead episode)
+  float* p_max = nullptr;               // device scalar: the largest priority ever assigned (1 before any update)
+  int* owner = nullptr;                 // [E·L] the batch row that sets a slot in a priority update, -1 between updates
+  int n_eps = 0;                        // the episodes_counter the leaves stand for
+  double alpha = 0.6, eps = 1e-6;
+  long long* idx = nullptr;             // sampler scratch: one flat transition index per row
+  int idx_cap = 0;
+};
+
+// Keep the leaves in step with a flush: the staged rows `rows` (n_rows records of `rowlen` floats, [ep, t] as int
+// bits first; device-readable) and the episode-table entries [ends_first, ends_n) it uploaded (ends_n = 0: none).
+// Called by oprl_replay_flush after its copies, on its stream.
+int prio_flush(oprl_replay* h, const float* rows, int n_rows, int ends_first, int ends_n, hipStream_t st);
+void prio_free(PrioTree* p);
+
+}  // namespace oprl
+
+struct oprl_replay {
+  int E, L, S, A;
+  float *states, *actions, *rewards, *dones;
+  int* ends_dev = nullptr;
+  int n_eps = 0;
+  long n_transitions = 0;
+  // double-buffered pinned staging for add_transition rows and for ends uploads
+  int rowlen = 0;
+  float* stage_host[2] = {nullptr, nullptr};
+  float* stage_dev[2] = {nullptr, nullptr};
+  int* ends_host[2] = {nullptr, nullptr};
+  hipEvent_t stage_ev[2], ends_ev[2];
+  bool stage_busy[2] = {false, false}, ends_busy[2] = {false, false};
+  int cur = 0, ends_cur = 0, n_staged = 0;
+  // the device copies of the pinned buffers' addresses, and the ends-table upload oprl_replay_set_lens left for the
+  // next flush: entries [first, n) of ends_host[ends_cur] differ from what the device holds (ends_last = its mirror)
+  float* stage_map[2] = {nullptr, nullptr};
+  int* ends_map[2] = {nullptr, nullptr};
+  std::vector<int> ends_last;
+  bool ends_pending = false;
+  int ends_first = 0, ends_n = 0;
+  oprl::PrioTree* prio = nullptr;       // the sum tree once oprl_replay_prio_enable ran, else null
+};

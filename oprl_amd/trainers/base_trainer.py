@@ -12,6 +12,7 @@ from typing import Callable
 import numpy as np
 import torch as t
 
+from oprl_amd.algos.base_algorithm import refuse_prioritized
 from oprl_amd.algos.protocols import AlgorithmProtocol
 from oprl_amd.buffers.protocols import ReplayBufferProtocol
 from oprl_amd.environment.protocols import EnvProtocol
@@ -50,6 +51,7 @@ class BaseTrainer(TrainerProtocol):
     def train(self) -> None:
         self.algo.check_created()
         self.replay_buffer.check_created()
+        refuse_prioritized(self.algo, self.replay_buffer)
         if self.fused_sample_update and hasattr(self.replay_buffer, "handle"):
             self.replay_buffer.eager_flush = True        # (buffers/episodic_buffer.py::add_transition)
         obs, _ = self.env.reset()
