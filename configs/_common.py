@@ -4,13 +4,14 @@ line, importing everything through the ``oprl`` alias package exactly as a refer
 from __future__ import annotations
 
 import sys
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from pathlib import Path
 from typing import Callable
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 from oprl.buffers.episodic_buffer import EpisodicReplayBuffer  # noqa: E402
+from oprl.buffers.nstep_buffer import NStepEpisodicReplayBuffer  # noqa: E402
 from oprl.environment import make_env as build_env  # noqa: E402
 from oprl.logging import make_text_logger_func  # noqa: E402
 from oprl.parse_args import parse_args  # noqa: E402
@@ -48,9 +49,12 @@ class TrainingScript:
                              device=self.args.device, precision=self.args.precision).create()
 
     def make_replay_buffer(self):
-        return EpisodicReplayBuffer(buffer_size_transitions=max(self.config.num_steps, REPLAY_TRANSITIONS),
-                                    state_dim=self.state_dim, action_dim=self.action_dim,
-                                    device=self.config.device).create()
+        kw = dict(buffer_size_transitions=max(self.config.num_steps, REPLAY_TRANSITIONS), state_dim=self.state_dim,
+                  action_dim=self.action_dim, device=self.config.device)
+        if self.args.n_step > 1:        # n-step returns: the sampler discounts with the ALGORITHM's gamma
+            gamma = next(f.default for f in fields(self.algo_cls) if f.name == "gamma")
+            return NStepEpisodicReplayBuffer(n_step=self.args.n_step, gamma=gamma, **kw).create()
+        return EpisodicReplayBuffer(**kw).create()
 
     def run(self) -> None:
         run_training(make_algo=self.make_algo, make_env=self.make_env, make_replay_buffer=self.make_replay_buffer,

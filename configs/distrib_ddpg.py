@@ -22,6 +22,7 @@ import torch.nn as nn  # noqa: E402
 from oprl.algos.ddpg import DDPG  # noqa: E402
 from oprl.algos.nn_models import DeterministicPolicy  # noqa: E402
 from oprl.buffers.episodic_buffer import EpisodicReplayBuffer  # noqa: E402
+from oprl.buffers.nstep_buffer import NStepEpisodicReplayBuffer  # noqa: E402
 from oprl.distrib import env_worker, policy_update_worker  # noqa: E402
 from oprl.environment import make_env as build_env  # noqa: E402
 from oprl.logging import FileTxtLogger, get_logs_path  # noqa: E402
@@ -63,8 +64,12 @@ def make_algo(logger, **overrides):
 
 def make_replay_buffer(**overrides):
     """``overrides``: a data-parallel rank's device and sampler seed (its own HBM shard)."""
-    return EpisodicReplayBuffer(buffer_size_transitions=REPLAY_TRANSITIONS, state_dim=OBS_DIM, action_dim=ACT_DIM,
-                                **{"device": cli.device, **overrides}).create()
+    kw = dict(buffer_size_transitions=REPLAY_TRANSITIONS, state_dim=OBS_DIM, action_dim=ACT_DIM,
+              **{"device": cli.device, **overrides})
+    if cli.n_step > 1:      # --n-step N: multi-step returns (the D4PG / Ape-X target), discounted with DDPG's gamma
+        gamma = DDPG.__dataclass_fields__["gamma"].default
+        return NStepEpisodicReplayBuffer(n_step=cli.n_step, gamma=gamma, **kw).create()
+    return EpisodicReplayBuffer(**kw).create()
 
 
 def make_logger():

@@ -413,6 +413,24 @@ int oprl_replay_sample(oprl_replay* h, int32_t B, const int64_t* idx, uint64_t s
                        uint64_t counter, float* out_s, float* out_a, float* out_r, float* out_d,
                        float* out_s2, int32_t* out_ep, int32_t* out_step, void* stream);
 
+/* ---- n-step returns ---------------------------------------------------------------------------------
+ * A replay in n-step mode samples, for a drawn slot (e, t), m = the steps taken: at most n, never past the episode's
+ * stored steps, none after the first step whose done is not 0.  The row it writes is
+ *   r = sum_{k<m} gamma^k r_{t+k},  d = 1 - gamma^(m-1) (1 - d_{t+m-1})  (d_t verbatim when m = 1),  s2 = s_{t+m},
+ * so that a learner's one-step target r + gamma (1 - d) q'(s2) IS the n-step target when its gamma is this one.
+ * set_nstep: 1 <= n <= 16, 0 < gamma <= 1 (else OPRL_ERR_INVALID); n = 1 switches the mode off.  With n > 1
+ * oprl_replay_sample and the learners' step_n / dp_step_n gather n-step rows (step_n / dp_step_n: OPRL_ERR_INVALID
+ * unless gamma equals the learner's hp.gamma; oprl_group_step_n refuses such a replay).  Not combined with prioritized
+ * replay: set_nstep(n > 1) on a prioritized handle and oprl_replay_prio_enable on an n-step handle return
+ * OPRL_ERR_STATE.  Host state only; replays that never call it are unchanged. */
+int oprl_replay_set_nstep(oprl_replay* h, int32_t n, double gamma);
+/* oprl_replay_sample with the handle's (n, gamma) through the n-step gather kernel — also at n = 1, where every output
+ * equals oprl_replay_sample's bit for bit — and, when out_m is non-NULL, the steps taken per row (int32[B]).  The
+ * index draw is oprl_replay_sample's: the same (seed, counter) picks the same (episode, step). */
+int oprl_replay_sample_nstep(oprl_replay* h, int32_t B, const int64_t* idx, uint64_t seed, uint64_t counter,
+                             float* out_s, float* out_a, float* out_r, float* out_d, float* out_s2, int32_t* out_ep,
+                             int32_t* out_step, int32_t* out_m, void* stream);
+
 /* ---- prioritized replay (Schaul et al., ICLR 2016, proportional variant) ------------------------------------------
  * A sum tree over the E·L slots of a replay, in HBM next to it: leaf e·L + t is the priority of slot
  * (e, t).  A slot is live when e < episodes_counter and t < ep_lens[e] (the set oprl_replay_sample draws from); every

@@ -9,7 +9,7 @@ _SUBMODULES = [
     "logging", "parse_args",
     "algos", "algos.protocols", "algos.base_algorithm", "algos.nn_models", "algos.nn_functions",
     "algos.ddpg", "algos.td3", "algos.sac", "algos.tqc", "algos.redq",
-    "buffers", "buffers.protocols", "buffers.episodic_buffer", "buffers.prioritized_buffer",
+    "buffers", "buffers.protocols", "buffers.episodic_buffer", "buffers.prioritized_buffer", "buffers.nstep_buffer",
     "environment", "environment.protocols", "environment.make_env",
     "runners", "runners.config", "runners.train", "runners.train_distrib",
     "trainers", "trainers.protocols", "trainers.base_trainer",

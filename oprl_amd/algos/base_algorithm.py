@@ -46,6 +46,7 @@ class OffPolicyAlgorithm(ABC):
         (oprl_learner_step_act) and the next ``actor.explore(act_next)`` — with this very array — only collects the
         row: one host wait per environment step instead of update-sync, act-launch, act-sync."""
         refuse_prioritized(self, replay_buffer)
+        check_nstep_gamma(self, replay_buffer)
         handle = getattr(replay_buffer, "handle", None)
         if handle is None or self.learner.export_grads:
             self.update(*replay_buffer.sample(batch_size))
@@ -88,6 +89,15 @@ def refuse_prioritized(algo, replay_buffer) -> None:
     if getattr(replay_buffer, "prioritized", False) and not getattr(algo, "prioritized", False):
         raise ValueError(f"{type(algo).__name__} does not apply importance weights: it cannot train from a prioritized "
                          "replay buffer (use EpisodicReplayBuffer)")
+
+
+def check_nstep_gamma(algo, replay_buffer) -> None:
+    """An n-step buffer (buffers/nstep_buffer.py) folds gamma^(m-1) into the done flag it writes and the learner
+    multiplies by its own gamma: the two discounts must be the same number."""
+    if getattr(replay_buffer, "n_step", 1) > 1 and replay_buffer.gamma != algo.gamma:
+        raise ValueError(f"the replay buffer samples {replay_buffer.n_step}-step returns with gamma={replay_buffer.gamma!r} "
+                         f"but {type(algo).__name__} discounts with gamma={algo.gamma!r}: build the buffer with the "
+                         "algorithm's gamma")
 
 
 def require_gpu(device: str) -> t.device:

@@ -20,7 +20,7 @@ import torch as t
 from torch import nn
 
 from oprl_amd import _capi
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, refuse_prioritized, require_gpu
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_nstep_gamma, refuse_prioritized, require_gpu
 from oprl_amd.algos.nn_functions import disable_gradient
 from oprl_amd.algos.nn_models import MLP, GaussianActor, _forward_sa, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
@@ -140,6 +140,7 @@ class REDQ(OffPolicyAlgorithm):
         ``act_next``: the actor's forward of it rides behind the last update (``step_n(K - 1)`` + ``step_act``, the
         same updates bit for bit)."""
         refuse_prioritized(self, replay_buffer)
+        check_nstep_gamma(self, replay_buffer)
         handle = getattr(replay_buffer, "handle", None)
         K = int(self.utd_ratio)
         if handle is None:

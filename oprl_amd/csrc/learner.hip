@@ -1737,7 +1737,17 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
   replay_dims(replay, &S, &A);
   if (S != h->S || A != h->A) { set_err("replay dims (%d,%d) != learner dims (%d,%d)", S, A, h->S, h->A); return OPRL_ERR_INVALID; }
   if (K < 0 || B < 1 || B > h->Bmax) { set_err("step_n: bad K/B"); return OPRL_ERR_INVALID; }
-  if (use_fused(h, B)) {
+  // An n-step replay (oprl_replay_set_nstep): the in-kernel gathers below read one-step rows, so such a
+  // replay goes through the sample + update loop at the end; the update still takes its fused form on the staged rows.
+  int nstep = 1;
+  double nstep_gamma = 0.0;
+  replay_nstep(replay, &nstep, &nstep_gamma);
+  if (nstep > 1 && nstep_gamma != h->cfg.hp.gamma) {
+    set_err("step_n: the replay's %d-step gamma %.17g is not the learner's %.17g (the sampler's gamma^(m-1) multiplies the learner's gamma)",
+            nstep, nstep_gamma, h->cfg.hp.gamma);
+    return OPRL_ERR_INVALID;
+  }
+  if (nstep == 1 && use_fused(h, B)) {
     // the slice kernels gather their own rows (same Philox draw / index map as k_replay_gather)
     BatchSrc& sc = h->src;
     RC(oprl_replay_flush(replay, stream));
@@ -1786,7 +1796,7 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
     h->staged_ready = false;
     return rc;
   }
-  if (h->cfg.algo == OPRL_TQC && h->batch_alt != nullptr && !h->sw.no_gather_ride && K > 1) {
+  if (nstep == 1 && h->cfg.algo == OPRL_TQC && h->batch_alt != nullptr && !h->sw.no_gather_ride && K > 1) {
     // the rows of update k + 1 are gathered by riders of update k's k_lw_dact launch (same draw as k_replay_gather)
     // into the other of two sets of batch rows; only the first update's rows are a launch
     PrefetchJob base;

@@ -205,7 +205,15 @@ extern "C" int oprl_learner_dp_step_n(oprl_learner* h, oprl_replay* replay, int3
   if (K < 0 || B < 1 || B > h->Bmax) { set_err("dp_step_n: bad K/B"); return OPRL_ERR_INVALID; }
   // every rank samples its own shard: the Philox key mixes the rank in
   const uint64_t rseed = seed * 0x9E3779B97F4A7C15ull + (uint64_t)dp_rank(h);
-  if (use_fused(h, B)) {
+  // an n-step replay takes the sample + dp_update loop at the end, as in oprl_learner_step_n
+  int nstep = 1;
+  double nstep_gamma = 0.0;
+  replay_nstep(replay, &nstep, &nstep_gamma);
+  if (nstep > 1 && nstep_gamma != h->cfg.hp.gamma) {
+    set_err("dp_step_n: the replay's %d-step gamma %.17g is not the learner's %.17g", nstep, nstep_gamma, h->cfg.hp.gamma);
+    return OPRL_ERR_INVALID;
+  }
+  if (nstep == 1 && use_fused(h, B)) {
     BatchSrc& sc = h->src;
     RC(oprl_replay_flush(replay, stream));
     long n_tr = 0;

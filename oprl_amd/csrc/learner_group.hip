@@ -120,6 +120,13 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
   int S = 0, A = 0;
   replay_dims(replay, &S, &A);
   if (S != h0->S || A != h0->A) { set_err("replay dims (%d,%d) != group dims (%d,%d)", S, A, h0->S, h0->A); return OPRL_ERR_INVALID; }
+  int nstep = 1;
+  double nstep_gamma = 0.0;
+  replay_nstep(replay, &nstep, &nstep_gamma);
+  if (nstep > 1) {     // the members gather their rows inside the group's launches, one step at a time
+    set_err("oprl_group_step_n: the replay samples %d-step returns (oprl_replay_set_nstep); packed learners take one-step replays only", nstep);
+    return OPRL_ERR_STATE;
+  }
   hipStream_t st = (hipStream_t)stream;
   RC(oprl_replay_flush(replay, stream));
   // everything that can be refused is checked BEFORE any member's counters move: the members advance together, so

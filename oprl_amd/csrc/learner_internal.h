@@ -72,6 +72,7 @@ hipError_t launch_tqc_target(const float* z, long net_stride, int ldz, int n_net
                              hipStream_t st);
 hipError_t launch_redq_min(const float* q, long net_stride, int ldq, int M, int B, float* out, hipStream_t st);
 int replay_dims(const oprl_replay* h, int* S, int* A);
+int replay_nstep(const oprl_replay* h, int* n, double* gamma);
 int replay_view(const oprl_replay* h, const float** states, const float** actions,
                 const float** rewards, const float** dones, const int** ends, int* n_eps, int* L,
                 long* n_transitions);

@@ -373,6 +373,8 @@ extern "C" int oprl_replay_sample(oprl_replay* h, int32_t B, const int64_t* idx,
     set_err("oprl_replay_sample: invalid argument");
     return OPRL_ERR_INVALID;
   }
+  if (h->nstep > 1)      // n-step mode (oprl_replay_set_nstep): the same draw, n-step rows (replay_nstep.hip)
+    return oprl_replay_sample_nstep(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
   if (h->n_transitions <= 0 || h->n_eps <= 0) {
     set_err("oprl_replay_sample: buffer is empty (np.random.randint(0, 0) raises in the reference)");
     return OPRL_ERR_STATE;
@@ -406,4 +408,6 @@ int replay_view(const oprl_replay* h, const float** states, const float** action
   *ends = h->ends_dev; *n_eps = h->n_eps; *L = h->L; *n_transitions = h->n_transitions;
   return 0;
 }
+// n-step mode of the handle (replay_nstep.hip): *n > 1 when oprl_replay_sample gathers n-step rows with *gamma
+int replay_nstep(const oprl_replay* h, int* n, double* gamma) { *n = h->nstep; *gamma = h->nstep_gamma; return 0; }
 }

@@ -34,6 +34,8 @@ struct PrioTree {
 // Keep the leaves in step with a flush: the staged rows `rows` (n_rows records of `rowlen` floats, [ep, t] as int
 // bits first; device-readable) and the episode-table entries [ends_first, ends_n) it uploaded (ends_n = 0: none).
 // Called by oprl_replay_flush after its copies, on its stream.
+constexpr int kNstepMax = 16;       // largest n of the n-step sampler (replay_nstep.hip: one lane per (sample, step))
+
 int prio_flush(oprl_replay* h, const float* rows, int n_rows, int ends_first, int ends_n, hipStream_t st);
 void prio_free(PrioTree* p);
 
@@ -61,4 +63,7 @@ struct oprl_replay {
   bool ends_pending = false;
   int ends_first = 0, ends_n = 0;
   oprl::PrioTree* prio = nullptr;       // the sum tree once oprl_replay_prio_enable ran, else null
+  // n-step mode (oprl_replay_set_nstep): with nstep > 1 oprl_replay_sample gathers n-step rows
+  int nstep = 1;
+  double nstep_gamma = 1.0;
 };

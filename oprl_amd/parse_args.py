@@ -14,6 +14,8 @@ _SHARED = (
     # exact fp32 — the reference's arithmetic, no input range.  "x2" is the faster parity mode, opt-in: it has a finite
     # range (|observation|, |hidden activation| < 4094, |w| < 256; leaving it raises from update() / check(), it is never
     # silent) — meant for normalised observations
+    # extension: multi-step returns out of the replay sampler (buffers/nstep_buffer.py)
+    ("--n-step", int, 1, "n-step returns: the sampler sums up to N discounted rewards and bootstraps N steps on (1..16; 1 = the reference's one-step targets)"),
     ("--precision", str, "f32", "f32 (exact fp32 MFMA, the default) | x2 (fp32 as fp16 hi + lo on the matrix cores: parity mode, |obs| < 4094) | bf16"),
 )
 _SINGLE = (

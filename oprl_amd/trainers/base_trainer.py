@@ -12,7 +12,7 @@ from typing import Callable
 import numpy as np
 import torch as t
 
-from oprl_amd.algos.base_algorithm import refuse_prioritized
+from oprl_amd.algos.base_algorithm import check_nstep_gamma, refuse_prioritized
 from oprl_amd.algos.protocols import AlgorithmProtocol
 from oprl_amd.buffers.protocols import ReplayBufferProtocol
 from oprl_amd.environment.protocols import EnvProtocol
@@ -52,6 +52,7 @@ class BaseTrainer(TrainerProtocol):
         self.algo.check_created()
         self.replay_buffer.check_created()
         refuse_prioritized(self.algo, self.replay_buffer)
+        check_nstep_gamma(self.algo, self.replay_buffer)
         if self.fused_sample_update and hasattr(self.replay_buffer, "handle"):
             self.replay_buffer.eager_flush = True        # (buffers/episodic_buffer.py::add_transition)
         obs, _ = self.env.reset()
