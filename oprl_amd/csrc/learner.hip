@@ -722,7 +722,7 @@ FusedForm fused_form(const oprl_learner* h, int B, bool dp_inline) {
 }
 
 // The kernel's arguments of a fused update of batch B: the form (fused_form) and the pointers and scalars it needs.
-DdpgArgs ddpg_args(oprl_learner* h, int B) {
+DdpgArgs ddpg_args(oprl_learner* h, const StepRows& rows, int B) {
   const oprl_learner_config& c = h->cfg;
   const FusedForm f = fused_form(h, B, h->dp_inline);
   DdpgArgs a;
@@ -757,8 +757,8 @@ DdpgArgs ddpg_args(oprl_learner* h, int B) {
     a.logp = h->logp;
   }
   a.B = B; a.S = h->S; a.A = h->A;
-  a.src = h->src;
-  a.next = h->next_src;
+  a.src = rows.cur;
+  a.next = rows.next;
   a.gamma = (float)c.hp.gamma;
   a.inv_B = 1.0f / (float)B;
   for (int l = 0; l < kMaxLayers; ++l) {
@@ -986,12 +986,12 @@ void actor_gate(const oprl_learner* h, const DdpgArgs& fa, int B, DwGate& g) {
 }
 
 // The whole update as k_ddpg_chain launches: phase 1's roles, the critic's tiles, role U + the actor's tiles, the critic
-// pass, of U updates (step_n: chain_u) per launch.  What the launch advances — the optimisers' step counts, the epochs,
+// pass, of U updates (rows.n_upd) per launch.  What the launch advances — the optimisers' step counts, the epochs,
 // the exchange tags and, data parallel, this rank's tile sequence — is committed once it is out: after an error return
 // Adam's bias corrections and the peers' sequence numbers are where they were.
-int whole_update(oprl_learner* h, DdpgArgs& fa, const FusedForm& form, int B, hipStream_t st) {
+int whole_update(oprl_learner* h, StepRows& rows, DdpgArgs& fa, const FusedForm& form, int B, hipStream_t st) {
   const int slices = (B + kR - 1) / kR;
-  const int U = h->chain_u < form.chain_max ? h->chain_u : form.chain_max;
+  const int U = rows.n_upd < form.chain_max ? rows.n_upd : form.chain_max;
   const int step_c = h->opt_step_critic + 1, step_a = h->opt_step_actor + 1;     // update 0's
   fa.prefetch_next = 0;
   DwKArgs kd;
@@ -1036,7 +1036,7 @@ int whole_update(oprl_learner* h, DdpgArgs& fa, const FusedForm& form, int B, hi
   memset((void*)&ca, 0, sizeof ca);
   ca.n_upd = U;
   ca.first_gather = fa.src.gather;
-  ca.pf_last = h->chain_pf_last ? 1 : 0;
+  ca.pf_last = rows.stage_after_last ? 1 : 0;
   ca.trace_u = U - 1;
   ca.rows = 16 + t_rows;
   ca.order = h->sw.chain_order;
@@ -1050,7 +1050,7 @@ int whole_update(oprl_learner* h, DdpgArgs& fa, const FusedForm& form, int B, hi
     ca.a_step[u] = sa_.step_size_host; ca.a_bc2[u] = sa_.bc2_sqrt_host;
   }
   ca.set0[0] = fa.src.s; ca.set0[1] = fa.src.a; ca.set0[2] = fa.src.r; ca.set0[3] = fa.src.d; ca.set0[4] = fa.src.s2;
-  for (int i = 0; i < 5; ++i) ca.set1[i] = h->chain_set1[i];
+  for (int i = 0; i < 5; ++i) ca.set1[i] = rows.other_set[i];
   if ((U > 1 || ca.pf_last) && ca.set1[0] == nullptr) { set_err("chain launch: no second staging set"); return OPRL_ERR_STATE; }
   ca.ct_fin = h->chain_flags; ca.at_fin = h->chain_flags + 192; ca.pf_done = h->chain_flags + 384;
   for (int w = 0; w < 4; ++w)
@@ -1090,12 +1090,13 @@ int whole_update(oprl_learner* h, DdpgArgs& fa, const FusedForm& form, int B, hi
   h->tp_tag = tag + 2u * (unsigned)U;
   h->epoch += (unsigned)(U - 1);
   h->whole_done = true;
+  rows.staged = rows.stage_after_last;                 // the launch's last update staged the next rows: set (cur + U) & 1
   return OPRL_OK;
 }
 
-int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
-                 const float* s2, int B, const float* noise0, hipStream_t st) {
+int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
+  const float *s = rows.cur.s, *a = rows.cur.a, *r = rows.cur.r, *d = rows.cur.d, *s2 = rows.cur.s2;
   if (use_fused(h, B)) {
     h->epoch += 1;
     if (h->epoch == 0 || h->epoch > 0xFFFFFFFFu - (unsigned)kChainMax) {   // the TD-target tag wrapped (or would inside a chain launch): retire every stale granule
@@ -1109,18 +1110,18 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
       }
     }
     const FusedForm form = fused_form(h, B, h->dp_inline);
-    DdpgArgs fa = ddpg_args(h, B);
+    DdpgArgs fa = ddpg_args(h, rows, B);
     if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));     // (a batch the lean kernels do not take: fp32 packs)
     fa.noise = noise0;
-    if (h->prefetch_p1 && h->prefetch_next) {
-      // (step_n sets prefetch_p1 only for a form with merged bits, which the rt2 form never has)
+    if (rows.stage == StepRows::kPhase1) {
+      // (step_n asks phase 1 to stage only for a form with merged bits, which the rt2 form never has)
       if (fa.rt2 != 0) { set_err("internal: phase 1 asked to stage the next rows in the rt2 form"); return OPRL_ERR_STATE; }
       fa.prefetch_p1 = 1;
-      h->staged_ready = true;
+      rows.staged = true;
     }
     if (h->trace != nullptr) fa.trace = h->trace;   // roles use slots 0 .. 1 + n_critics
     h->whole_done = false;
-    if (form.whole) return whole_update(h, fa, form, B, st);
+    if (form.whole) return whole_update(h, rows, fa, form, B, st);
     RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
     if ((fa.merged & 1) != 0) {
       // phase 1 and the critic's dW + Adam tiles as ONE launch: the tiles wait for the roles' flag granules
@@ -1288,19 +1289,20 @@ int critic_phase(oprl_learner* h, const float* s, const float* a, const float* r
 }
 
 // ------------------------------------------------------------- actor phase
-int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hipStream_t st) {
+int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
+  const float* s = rows.cur.s;
   if (h->whole_done) {          // (this update's actor step ran inside the critic phase's launch: k_ddpg_update)
     h->whole_done = false;
     return OPRL_OK;
   }
   if (use_fused(h, B)) {
-    DdpgArgs fa = ddpg_args(h, B);
+    DdpgArgs fa = ddpg_args(h, rows, B);
     if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));
     RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
     if (h->trace != nullptr && c.algo == OPRL_DDPG) fa.trace = h->trace + (size_t)3 * 64 * kTraceStamps * 2;   // slot 3
     else if (h->trace != nullptr && h->nc == 2) fa.trace = h->trace + (size_t)6 * 64 * kTraceStamps * 2;      // twin critics: roles 0 .. 3 are phase 1's, slot 6
-    fa.prefetch_next = h->prefetch_p1 ? 0 : h->prefetch_next;
+    fa.prefetch_next = rows.stage == StepRows::kPhase2 ? 1 : 0;
     // Where phase 2's own workgroups already fill the chip (SAC at B = 1024: 4 x 64), its prefetch row is a round of
     // its own; the actor's dW launch, which follows and leaves 40 % of the chip idle, carries the row instead
     // (prefetch_rows_direct, the same rows).
@@ -1308,15 +1310,15 @@ int actor_phase(oprl_learner* h, const float* s, int B, const float* noise1, hip
     PrefetchJob pj;
     {
       const int slices = (B + kR - 1) / kR;
-      const int rows = (fa.wide & 2) != 0 ? 8 : fa.nc * ((fa.sac && fa.p2_pair) ? 2 : 1);
-      if (fa.prefetch_next && (rows + 1) * slices > h->n_cus && !h->dp_inline) {
+      const int grid_rows = (fa.wide & 2) != 0 ? 8 : fa.nc * ((fa.sac && fa.p2_pair) ? 2 : 1);
+      if (fa.prefetch_next && (grid_rows + 1) * slices > h->n_cus && !h->dp_inline) {
         pf_on_dw = true;
         fa.prefetch_next = 0;
         memset((void*)&pj, 0, sizeof pj);
         pj.next = fa.next; pj.S = h->S; pj.A = h->A; pj.B = B; pj.z0 = -1;
       }
     }
-    if (h->prefetch_next && !h->prefetch_p1) h->staged_ready = true;
+    if (rows.stage == StepRows::kPhase2) rows.staged = true;
     if ((fa.merged & 2) != 0 && !pf_on_dw) {
       // phase 2 and the actor's dW + Adam tiles as ONE launch: the tiles wait for the du (first layer: dz1) granules
       const DwArgs dw = dw_args(h, false, B, h->opt_step_actor + 1);
@@ -1629,22 +1631,19 @@ extern "C" int oprl_profile_read(int64_t* counts_host, double* ms_host, int32_t 
 }
 extern "C" int oprl_abi_version(void) { return OPRL_ABI_VERSION; }
 
-extern "C" int oprl_learner_update_phase(oprl_learner* h, int32_t phase, const float* s,
-                                         const float* a, const float* r, const float* d,
-                                         const float* s2, int32_t B, const float* noise0,
-                                         const float* noise1, void* stream) {
-  RC(check_batch(h, s, a, r, d, s2, B));
+namespace oprl_host {
+int learner_update_phase(oprl_learner* h, int phase, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream) {
+  RC(check_batch(h, rows.cur.s, rows.cur.a, rows.cur.r, rows.cur.d, rows.cur.s2, B));
   RC(check_device_error(h));      // an expired wait of an earlier launch (asynchronous: whatever has run by now)
   hipStream_t st = (hipStream_t)stream;
   h->last_B = B;
   if (phase == 0) h->trace_slot = 0;
-  if (!h->src.gather) { h->src.s = s; h->src.a = a; h->src.r = r; h->src.d = d; h->src.s2 = s2; }
   h->noise1_pending = noise1;
-  if (phase == 0) return critic_phase(h, s, a, r, d, s2, B, noise0, st);
+  if (phase == 0) return critic_phase(h, rows, B, noise0, st);
   if (phase == 1) {
     h->actor_updated_last = actor_due(h);
     int rc = OPRL_OK;
-    if (h->actor_updated_last) rc = actor_phase(h, s, B, noise1, st);
+    if (h->actor_updated_last) rc = actor_phase(h, rows, B, noise1, st);
     if (rc == OPRL_OK) h->update_count += 1;
     return rc;
   }
@@ -1652,11 +1651,22 @@ extern "C" int oprl_learner_update_phase(oprl_learner* h, int32_t phase, const f
   return OPRL_ERR_INVALID;
 }
 
-extern "C" int oprl_learner_update(oprl_learner* h, const float* s, const float* a, const float* r,
-                                   const float* d, const float* s2, int32_t B, const float* noise0,
-                                   const float* noise1, void* stream) {
-  RC(oprl_learner_update_phase(h, 0, s, a, r, d, s2, B, noise0, noise1, stream));
-  return oprl_learner_update_phase(h, 1, s, a, r, d, s2, B, noise0, noise1, stream);
+int learner_update(oprl_learner* h, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream) {
+  RC(learner_update_phase(h, 0, rows, B, noise0, noise1, stream));
+  return learner_update_phase(h, 1, rows, B, noise0, noise1, stream);
+}
+}  // namespace oprl_host
+
+extern "C" int oprl_learner_update_phase(oprl_learner* h, int32_t phase, const float* s, const float* a, const float* r, const float* d,
+                                         const float* s2, int32_t B, const float* noise0, const float* noise1, void* stream) {
+  StepRows rows = plain_rows(s, a, r, d, s2);
+  return learner_update_phase(h, phase, rows, B, noise0, noise1, stream);
+}
+
+extern "C" int oprl_learner_update(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
+                                   const float* s2, int32_t B, const float* noise0, const float* noise1, void* stream) {
+  StepRows rows = plain_rows(s, a, r, d, s2);
+  return learner_update(h, rows, B, noise0, noise1, stream);
 }
 
 extern "C" int oprl_learner_apply(oprl_learner* h, int32_t phase, double grad_scale, void* stream) {
@@ -1680,47 +1690,86 @@ extern "C" int oprl_learner_apply(oprl_learner* h, int32_t phase, double grad_sc
 }
 
 namespace oprl_host {
-// step_n's K-loop as launches of up to chain_max updates each (k_ddpg_chain); h->src: the replay's view, seed set.
-// set[2][5]: the two staging sets.  Also the data-parallel loop when the gradient exchange is inside the tiles.
-int chain_loop(oprl_learner* h, int K, int B, float* (*set)[5], void* stream) {
-  BatchSrc& sc = h->src;
-  int cur = 0;
-  int rc = OPRL_OK;
-  h->staged_ready = false;
-  for (int k = 0; k < K && rc == OPRL_OK;) {
-    const int U = K - k < h->sw.chain_max ? K - k : h->sw.chain_max;
-    float** b = set[cur];
-    float** nb = set[cur ^ 1];
-    for (int i = 0; i < 5; ++i) h->chain_set1[i] = nb[i];
-    sc.counter = (unsigned long long)h->update_count;
-    h->next_src.counter = sc.counter + 1;
-    h->next_src.s = nb[0]; h->next_src.a = nb[1]; h->next_src.r = nb[2]; h->next_src.d = nb[3]; h->next_src.s2 = nb[4];
-    h->prefetch_next = 0;
-    sc.gather = h->staged_ready ? 0 : 1;
-    sc.s = b[0]; sc.a = b[1]; sc.r = b[2]; sc.d = b[3]; sc.s2 = b[4];      // (set 0 of the launch, gathered or staged)
-    h->chain_u = U;
-    h->chain_pf_last = k + U < K;
-    rc = oprl_learner_update(h, b[0], b[1], b[2], b[3], b[4], B, nullptr, nullptr, stream);
-    h->chain_u = 1;
-    if (rc == OPRL_OK) h->update_count += U - 1;        // (update() counted one)
-    h->staged_ready = h->chain_pf_last;                 // the launch's last update staged the next rows: set (cur + U) & 1
-    h->chain_pf_last = false;
-    for (int i = 0; i < 5; ++i) h->chain_set1[i] = nullptr;
-    cur = (cur + U) & 1;
-    k += U;
+int RowStager::check(const char* who, const oprl_learner* h, const oprl_replay* replay, bool packed, int K, int B, int* nstep) {
+  int S = 0, A = 0;
+  replay_dims(replay, &S, &A);
+  if (S != h->S || A != h->A) { set_err("replay dims (%d,%d) != %s dims (%d,%d)", S, A, packed ? "group" : "learner", h->S, h->A); return OPRL_ERR_INVALID; }
+  if (K < 0 || B < 1 || B > h->Bmax) { set_err("%s: bad K/B", who); return OPRL_ERR_INVALID; }
+  // An n-step replay (oprl_replay_set_nstep): the in-kernel gathers read one-step rows, so such a replay
+  // goes through the callers' sample + update loops; the update still takes its fused form on the sampled rows.
+  double gamma = 0.0;
+  replay_nstep(replay, nstep, &gamma);
+  if (*nstep > 1 && packed) {     // the members gather their rows inside the group's launches, one step at a time
+    set_err("%s: the replay samples %d-step returns (oprl_replay_set_nstep); packed learners take one-step replays only", who, *nstep);
+    return OPRL_ERR_STATE;
   }
-  sc.gather = 0;
-  h->prefetch_next = 0;
-  h->staged_ready = false;
-  return rc;
+  if (*nstep > 1 && gamma != h->cfg.hp.gamma) {
+    set_err("%s: the replay's %d-step gamma %.17g is not the learner's %.17g (the sampler's gamma^(m-1) multiplies the learner's gamma)",
+            who, *nstep, gamma, h->cfg.hp.gamma);
+    return OPRL_ERR_INVALID;
+  }
+  return OPRL_OK;
 }
 
-// step_n's two sets of batch rows {s, a, r, d, s2}: the learner's own and batch_alt
-void staging_sets(const oprl_learner* h, float* set[2][5]) {
+// The kernels gather their own rows (same Philox draw / index map as k_replay_gather): the first update in its slice
+// kernels, every later one from a staging set that a launch of the update before it has filled.
+int RowStager::open(const char* who, const oprl_learner* h, oprl_replay* replay, uint64_t seed, void* stream) {
+  RC(oprl_replay_flush(replay, stream));
+  rows = StepRows{};
+  BatchSrc& v = rows.cur;
+  long n_tr = 0;
+  replay_view(replay, &v.states, &v.actions, &v.rewards, &v.dones, &v.ends, &v.n_eps, &v.L, &n_tr);
+  if (n_tr <= 0 || v.n_eps <= 0) { set_err("%s: replay buffer is empty", who); return OPRL_ERR_STATE; }
+  v.n_transitions = n_tr;
+  v.gather = 1;
+  rows.next = v;
+  bind(h, seed);
+  return OPRL_OK;
+}
+
+void RowStager::bind(const oprl_learner* h, uint64_t seed) {
+  rows.cur.seed = rows.next.seed = seed;
   const size_t Bm = (size_t)h->Bmax;
   const size_t off[5] = {0, Bm * h->S, Bm * (h->S + h->A), Bm * (h->S + h->A + 1), Bm * (h->S + h->A + 2)};
   float* const own[5] = {h->bs, h->ba, h->br, h->bd, h->bs2};
-  for (int i = 0; i < 5; ++i) { set[0][i] = own[i]; set[1][i] = h->batch_alt + off[i]; }
+  for (int i = 0; i < 5; ++i) { set[0][i] = own[i]; set[1][i] = h->batch_alt != nullptr ? h->batch_alt + off[i] : own[i]; }
+}
+
+// The coming update reads set[cur]: staged there, else gathered by its own kernels.  Phase-1 staging fills the other set,
+// whose rows the update's own roles are not reading, and the sets alternate; phase-2 staging fills the set it has read.
+// K_left > 0: a k_ddpg_chain launch of U = min(K_left, chain_max) updates instead — update u of the launch stages the rows
+// of update u + 1 into the other set, the last one only when updates are left; the next launch reads set (cur + U) & 1.
+StepRows& RowStager::plan(const oprl_learner* h, StepRows::Stage stage, int K_left) {
+  const int U = K_left < h->sw.chain_max ? K_left : h->sw.chain_max;      // (0: not a chain launch)
+  const bool other = stage == StepRows::kPhase1 || U > 0;
+  float* const* b = set[cur];
+  float* const* nb = set[other ? cur ^ 1 : cur];
+  BatchSrc &c = rows.cur, &n = rows.next;
+  c.s = b[0]; c.a = b[1]; c.r = b[2]; c.d = b[3]; c.s2 = b[4];
+  n.s = nb[0]; n.a = nb[1]; n.r = nb[2]; n.d = nb[3]; n.s2 = nb[4];
+  c.counter = (unsigned long long)h->update_count;
+  n.counter = c.counter + 1;
+  c.gather = staged ? 0 : 1;
+  rows.stage = stage;
+  rows.n_upd = U > 0 ? U : 1;
+  rows.stage_after_last = U > 0 && U < K_left;
+  for (int i = 0; i < 5; ++i) rows.other_set[i] = U > 0 ? set[cur ^ 1][i] : nullptr;
+  rows.staged = false;
+  flip = other ? rows.n_upd : 0;
+  return rows;
+}
+
+// step_n's K-loop as launches of up to chain_max updates each (k_ddpg_chain).  Also the data-parallel loop when the gradient
+// exchange is inside the tiles.
+int chain_loop(oprl_learner* h, RowStager& stg, int K, int B, void* stream) {
+  for (int k = 0; k < K;) {
+    StepRows& rows = stg.plan(h, StepRows::kNone, K - k);
+    RC(learner_update(h, rows, B, nullptr, nullptr, stream));
+    h->update_count += rows.n_upd - 1;                  // (learner_update() counted one)
+    k += rows.n_upd;
+    stg.done();
+  }
+  return OPRL_OK;
 }
 
 // does step_n at this batch run as chain launches?
@@ -1733,108 +1782,53 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
                                    uint64_t seed, void* stream) {
   if (!h || !replay) { set_err("oprl_learner_step_n: null handle"); return OPRL_ERR_INVALID; }
   if (h->cfg.export_grads) { set_err("step_n is the single-GPU fused path; export_grads learners use update_phase/apply"); return OPRL_ERR_STATE; }
-  int S = 0, A = 0;
-  replay_dims(replay, &S, &A);
-  if (S != h->S || A != h->A) { set_err("replay dims (%d,%d) != learner dims (%d,%d)", S, A, h->S, h->A); return OPRL_ERR_INVALID; }
-  if (K < 0 || B < 1 || B > h->Bmax) { set_err("step_n: bad K/B"); return OPRL_ERR_INVALID; }
-  // An n-step replay (oprl_replay_set_nstep): the in-kernel gathers below read one-step rows, so such a
-  // replay goes through the sample + update loop at the end; the update still takes its fused form on the staged rows.
   int nstep = 1;
-  double nstep_gamma = 0.0;
-  replay_nstep(replay, &nstep, &nstep_gamma);
-  if (nstep > 1 && nstep_gamma != h->cfg.hp.gamma) {
-    set_err("step_n: the replay's %d-step gamma %.17g is not the learner's %.17g (the sampler's gamma^(m-1) multiplies the learner's gamma)",
-            nstep, nstep_gamma, h->cfg.hp.gamma);
-    return OPRL_ERR_INVALID;
-  }
+  RC(RowStager::check("step_n", h, replay, false, K, B, &nstep));
+  RowStager stg;
   if (nstep == 1 && use_fused(h, B)) {
-    // the slice kernels gather their own rows (same Philox draw / index map as k_replay_gather)
-    BatchSrc& sc = h->src;
-    RC(oprl_replay_flush(replay, stream));
-    long n_tr = 0;
-    replay_view(replay, &sc.states, &sc.actions, &sc.rewards, &sc.dones, &sc.ends, &sc.n_eps, &sc.L, &n_tr);
-    if (n_tr <= 0 || sc.n_eps <= 0) { set_err("step_n: replay buffer is empty"); return OPRL_ERR_STATE; }
-    sc.n_transitions = n_tr;
-    sc.seed = seed;
-    sc.gather = 1;
-    // The first update gathers in-kernel; every update's phase 2 also gathers the NEXT
-    // update's rows into the staging batch (h->bs ..), which phase 1 then reads as plain rows.
-    h->next_src = sc;
-    // With the merged phase 2 (whose roles fill the chip) PHASE 1 carries the next update's rows — every update, TD3's
-    // critic-only ones included — into the other of two staging sets, since its own roles are still reading theirs
-    float* set[2][5];
-    staging_sets(h, set);
+    RC(stg.open("step_n", h, replay, seed, stream));
     // k_ddpg_chain: up to chain_max updates per launch, the rows of update u + 1 staged by update u inside the launch
-    const bool chain = chain_ok(h, B);
+    if (chain_ok(h, B)) return chain_loop(h, stg, K, B, stream);
+    // Otherwise phase 2 of every update that has one gathers the next update's rows into the set it has read.  With the
+    // merged phase 2 (whose roles fill the chip) PHASE 1 carries them — every update, TD3's critic-only ones included — into
+    // the other of the two sets, since its own roles are still reading theirs ...
     const FusedForm probe = fused_form(h, B, h->dp_inline);
     // (... and TD3's merged twin launches in every arithmetic, r06-15: without the merged phase 2 — exact fp32, bf16 — a
     // critic-only update had no launch that staged the next rows, and the update behind it gathered its own inside the roles'
     // first stage: 4.8 us against 2.9 before the first barrier of every role of every second launch)
     const bool td3_p1 = h->cfg.algo == OPRL_TD3 && (probe.merged & 1) != 0 && !h->sw.no_p1_rows;
-    h->prefetch_p1 = !chain && h->batch_alt != nullptr && ((probe.merged & 2) != 0 || td3_p1);
-    int cur = 0;
-    int rc = OPRL_OK;
-    h->staged_ready = false;
-    if (chain) return chain_loop(h, K, B, set, stream);
-    for (int k = 0; k < K && rc == OPRL_OK; ++k) {
-      float** b = set[cur];
-      float** nb = set[h->prefetch_p1 ? cur ^ 1 : cur];
-      h->next_src.s = nb[0]; h->next_src.a = nb[1]; h->next_src.r = nb[2]; h->next_src.d = nb[3]; h->next_src.s2 = nb[4];
-      sc.counter = (unsigned long long)h->update_count;
-      h->next_src.counter = sc.counter + 1;
-      h->prefetch_next = (k + 1 < K) ? 1 : 0;
-      // rows staged by the previous update (phase 2 does not run on TD3's critic-only steps), else the slice kernels
-      // gather their own
-      sc.gather = h->staged_ready ? 0 : 1;
-      h->staged_ready = false;
-      rc = oprl_learner_update(h, b[0], b[1], b[2], b[3], b[4], B, nullptr, nullptr, stream);
-      if (h->prefetch_p1) cur ^= 1;
+    const bool p1 = h->batch_alt != nullptr && ((probe.merged & 2) != 0 || td3_p1);
+    for (int k = 0; k < K; ++k) {
+      RC(learner_update(h, stg.plan(h, k + 1 == K ? StepRows::kNone : p1 ? StepRows::kPhase1 : StepRows::kPhase2), B, nullptr, nullptr, stream));
+      stg.done();
     }
-    sc.gather = 0;
-    h->prefetch_next = 0;
-    h->prefetch_p1 = false;
-    h->staged_ready = false;
-    return rc;
+    return OPRL_OK;
   }
   if (nstep == 1 && h->cfg.algo == OPRL_TQC && h->batch_alt != nullptr && !h->sw.no_gather_ride && K > 1) {
     // the rows of update k + 1 are gathered by riders of update k's k_lw_dact launch (same draw as k_replay_gather)
     // into the other of two sets of batch rows; only the first update's rows are a launch
-    PrefetchJob base;
-    memset((void*)&base, 0, sizeof base);
-    RC(oprl_replay_flush(replay, stream));
-    long n_tr = 0;
-    replay_view(replay, &base.next.states, &base.next.actions, &base.next.rewards, &base.next.dones, &base.next.ends,
-                &base.next.n_eps, &base.next.L, &n_tr);
-    if (n_tr <= 0 || base.next.n_eps <= 0) { set_err("step_n: replay buffer is empty"); return OPRL_ERR_STATE; }
-    base.next.n_transitions = n_tr;
-    base.next.seed = seed;
-    base.next.gather = 1;
-    base.S = h->S; base.A = h->A; base.B = B; base.z0 = -1;
-    float* set[2][5];
-    staging_sets(h, set);
-    int cur = 0;
-    bool staged = false;
+    RC(stg.open("step_n", h, replay, seed, stream));
     int rc = OPRL_OK;
     for (int k = 0; k < K && rc == OPRL_OK; ++k) {
-      float** b = set[cur];
-      if (!staged)
+      StepRows& rows = stg.plan(h, StepRows::kPhase1);    // (the sets alternate as under phase-1 staging)
+      float* const* b = stg.set[stg.cur];
+      if (rows.cur.gather)
         rc = oprl_replay_sample(replay, B, nullptr, seed, (uint64_t)h->update_count, b[0], b[1], b[2], b[3], b[4], nullptr, nullptr, stream);
-      staged = false;
       h->prefetch_done = false;
       h->prefetch_pending = false;
       if (rc == OPRL_OK && k + 1 < K) {
-        float** nb = set[cur ^ 1];
-        h->prefetch = base;
-        h->prefetch.next.counter = (unsigned long long)h->update_count + 1;
-        h->prefetch.next.s = nb[0]; h->prefetch.next.a = nb[1]; h->prefetch.next.r = nb[2]; h->prefetch.next.d = nb[3];
-        h->prefetch.next.s2 = nb[4];
+        memset((void*)&h->prefetch, 0, sizeof h->prefetch);
+        h->prefetch.next = rows.next;
+        h->prefetch.S = h->S; h->prefetch.A = h->A; h->prefetch.B = B; h->prefetch.z0 = -1;
         h->prefetch_pending = true;
       }
-      if (rc == OPRL_OK) rc = oprl_learner_update(h, b[0], b[1], b[2], b[3], b[4], B, nullptr, nullptr, stream);
+      rows.cur.gather = 0;                                // the generic launches read plain rows and know no stage:
+      rows.stage = StepRows::kNone;                       // the next rows travel as the offer above
+      if (rc == OPRL_OK) rc = learner_update(h, rows, B, nullptr, nullptr, stream);
       h->prefetch_pending = false;
-      staged = h->prefetch_done;
+      rows.staged = h->prefetch_done;
       h->prefetch_done = false;
-      cur ^= 1;
+      stg.done();
     }
     return rc;
   }

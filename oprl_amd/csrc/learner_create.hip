@@ -104,8 +104,6 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   if (e == hipSuccess) e = init_slice_tp_attrs();
   if (e == hipSuccess) e = init_layerwise_attrs();
   if (e != hipSuccess) { set_err("hipFuncSetAttribute: %s", hipGetErrorString(e)); delete h; return OPRL_ERR_HIP; }
-  memset(&h->src, 0, sizeof h->src);
-  memset(&h->next_src, 0, sizeof h->next_src);
   if (h->nc > 2) {
     bool ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
     for (int j = 1; ok && j < h->nc; ++j)

@@ -159,12 +159,8 @@ int dp_all_reduce(oprl_learner* h, void* buf, size_t n, bool as_double, hipStrea
   NCCLC(h, h->rccl.all_reduce(buf, buf, n, as_double ? kNcclFloat64 : kNcclFloat32, kNcclSum, h->rccl.comm, st));
   return OPRL_OK;
 }
-}  // namespace
 
-
-extern "C" int oprl_learner_dp_update(oprl_learner* h, const float* s, const float* a, const float* r,
-                                      const float* d, const float* s2, int32_t B, const float* noise0,
-                                      const float* noise1, void* stream) {
+int dp_update(oprl_learner* h, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream) {
   if (!h || (!h->rccl.comm && !h->p2p_ok)) { set_err("oprl_learner_dp_update: call oprl_comm_init (or connect the peer windows) first"); return OPRL_ERR_STATE; }
   hipStream_t st = (hipStream_t)stream;
   const oprl_learner_config& c = h->cfg;
@@ -173,8 +169,7 @@ extern "C" int oprl_learner_dp_update(oprl_learner* h, const float* s, const flo
   // run Adam on the mean — no separate all-reduce or apply launches.
   if (h->p2p_ok && h->p2p_inline && !h->sw.no_dp_inline && h->p2p.tile_bytes > 0 && use_fused(h, B)) {
     h->dp_inline = true;
-    int rc = oprl_learner_update_phase(h, 0, s, a, r, d, s2, B, noise0, noise1, stream);
-    if (rc == OPRL_OK) rc = oprl_learner_update_phase(h, 1, s, a, r, d, s2, B, noise0, noise1, stream);
+    const int rc = learner_update(h, rows, B, noise0, noise1, stream);
     h->dp_inline = false;
     RC(rc);
     if (h->actor_updated_last && alpha_ptr(h) != nullptr) {   // the temperature: one double, exchanged on its own
@@ -183,10 +178,10 @@ extern "C" int oprl_learner_dp_update(oprl_learner* h, const float* s, const flo
     }
     return OPRL_OK;
   }
-  RC(oprl_learner_update_phase(h, 0, s, a, r, d, s2, B, noise0, noise1, stream));
+  RC(learner_update_phase(h, 0, rows, B, noise0, noise1, stream));
   RC(dp_all_reduce(h, c.critics[0].grad, (size_t)h->n_critic_params, false, st));
   RC(oprl_learner_apply(h, 0, scale, stream));
-  RC(oprl_learner_update_phase(h, 1, s, a, r, d, s2, B, noise0, noise1, stream));
+  RC(learner_update_phase(h, 1, rows, B, noise0, noise1, stream));
   if (h->actor_updated_last) {
     RC(dp_all_reduce(h, c.actor.grad, (size_t)h->n_actor_params, false, st));
     if (alpha_ptr(h) != nullptr) RC(dp_all_reduce(h, h->alpha_grad, 1, true, st));
@@ -194,67 +189,42 @@ extern "C" int oprl_learner_dp_update(oprl_learner* h, const float* s, const flo
   }
   return OPRL_OK;
 }
+}  // namespace
+
+extern "C" int oprl_learner_dp_update(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
+                                      const float* s2, int32_t B, const float* noise0, const float* noise1, void* stream) {
+  StepRows rows = plain_rows(s, a, r, d, s2);
+  return dp_update(h, rows, B, noise0, noise1, stream);
+}
 
 extern "C" int oprl_learner_dp_step_n(oprl_learner* h, oprl_replay* replay, int32_t K, int32_t B,
                                       uint64_t seed, void* stream) {
   if (!h || !replay) { set_err("oprl_learner_dp_step_n: null handle"); return OPRL_ERR_INVALID; }
   if (!h->rccl.comm && !h->p2p_ok) { set_err("oprl_learner_dp_step_n: call oprl_comm_init (or connect the peer windows) first"); return OPRL_ERR_STATE; }
-  int S = 0, A = 0;
-  replay_dims(replay, &S, &A);
-  if (S != h->S || A != h->A) { set_err("replay dims (%d,%d) != learner dims (%d,%d)", S, A, h->S, h->A); return OPRL_ERR_INVALID; }
-  if (K < 0 || B < 1 || B > h->Bmax) { set_err("dp_step_n: bad K/B"); return OPRL_ERR_INVALID; }
-  // every rank samples its own shard: the Philox key mixes the rank in
-  const uint64_t rseed = seed * 0x9E3779B97F4A7C15ull + (uint64_t)dp_rank(h);
   // an n-step replay takes the sample + dp_update loop at the end, as in oprl_learner_step_n
   int nstep = 1;
-  double nstep_gamma = 0.0;
-  replay_nstep(replay, &nstep, &nstep_gamma);
-  if (nstep > 1 && nstep_gamma != h->cfg.hp.gamma) {
-    set_err("dp_step_n: the replay's %d-step gamma %.17g is not the learner's %.17g", nstep, nstep_gamma, h->cfg.hp.gamma);
-    return OPRL_ERR_INVALID;
-  }
+  RC(RowStager::check("dp_step_n", h, replay, false, K, B, &nstep));
+  // every rank samples its own shard: the Philox key mixes the rank in
+  const uint64_t rseed = seed * 0x9E3779B97F4A7C15ull + (uint64_t)dp_rank(h);
   if (nstep == 1 && use_fused(h, B)) {
-    BatchSrc& sc = h->src;
-    RC(oprl_replay_flush(replay, stream));
-    long n_tr = 0;
-    replay_view(replay, &sc.states, &sc.actions, &sc.rewards, &sc.dones, &sc.ends, &sc.n_eps, &sc.L, &n_tr);
-    if (n_tr <= 0 || sc.n_eps <= 0) { set_err("dp_step_n: replay buffer is empty"); return OPRL_ERR_STATE; }
-    sc.n_transitions = n_tr;
-    sc.seed = rseed;
-    sc.gather = 1;
-    // as in oprl_learner_step_n: phase 2 of every update gathers the next update's rows
-    h->next_src = sc;
+    RowStager stg;
+    RC(stg.open("dp_step_n", h, replay, rseed, stream));
     // The gradient exchange inside the tiles of the whole-update launch (peer windows, PrecX2 learners): the data-parallel
     // K-loop IS the single-GPU one — k_ddpg_chain, up to chain_max updates per launch, every tile all-reducing its
     // gradient with the other ranks' before Adam.  No all-reduce launches, no apply launches.
     if (h->p2p_ok && h->p2p_inline && !h->sw.no_dp_inline && h->p2p.tile_bytes > 0) {
       h->dp_inline = true;
-      if (chain_ok(h, B)) {
-        const size_t Bm = (size_t)h->Bmax;
-        float* alt = h->batch_alt;
-        float* set[2][5] = {{h->bs, h->ba, h->br, h->bd, h->bs2},
-                            {alt, alt + Bm * h->S, alt + Bm * (h->S + h->A), alt + Bm * (h->S + h->A + 1), alt + Bm * (h->S + h->A + 2)}};
-        const int rc_chain = chain_loop(h, K, B, set, stream);
-        h->dp_inline = false;
-        return rc_chain;
-      }
+      const bool chain = chain_ok(h, B);
+      const int rc = chain ? chain_loop(h, stg, K, B, stream) : OPRL_OK;
       h->dp_inline = false;
+      if (chain) return rc;
     }
-    h->next_src.s = h->bs; h->next_src.a = h->ba; h->next_src.r = h->br; h->next_src.d = h->bd;
-    h->next_src.s2 = h->bs2;
-    int rc = OPRL_OK;
-    for (int k = 0; k < K && rc == OPRL_OK; ++k) {
-      sc.counter = (unsigned long long)h->update_count;
-      h->next_src.counter = sc.counter + 1;
-      h->prefetch_next = (k + 1 < K) ? 1 : 0;
-      sc.gather = h->staged_ready ? 0 : 1;
-      h->staged_ready = false;
-      rc = oprl_learner_dp_update(h, h->bs, h->ba, h->br, h->bd, h->bs2, B, nullptr, nullptr, stream);
+    // otherwise one set: phase 2 of every update gathers the next update's rows into the set it has read
+    for (int k = 0; k < K; ++k) {
+      RC(dp_update(h, stg.plan(h, k + 1 < K ? StepRows::kPhase2 : StepRows::kNone), B, nullptr, nullptr, stream));
+      stg.done();
     }
-    sc.gather = 0;
-    h->prefetch_next = 0;
-    h->staged_ready = false;
-    return rc;
+    return OPRL_OK;
   }
   for (int k = 0; k < K; ++k) {
     RC(oprl_replay_sample(replay, B, nullptr, rseed, (uint64_t)h->update_count, h->bs, h->ba, h->br,
@@ -263,4 +233,3 @@ extern "C" int oprl_learner_dp_step_n(oprl_learner* h, oprl_replay* replay, int3
   }
   return OPRL_OK;
 }
-

@@ -117,18 +117,9 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
   const int n = (int)g->L.size();
   oprl_learner* h0 = g->L[0];
   if (B < 1 || B > h0->Bmax) { set_err("oprl_group_step_n: bad batch %d", B); return OPRL_ERR_INVALID; }
-  int S = 0, A = 0;
-  replay_dims(replay, &S, &A);
-  if (S != h0->S || A != h0->A) { set_err("replay dims (%d,%d) != group dims (%d,%d)", S, A, h0->S, h0->A); return OPRL_ERR_INVALID; }
   int nstep = 1;
-  double nstep_gamma = 0.0;
-  replay_nstep(replay, &nstep, &nstep_gamma);
-  if (nstep > 1) {     // the members gather their rows inside the group's launches, one step at a time
-    set_err("oprl_group_step_n: the replay samples %d-step returns (oprl_replay_set_nstep); packed learners take one-step replays only", nstep);
-    return OPRL_ERR_STATE;
-  }
+  RC(RowStager::check("oprl_group_step_n", h0, replay, true, K, B, &nstep));
   hipStream_t st = (hipStream_t)stream;
-  RC(oprl_replay_flush(replay, stream));
   // everything that can be refused is checked BEFORE any member's counters move: the members advance together, so
   // being in phase now is being in phase for all K updates
   for (int l = 0; l < n; ++l) {
@@ -139,36 +130,31 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
     }
   }
   // (what is left — an internal inconsistency of the launch tables — rolls the members' counters back to here)
-  struct Snap { unsigned epoch, tp_tag; long long update_count; int oc, oa, oal; bool staged, aul, s0, s1; };
+  struct Snap { unsigned epoch, tp_tag; long long update_count; int oc, oa, oal; bool aul, s0, s1; };
   std::vector<Snap> snap(n);
   auto take = [&]() {
     for (int l = 0; l < n; ++l) {
       const oprl_learner* h = g->L[l];
       snap[l] = Snap{h->epoch, h->tp_tag, (long long)h->update_count, (int)h->opt_step_critic, (int)h->opt_step_actor, (int)h->opt_step_alpha,
-                     h->staged_ready, h->actor_updated_last, h->stale32[0], h->stale32[1]};
+                     h->actor_updated_last, h->stale32[0], h->stale32[1]};
     }
   };
-  auto roll_back = [&]() {
+  auto roll_back = [&](int rc) {
     for (int l = 0; l < n; ++l) {
       oprl_learner* h = g->L[l];
       const Snap& q = snap[l];
       h->epoch = q.epoch; h->tp_tag = q.tp_tag; h->update_count = q.update_count; h->opt_step_critic = q.oc; h->opt_step_actor = q.oa;
-      h->opt_step_alpha = q.oal; h->staged_ready = q.staged; h->actor_updated_last = q.aul; h->stale32[0] = q.s0; h->stale32[1] = q.s1;
+      h->opt_step_alpha = q.oal; h->actor_updated_last = q.aul; h->stale32[0] = q.s0; h->stale32[1] = q.s1;
     }
+    return rc;
   };
+  // every member's rows: the replay's one view under the member's own seed; phase 2 stages into the one set it reads
+  std::vector<RowStager> rows_of(1);
+  RC(rows_of[0].open("oprl_group_step_n", h0, replay, seeds[0], stream));
+  rows_of.resize(n, rows_of[0]);
   for (int l = 0; l < n; ++l) {
-    oprl_learner* h = g->L[l];
-    BatchSrc& sc = h->src;
-    long n_tr = 0;
-    replay_view(replay, &sc.states, &sc.actions, &sc.rewards, &sc.dones, &sc.ends, &sc.n_eps, &sc.L, &n_tr);
-    if (n_tr <= 0 || sc.n_eps <= 0) { set_err("oprl_group_step_n: replay buffer is empty"); return OPRL_ERR_STATE; }
-    sc.n_transitions = n_tr;
-    sc.seed = seeds[l];
-    sc.gather = 1;
-    sc.s = h->bs; sc.a = h->ba; sc.r = h->br; sc.d = h->bd; sc.s2 = h->bs2;
-    h->next_src = sc;
-    h->staged_ready = false;
-    h->last_B = B;
+    rows_of[l].bind(g->L[l], seeds[l]);
+    g->L[l]->last_B = B;
   }
   static_assert(sizeof(DdpgArgs) % 8 == 0 && sizeof(DwKArgsG) % 8 == 0 && sizeof(DwKArgsG2) % 8 == 0, "the blocks of an update lie back to back");
   const size_t dc_bytes = dw_group_block_bytes(g->ni_c), da_bytes = dw_group_block_bytes(kDwGroupItems);
@@ -190,17 +176,19 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
       due[j] = actor_due(g->L[0]);
       for (int l = 0; l < n; ++l) {
         oprl_learner* h = g->L[l];
-        if (actor_due(h) != due[j]) { roll_back(); set_err("oprl_group_step_n: the members' delayed actor steps are out of phase (update counts differ modulo policy_freq)"); return OPRL_ERR_STATE; }
-        h->src.counter = (unsigned long long)h->update_count;
-        h->next_src.counter = h->src.counter + 1;
-        h->src.gather = h->staged_ready ? 0 : 1;
-        h->staged_ready = false;
-        const int prefetch = (k + 1 < K && due[j]) ? 1 : 0;     // (the row of phase 2's launch: actor steps only)
+        if (actor_due(h) != due[j]) { set_err("oprl_group_step_n: the members' delayed actor steps are out of phase (update counts differ modulo policy_freq)"); return roll_back(OPRL_ERR_STATE); }
+        const bool prefetch = k + 1 < K && due[j];              // (the row of phase 2's launch: actor steps only)
+        StepRows& rows = rows_of[l].plan(h, prefetch ? StepRows::kPhase2 : StepRows::kNone);
         h->epoch += 1;
-        if (h->epoch == 0) { h->epoch = 1; HIPC(hipMemsetAsync(h->y_granules, 0, ((size_t)4 * h->Bmax + 256) * sizeof(unsigned long long), st)); }
-        p1[l] = ddpg_args(h, B);
+        if (h->epoch == 0) {      // (the TD-target tag wrapped)
+          h->epoch = 1;
+          const hipError_t e = hipMemsetAsync(h->y_granules, 0, ((size_t)4 * h->Bmax + 256) * sizeof(unsigned long long), st);
+          if (e != hipSuccess) { set_err("oprl_group_step_n: hipMemsetAsync failed: %s", hipGetErrorString(e)); return roll_back(OPRL_ERR_HIP); }
+        }
+        p1[l] = ddpg_args(h, rows, B);
         p1[l].group_span = g->span;
-        RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &p1[l].cluster_tag));
+        int rc = next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &p1[l].cluster_tag);
+        if (rc != OPRL_OK) return roll_back(rc);
         DwKArgs kd;
         // (as the un-merged launches of a solo learner; the step counts move with the blocks, roll_back puts them back)
         DwArgs dw = dw_args(h, true, B, h->opt_step_critic + 1);
@@ -208,11 +196,12 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
         dw_commit(h, true, dw, 1);
         int ta = tiles_a;
         if (due[j]) {
-          p2[l] = ddpg_args(h, B);
+          p2[l] = ddpg_args(h, rows, B);
           p2[l].group_span = g->span;
-          RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &p2[l].cluster_tag));   // (a launch, a tag)
-          p2[l].prefetch_next = prefetch;
-          h->staged_ready = prefetch != 0;
+          rc = next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &p2[l].cluster_tag);   // (a launch, a tag)
+          if (rc != OPRL_OK) return roll_back(rc);
+          p2[l].prefetch_next = prefetch ? 1 : 0;
+          rows.staged = prefetch;
           dw = dw_args(h, false, B, h->opt_step_actor + 1);
           if (alpha_rides(h)) dw.alpha = alpha_job(h, B, h->opt_step_alpha + 1);    // (SAC: the temperature step rides)
           ta = fill_dw_kargs(dw, &kd) < 0 ? -1 : compact_dw_kargs(kd, da + (size_t)l * da_bytes, kDwGroupItems);
@@ -222,12 +211,12 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
         }
         if (l == 0 && j == 0) tiles_c = tc;
         if (tc < 0 || ta < 0 || tc != tiles_c || p1[l].nc != p1[0].nc || p1[l].merged || p1[l].wide || p1[l].whole || p1[l].twin_split) {
-          roll_back();
           set_err("oprl_group_step_n: internal: bad launch arguments");
-          return OPRL_ERR_INVALID;
+          return roll_back(OPRL_ERR_INVALID);
         }
         h->actor_updated_last = due[j];
         h->update_count += 1;
+        rows_of[l].done();
       }
       first[j][0] = p1[0];
       if (due[j]) first[j][1] = p2[0];
@@ -248,7 +237,6 @@ extern "C" int oprl_group_step_n(oprl_group* g, oprl_replay* replay, int32_t K, 
       HIPC(launch_dw_adam_group(da, kDwGroupItems, n, tiles_a, st));
     }
   }
-  for (oprl_learner* h : g->L) { h->src.gather = 0; h->prefetch_next = 0; h->staged_ready = false; }
   return OPRL_OK;
 }
 

@@ -293,6 +293,24 @@ struct FusedForm {
   int chain_max = 1;           // updates per k_ddpg_chain launch at most (1 unless `whole`)
 };
 
+// The rows of one update — or of one chain launch — as the launch builders see them.  It travels down
+// from the entry point as an argument; nothing of it is kept on the learner.
+struct StepRows {
+  enum Stage { kNone, kPhase1, kPhase2 };
+  BatchSrc cur;                // the update's rows: the caller's (gather 0), or the kernels' own gather with its counter
+  BatchSrc next;               // what the staging launch gathers (counter + 1), s .. s2: the set the rows go to
+  Stage stage = kNone;         // which of the update's launches carries the next update's rows
+  int n_upd = 1;               // chain launch: the updates it runs (at most the form's chain_max) ...
+  bool stage_after_last = false;   // ... whether its last update stages the rows of the update after it ...
+  const float* other_set[5] = {};  // ... and the other staging set (cur's s .. s2 are set 0 of the launch)
+  bool staged = false;         // out: a launch that stages the next update's rows has gone out
+};
+inline StepRows plain_rows(const float* s, const float* a, const float* r, const float* d, const float* s2) {
+  StepRows rows{};
+  rows.cur.s = s; rows.cur.a = a; rows.cur.r = r; rows.cur.d = d; rows.cur.s2 = s2;
+  return rows;
+}
+
 }  // namespace oprl_host
 
 using namespace oprl_host;
@@ -366,7 +384,6 @@ struct oprl_learner {
   bool multi_collect = false;  // for_each_net over > 2 single-CU nets: one k_mlp_slice_multi launch
   int multi_n = 0, multi_width = 0;
   MlpArgs multi_args[kMaxMulti];
-  bool staged_ready = false;   // step_n: the staging batch holds the next update's rows (written by phase 2)
   unsigned long long* y_granules = nullptr;   // [Bmax] TD-target hand-off (fused DDPG)
   unsigned epoch = 0;          // monotonically increasing, never reset
   int ncl = 1;                 // CUs per slice cluster in the fused path (csrc/tp3.h)
@@ -402,10 +419,6 @@ struct oprl_learner {
     while (c > 1 && roles * c * slices > n_cus) c >>= 1;
     return c;
   }
-  BatchSrc src;                // where the current update's minibatch comes from
-  BatchSrc next_src;           // step_n: what phase 2 should gather for the next update
-  int prefetch_next = 0;
-  bool prefetch_p1 = false;    // step_n: phase 1 carries the next update's rows (two staging sets), not phase 2
   // key of the in-update noise streams (TD3 smoothing, SAC / TQC reparameterisation draws): the run
   // seed and, in a data-parallel job, the rank — every seed and every rank draws its own eps
   uint64_t noise_seed = 0;
@@ -450,9 +463,6 @@ struct oprl_learner {
   float* gu = nullptr;                         // [kDuLd][Bm][256] the actor's unit-seed dz1 rows (DwGate kind 3)
   float* chain_b16 = nullptr;                  // [4][kMaxLayers][256]
   float* w3buf1 = nullptr;                     // (w3buf[0] = w3_snap)
-  int chain_u = 1;             // step_n: updates the next whole-update launch runs (k_ddpg_chain)
-  bool chain_pf_last = false;  // ... and whether its last update stages the rows of the update after it
-  const float* chain_set1[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // the other staging set (set 0 = the update's rows)
   bool whole_done = false;     // this update's actor phase was part of the critic phase's launch
   float* pack16[OPRL_MAX_CRITICS + 1] = {};
   float* pack16_t[OPRL_MAX_CRITICS + 1] = {};
@@ -472,7 +482,7 @@ hipError_t uc_alloc(void** out, size_t bytes);
 size_t net_ws_floats(const oprl_net& n, int B);
 int fresh32(const oprl_net* net, hipStream_t st);
 FusedForm fused_form(const oprl_learner* h, int B, bool dp_inline);
-DdpgArgs ddpg_args(oprl_learner* h, int B);
+DdpgArgs ddpg_args(oprl_learner* h, const StepRows& rows, int B);
 int chain_rows(const oprl_learner* h, int B);
 void build_repack_items(const oprl_net* const* nets, int n_nets, int which,
                         std::vector<RepackItem>& items, int* blocks_out,
@@ -499,8 +509,31 @@ extern std::mutex g_lazy_mu;
 extern std::vector<oprl_learner*> g_lazy;
 int repack_nets(const oprl_net* const* nets, int n_nets, int which, hipStream_t st,
                 float* const* pk16 = nullptr, float* const* pk16_t = nullptr, int pl = 1);
+// oprl_learner_update_phase / oprl_learner_update on a given plan of rows (the C entry points pass plain_rows)
+int learner_update_phase(oprl_learner* h, int phase, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream);
+int learner_update(oprl_learner* h, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream);
+
+// The row protocol of a K-loop over a replay whose rows the fused kernels gather themselves: the replay's
+// view and the seed, the two staging sets, which of them the coming update reads and whether its rows are already there.
+// open() is the loops' shared set-up; plan() yields the coming update's (chain launch's) StepRows, done() takes its
+// `staged` and moves on.  It lives on the entry point's stack: a refused or failed call leaves nothing behind.
+struct RowStager {
+  StepRows rows;               // the plan under way (built in place, handed out by reference)
+  float* set[2][5];            // {s, a, r, d, s2}: the learner's own batch rows and batch_alt (the own ones again without it)
+  int cur = 0;                 // the set the coming update reads
+  bool staged = false;         // ... which a launch of the previous update has already filled
+  int flip = 0;                // sets done() moves on by: 1 after phase-1 staging, U after a chain launch, else 0
+  // do the replay and K / B fit (dims; K / B; an n-step replay's gamma; packed learners: one-step only)?  *nstep > 1: no in-kernel gather
+  static int check(const char* who, const oprl_learner* h, const oprl_replay* replay, bool packed, int K, int B, int* nstep);
+  int open(const char* who, const oprl_learner* h, oprl_replay* replay, uint64_t seed, void* stream);
+  void bind(const oprl_learner* h, uint64_t seed);     // the seed and staging sets of (another) learner over the opened view
+  // K_left > 0: a chain launch.  (TQC's rider loop takes a kPhase1 plan for the set alternation and the `next` rows only:
+  // its generic launches read plain rows, and it sets `staged` itself from the riders' prefetch_done.)
+  StepRows& plan(const oprl_learner* h, StepRows::Stage stage, int K_left = 0);
+  void done() { staged = rows.staged; cur = (cur + flip) & 1; }
+};
 // step_n's K-loop as launches of several updates each (k_ddpg_chain); also the inline data-parallel loop
-int chain_loop(oprl_learner* h, int K, int B, float* (*set)[5], void* stream);
+int chain_loop(oprl_learner* h, RowStager& stg, int K, int B, void* stream);
 bool chain_ok(oprl_learner* h, int B);
 }  // namespace oprl_host
 using namespace oprl_host;
