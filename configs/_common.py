@@ -12,9 +12,10 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 from oprl.buffers.episodic_buffer import EpisodicReplayBuffer  # noqa: E402
 from oprl.buffers.nstep_buffer import NStepEpisodicReplayBuffer  # noqa: E402
+from oprl.buffers.prioritized_buffer import PrioritizedEpisodicReplayBuffer  # noqa: E402
 from oprl.environment import make_env as build_env  # noqa: E402
 from oprl.logging import make_text_logger_func  # noqa: E402
-from oprl.parse_args import parse_args  # noqa: E402
+from oprl.parse_args import check_per, parse_args  # noqa: E402
 from oprl.runners.config import CommonParameters  # noqa: E402
 from oprl.runners.train import run_training  # noqa: E402
 
@@ -33,6 +34,7 @@ class TrainingScript:
 
     def __post_init__(self) -> None:
         self.args = parse_args()
+        self.per = check_per(self.args)      # --per: prioritized replay and an algorithm that applies its weights
         probe = self.make_env(seed=0)
         self.state_dim = int(probe.observation_space.shape[0])
         self.action_dim = int(probe.action_space.shape[0])
@@ -46,7 +48,8 @@ class TrainingScript:
 
     def make_algo(self, logger):
         return self.algo_cls(logger=logger, state_dim=self.state_dim, action_dim=self.action_dim,
-                             device=self.args.device, precision=self.args.precision).create()
+                             device=self.args.device, precision=self.args.precision,
+                             **({"prioritized": True} if self.per else {})).create()
 
     def make_replay_buffer(self):
         kw = dict(buffer_size_transitions=max(self.config.num_steps, REPLAY_TRANSITIONS), state_dim=self.state_dim,
@@ -54,6 +57,8 @@ class TrainingScript:
         if self.args.n_step > 1:        # n-step returns: the sampler discounts with the ALGORITHM's gamma
             gamma = next(f.default for f in fields(self.algo_cls) if f.name == "gamma")
             return NStepEpisodicReplayBuffer(n_step=self.args.n_step, gamma=gamma, **kw).create()
+        if self.per:
+            return PrioritizedEpisodicReplayBuffer(**kw).create()
         return EpisodicReplayBuffer(**kw).create()
 
     def run(self) -> None:

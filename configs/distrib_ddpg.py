@@ -23,14 +23,16 @@ from oprl.algos.ddpg import DDPG  # noqa: E402
 from oprl.algos.nn_models import DeterministicPolicy  # noqa: E402
 from oprl.buffers.episodic_buffer import EpisodicReplayBuffer  # noqa: E402
 from oprl.buffers.nstep_buffer import NStepEpisodicReplayBuffer  # noqa: E402
+from oprl.buffers.prioritized_buffer import PrioritizedEpisodicReplayBuffer  # noqa: E402
 from oprl.distrib import env_worker, policy_update_worker  # noqa: E402
 from oprl.environment import make_env as build_env  # noqa: E402
 from oprl.logging import FileTxtLogger, get_logs_path  # noqa: E402
-from oprl.parse_args import parse_args_distrib  # noqa: E402
+from oprl.parse_args import check_per, parse_args_distrib  # noqa: E402
 from oprl.runners.config import DistribConfig  # noqa: E402
 from oprl.runners.train_distrib import run_distrib_training  # noqa: E402
 
 cli = parse_args_distrib()
+PER = check_per(cli)      # --per: prioritized replay (with --n-step the D4PG / Ape-X pair; the two do not combine yet)
 HIDDEN = (256, 256)
 REPLAY_TRANSITIONS = 1_000_000
 
@@ -59,7 +61,7 @@ def make_policy():
 def make_algo(logger, **overrides):
     """``overrides``: what a data-parallel rank needs on top (device=cuda:<rank>, export_grads=True)."""
     return DDPG(logger=logger, state_dim=OBS_DIM, action_dim=ACT_DIM,
-                **{"device": cli.device, "precision": cli.precision, **overrides}).create()
+                **{"device": cli.device, "precision": cli.precision, "prioritized": PER, **overrides}).create()
 
 
 def make_replay_buffer(**overrides):
@@ -69,6 +71,8 @@ def make_replay_buffer(**overrides):
     if cli.n_step > 1:      # --n-step N: multi-step returns (the D4PG / Ape-X target), discounted with DDPG's gamma
         gamma = DDPG.__dataclass_fields__["gamma"].default
         return NStepEpisodicReplayBuffer(n_step=cli.n_step, gamma=gamma, **kw).create()
+    if PER:
+        return PrioritizedEpisodicReplayBuffer(**kw).create()
     return EpisodicReplayBuffer(**kw).create()
 
 

@@ -458,6 +458,26 @@ int oprl_replay_prio_read(oprl_replay* h, float* tree_out, int64_t n, int64_t* n
 /* Restore leaves[E·L] (device; the entries of dead slots are taken as 0) and p_max (> 0); the nodes are rebuilt. */
 int oprl_replay_prio_load(oprl_replay* h, const float* leaves, float p_max, void* stream);
 
+/* ---- training from prioritized replay ("Training from it") -----------------------------------------
+ * One reference-semantics update whose critic loss is (1/B) sum_b w[b] (Q(s,a) - y)^2 per critic, w[B] on the device;
+ * the actor and temperature losses are not weighted (Schaul et al.).  td_abs_out[B] (device) receives
+ * (sum_j |Q_j(s,a) - y|) / n_critics.  With w = 1 everywhere the update is oprl_learner_update's on a no_fuse learner,
+ * bit for bit.  The critic step runs the generic launch sequence as forward | k_td_weighted_seed | backward, so:
+ * OPRL_ERR_STATE for a learner whose fused form is on (create it with no_fuse), for export_grads / data-parallel
+ * learners and members of a group; OPRL_ERR_INVALID for TQC (its quantile-Huber seed takes no per-row weight yet) and
+ * for a precision other than OPRL_PREC_F32.  A refused call changes nothing. */
+int oprl_learner_update_weighted(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
+                                 const float* s2, const float* w, int32_t B, const float* noise0, const float* noise1,
+                                 float* td_abs_out, void* stream);
+/* K times, with u the learner's update count before each update: oprl_replay_prio_sample(seed, counter = u,
+ * beta = min(1, beta0 + (1 - beta0) u / beta_steps), formed in double), oprl_learner_update_weighted on those rows
+ * and weights, oprl_replay_prio_update(the rows' slots, its td_abs).  Everything is enqueued on `stream`; the host
+ * waits for nothing.  Refused like update_weighted, and: a replay without a sum tree or an empty one
+ * (OPRL_ERR_STATE), dims that are not the learner's, K < 0, B outside [1, max_batch], beta0 outside [0, 1] or
+ * beta_steps <= 0 (OPRL_ERR_INVALID). */
+int oprl_learner_step_n_prio(oprl_learner* h, oprl_replay* replay, int32_t K, int32_t B, uint64_t seed, double beta0,
+                             double beta_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,8 @@ SIGNATURES = {
     "oprl_replay_prio_update": (C.c_int, [_P, _I32, _P, _P, _P]),
     "oprl_replay_prio_read": (C.c_int, [_P, _P, _I64, C.POINTER(_I64), C.POINTER(C.c_float), _P]),
     "oprl_replay_prio_load": (C.c_int, [_P, _P, _F, _P]),
+    "oprl_learner_update_weighted": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "oprl_learner_step_n_prio": (C.c_int, [_P, _P, _I32, _I32, _U64, _D, _D, _P]),
 }
 
 _lib = None

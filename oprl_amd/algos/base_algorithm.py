@@ -44,9 +44,17 @@ class OffPolicyAlgorithm(ABC):
         ``act_next``: the observation the NEXT environment step starts from (the trainer has it before the update,
         base_trainer.py:38-74).  The actor's forward for it rides behind the update in the same call
         (oprl_learner_step_act) and the next ``actor.explore(act_next)`` — with this very array — only collects the
-        row: one host wait per environment step instead of update-sync, act-launch, act-sync."""
+        row: one host wait per environment step instead of update-sync, act-launch, act-sync.
+
+        A ``prioritized`` algorithm over a prioritized buffer: one ``step_n_prio`` call instead (draw by priority,
+        weighted update, new priorities); ``act_next`` is accepted but rides nowhere, ``explore`` runs its own forward."""
         refuse_prioritized(self, replay_buffer)
         check_nstep_gamma(self, replay_buffer)
+        if trains_prioritized(self, replay_buffer):
+            step = self.update_step
+            step_prioritized(self, replay_buffer, 1, batch_size)
+            self._log_update(step)
+            return
         handle = getattr(replay_buffer, "handle", None)
         if handle is None or self.learner.export_grads:
             self.update(*replay_buffer.sample(batch_size))
@@ -84,11 +92,38 @@ class OffPolicyAlgorithm(ABC):
 
 
 def refuse_prioritized(algo, replay_buffer) -> None:
-    """No learner applies importance weights yet: a prioritized buffer (buffers/prioritized_buffer.py) is refused
-    rather than sampled without them."""
+    """A prioritized buffer (buffers/prioritized_buffer.py) trains only an algorithm created with ``prioritized=True``
+    (DDPG, TD3, SAC, REDQ), whose critic loss applies the importance weights; any other algorithm refuses it rather
+    than sample it without them."""
     if getattr(replay_buffer, "prioritized", False) and not getattr(algo, "prioritized", False):
         raise ValueError(f"{type(algo).__name__} does not apply importance weights: it cannot train from a prioritized "
-                         "replay buffer (use EpisodicReplayBuffer)")
+                         "replay buffer (use EpisodicReplayBuffer, or create the algorithm with prioritized=True)")
+
+
+def check_prioritized_config(algo) -> None:
+    """``prioritized=True`` runs the exact-fp32 generic launch sequence on one GPU: called by
+    ``create()`` before anything touches the GPU."""
+    if not getattr(algo, "prioritized", False):
+        return
+    if algo.precision != "f32":
+        raise ValueError(f"{type(algo).__name__}(prioritized=True) needs precision='f32', not {algo.precision!r}")
+    if algo.export_grads:
+        raise ValueError(f"{type(algo).__name__}(prioritized=True) does not export gradients (no data-parallel "
+                         "prioritized training)")
+
+
+def trains_prioritized(algo, replay_buffer) -> bool:
+    """A prioritized algorithm over a prioritized buffer with its tree on the device: the weighted path.  (A prioritized
+    algorithm over a plain buffer trains uniformly through the plain path.)"""
+    return (getattr(algo, "prioritized", False) and getattr(replay_buffer, "prioritized", False)
+            and getattr(replay_buffer, "handle", None) is not None)
+
+
+def step_prioritized(algo, replay_buffer, K: int, batch_size: int) -> None:
+    """K times: draw by priority at counter u = the update count, one weighted update, new priorities from its |TD| —
+    one C call (oprl_learner_step_n_prio), nothing waited for."""
+    algo.learner.step_n_prio(replay_buffer.handle, int(K), int(batch_size), seed=int(replay_buffer.seed),
+                             beta0=float(replay_buffer.beta0), beta_steps=float(replay_buffer.beta_steps))
 
 
 def check_nstep_gamma(algo, replay_buffer) -> None:
@@ -327,6 +362,23 @@ class HipLearner:
                 self.handle, _capi.ptr(s), _capi.ptr(a), _capi.ptr(r), _capi.ptr(d), _capi.ptr(s2), B,
                 _capi.ptr(n0), _capi.ptr(n1), _capi.current_stream()), "oprl_learner_update")
 
+    def update_weighted(self, state, action, reward, done, next_state, weights, noise0=None, noise1=None) -> t.Tensor:
+        """One update whose critic loss carries the importance weights ``weights`` ([B] or [B, 1]); returns the rows'
+        |TD| (mean over the critics) as a device tensor [B] (oprl_learner_update_weighted)."""
+        self.check_bound()
+        B, s, a, r, d, s2 = self._prep(state, action, reward, done, next_state)
+        w = t.as_tensor(weights).to(device=self.device, dtype=t.float32).reshape(-1).contiguous()
+        if w.numel() != B:
+            raise ValueError(f"{w.numel()} weights for a batch of {B}")
+        n0 = None if noise0 is None else noise0.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        n1 = None if noise1 is None else noise1.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        td = t.empty(B, dtype=t.float32, device=self.device)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_update_weighted(
+                self.handle, _capi.ptr(s), _capi.ptr(a), _capi.ptr(r), _capi.ptr(d), _capi.ptr(s2), _capi.ptr(w), B,
+                _capi.ptr(n0), _capi.ptr(n1), _capi.ptr(td), _capi.current_stream()), "oprl_learner_update_weighted")
+        return td
+
     def update_phase(self, phase, state, action, reward, done, next_state, noise0=None, noise1=None):
         self.check_bound()
         B, s, a, r, d, s2 = self._prep(state, action, reward, done, next_state)
@@ -347,6 +399,15 @@ class HipLearner:
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_step_n(self.handle, replay_handle, K, B, seed,
                                                      _capi.current_stream()), "oprl_learner_step_n")
+
+    def step_n_prio(self, replay_handle, K: int, B: int, seed: int, beta0: float, beta_steps: float) -> None:
+        """K prioritized sample + weighted update + priority update rounds over a replay with a sum tree
+        (oprl_learner_step_n_prio)."""
+        self.check_bound()
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_step_n_prio(self.handle, replay_handle, K, B, seed, float(beta0),
+                                                          float(beta_steps), _capi.current_stream()),
+                        "oprl_learner_step_n_prio")
 
     def step_act(self, replay_handle, B: int, seed: int, obs) -> None:
         """One sample()+update() and, enqueued behind it, the actor's forward of ``obs`` with the updated weights

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import torch as t
 from torch import nn
 
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, require_gpu
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_prioritized_config, require_gpu
 from oprl_amd.algos.nn_functions import disable_gradient
 from oprl_amd.algos.nn_models import Critic, DeterministicPolicy, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
@@ -35,6 +35,7 @@ class DDPG(OffPolicyAlgorithm):
     max_batch: int = 4096          # rows the HIP workspace is sized for
     export_grads: bool = False     # data-parallel learner: reduce grads between phases
     no_fuse: bool = False          # force the generic per-net launch sequence (tests / A-B)
+    prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # "f32": exact-fp32 MFMA (parity mode, no input range); "x2": fp32 as fp16 hi + lo (parity mode, |obs| < 4094: leaving the range raises); "bf16": bf16 MFMA inputs, fp32 accumulate / master / Adam (include/oprl_amd.h)
 
     actor: PolicyProtocol = field(init=False)
@@ -45,6 +46,7 @@ class DDPG(OffPolicyAlgorithm):
     _created: bool = False
 
     def create(self) -> "DDPG":
+        check_prioritized_config(self)
         dev = require_gpu(self.device)
 
         def policy():
@@ -77,7 +79,7 @@ class DDPG(OffPolicyAlgorithm):
             actor_target_group=self.actor_target,
             critic_group=self.critic, critic_mlps=[self.critic.q1],
             critic_target_group=self.critic_target, critic_target_mlps=[self.critic_target.q1],
-            hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, no_fuse=self.no_fuse, precision=self.precision)
+            hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
         self._created = True
         return self
 
@@ -92,5 +94,11 @@ class DDPG(OffPolicyAlgorithm):
         reward: t.Tensor,
         done: t.Tensor,
         next_state: t.Tensor,
+        weights: t.Tensor | None = None,
     ) -> None:
+        """``weights``: importance weights [B] or [B, 1] of a prioritized batch; the rows' |TD| is left in
+        ``last_td_abs`` (device tensor)."""
+        if weights is not None:
+            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights)
+            return
         self.learner.update(state, action, reward, done, next_state)

@@ -20,7 +20,8 @@ import torch as t
 from torch import nn
 
 from oprl_amd import _capi
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_nstep_gamma, refuse_prioritized, require_gpu
+from oprl_amd.algos.base_algorithm import (HipLearner, OffPolicyAlgorithm, check_nstep_gamma, check_prioritized_config,
+                                            refuse_prioritized, require_gpu, step_prioritized, trains_prioritized)
 from oprl_amd.algos.nn_functions import disable_gradient
 from oprl_amd.algos.nn_models import MLP, GaussianActor, _forward_sa, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
@@ -64,6 +65,7 @@ class REDQ(OffPolicyAlgorithm):
     max_batch: int = 4096
     export_grads: bool = False    # refused by the learner (no data-parallel REDQ)
     no_fuse: bool = False         # (REDQ has no fused form: no effect)
+    prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # f32 only: the learner refuses the others
 
     actor: PolicyProtocol = field(init=False)
@@ -73,6 +75,7 @@ class REDQ(OffPolicyAlgorithm):
     _created: bool = False
 
     def create(self) -> "REDQ":
+        check_prioritized_config(self)
         dev = require_gpu(self.device)
         if not 1 <= self.n_critics <= _capi.OPRL_MAX_CRITICS:
             raise ValueError(f"REDQ: n_critics={self.n_critics} outside [1, {_capi.OPRL_MAX_CRITICS}]")
@@ -104,7 +107,7 @@ class REDQ(OffPolicyAlgorithm):
             critic_group=self.critic, critic_mlps=self.critic.nets,
             critic_target_group=self.critic_target, critic_target_mlps=self.critic_target.nets,
             hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, log_alpha=self.log_alpha,
-            no_fuse=self.no_fuse, precision=self.precision)
+            no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
         self._created = True
         return self
 
@@ -127,12 +130,18 @@ class REDQ(OffPolicyAlgorithm):
         next_state: t.Tensor,
         *,
         noise: tuple[t.Tensor, t.Tensor] | None = None,
+        weights: t.Tensor | None = None,
     ) -> None:
         """ONE update (a critic step; an actor step too when it completes a group of ``utd_ratio``).  ``noise``:
-        optional (eps_next [B,A], eps_current [B,A]) standing in for the device draws of streams 1 and 2."""
+        optional (eps_next [B,A], eps_current [B,A]) standing in for the device draws of streams 1 and 2.
+        ``weights``: importance weights [B] or [B, 1] of a prioritized batch (critic loss only); the rows' |TD|, the
+        mean over the ensemble, is left in ``last_td_abs`` (device tensor)."""
         n0, n1 = noise if noise is not None else (None, None)
         step = self.update_step
-        self.learner.update(state, action, reward, done, next_state, noise0=n0, noise1=n1)
+        if weights is not None:
+            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights, noise0=n0, noise1=n1)
+        else:
+            self.learner.update(state, action, reward, done, next_state, noise0=n0, noise1=n1)
         self._log_update(step)
 
     def update_from_buffer(self, replay_buffer, batch_size: int, act_next=None) -> None:
@@ -141,8 +150,16 @@ class REDQ(OffPolicyAlgorithm):
         same updates bit for bit)."""
         refuse_prioritized(self, replay_buffer)
         check_nstep_gamma(self, replay_buffer)
-        handle = getattr(replay_buffer, "handle", None)
         K = int(self.utd_ratio)
+        if trains_prioritized(self, replay_buffer):      # (one step_n_prio call; act_next rides nowhere)
+            step = self.update_step
+            step_prioritized(self, replay_buffer, K, batch_size)
+            for u in range(step, step + K):
+                if u % self.log_every == 0:
+                    self._log_update(u)
+                    break
+            return
+        handle = getattr(replay_buffer, "handle", None)
         if handle is None:
             for _ in range(K):
                 self.update(*replay_buffer.sample(batch_size))

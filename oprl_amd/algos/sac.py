@@ -10,7 +10,7 @@ from dataclasses import dataclass, field
 import torch as t
 from torch import nn
 
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, require_gpu
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_prioritized_config, require_gpu
 from oprl_amd.algos.nn_functions import disable_gradient
 from oprl_amd.algos.nn_models import DoubleCritic, GaussianActor, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
@@ -35,6 +35,7 @@ class SAC(OffPolicyAlgorithm):
     max_batch: int = 4096
     export_grads: bool = False
     no_fuse: bool = False     # True: the generic per-net launch sequence instead of the fused kernels
+    prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # "f32": exact-fp32 MFMA (parity mode); "bf16": bf16 MFMA inputs, fp32 accumulate / master / Adam (include/oprl_amd.h)
 
     actor: PolicyProtocol = field(init=False)
@@ -44,6 +45,7 @@ class SAC(OffPolicyAlgorithm):
     _created: bool = False
 
     def create(self) -> "SAC":
+        check_prioritized_config(self)
         dev = require_gpu(self.device)
         self.actor = GaussianActor(self.state_dim, self.action_dim, (256, 256),
                                    nn.ReLU(inplace=True), device=self.device).to(dev)
@@ -74,7 +76,7 @@ class SAC(OffPolicyAlgorithm):
             critic_target_group=self.critic_target,
             critic_target_mlps=[self.critic_target.q1, self.critic_target.q2],
             hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, log_alpha=self.log_alpha,
-            no_fuse=self.no_fuse, precision=self.precision)
+            no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
         self._created = True
         return self
 
@@ -97,12 +99,18 @@ class SAC(OffPolicyAlgorithm):
         next_state: t.Tensor,
         *,
         noise: tuple[t.Tensor, t.Tensor] | None = None,
+        weights: t.Tensor | None = None,
     ) -> None:
         """``noise``: optional (eps_next [B,A], eps_current [B,A]) standing in for
-        the two ``Normal(0,1).sample()`` draws (nn_models.py:213); None = Philox."""
+        the two ``Normal(0,1).sample()`` draws (nn_models.py:213); None = Philox.
+        ``weights``: importance weights [B] or [B, 1] of a prioritized batch (critic loss only); the rows' |TD| is
+        left in ``last_td_abs`` (device tensor)."""
         n0, n1 = noise if noise is not None else (None, None)
         step = self.update_step
-        self.learner.update(state, action, reward, done, next_state, noise0=n0, noise1=n1)
+        if weights is not None:
+            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights, noise0=n0, noise1=n1)
+        else:
+            self.learner.update(state, action, reward, done, next_state, noise0=n0, noise1=n1)
         self._log_update(step)
 
     def _log_update(self, step: int) -> None:

@@ -9,7 +9,7 @@ from dataclasses import dataclass, field
 import torch as t
 from torch import nn
 
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, require_gpu
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_prioritized_config, require_gpu
 from oprl_amd.algos.nn_functions import disable_gradient
 from oprl_amd.algos.nn_models import DeterministicPolicy, DoubleCritic, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
@@ -36,6 +36,7 @@ class TD3(OffPolicyAlgorithm):
     max_batch: int = 4096
     export_grads: bool = False
     no_fuse: bool = False     # True: the generic per-net launch sequence instead of the fused kernels
+    prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # "f32": exact-fp32 MFMA (parity mode); "bf16": bf16 MFMA inputs, fp32 accumulate / master / Adam (include/oprl_amd.h)
 
     actor: PolicyProtocol = field(init=False)
@@ -46,6 +47,7 @@ class TD3(OffPolicyAlgorithm):
     _created: bool = False
 
     def create(self) -> "TD3":
+        check_prioritized_config(self)
         dev = require_gpu(self.device)
 
         def policy():
@@ -82,7 +84,7 @@ class TD3(OffPolicyAlgorithm):
             critic_group=self.critic, critic_mlps=[self.critic.q1, self.critic.q2],
             critic_target_group=self.critic_target,
             critic_target_mlps=[self.critic_target.q1, self.critic_target.q2],
-            hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, no_fuse=self.no_fuse, precision=self.precision)
+            hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
         self._created = True
         return self
 
@@ -99,11 +101,17 @@ class TD3(OffPolicyAlgorithm):
         next_state: t.Tensor,
         *,
         noise: t.Tensor | None = None,
+        weights: t.Tensor | None = None,
     ) -> None:
         """``noise``: optional injected N(0,1) draw [B, A] standing in for
-        ``randn_like(action)`` (td3.py:98); None draws it on device (Philox)."""
+        ``randn_like(action)`` (td3.py:98); None draws it on device (Philox).
+        ``weights``: importance weights [B] or [B, 1] of a prioritized batch; the rows' |TD| is left in
+        ``last_td_abs`` (device tensor)."""
         step = self.update_step
-        self.learner.update(state, action, reward, done, next_state, noise0=noise)
+        if weights is not None:
+            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights, noise0=noise)
+        else:
+            self.learner.update(state, action, reward, done, next_state, noise0=noise)
         self._log_update(step)
 
     def _log_update(self, step: int) -> None:

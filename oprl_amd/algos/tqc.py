@@ -68,6 +68,7 @@ class TQC(OffPolicyAlgorithm):
     max_batch: int = 4096
     export_grads: bool = False
     precision: str = "f32"         # "f32": exact-fp32 MFMA (parity mode); "bf16": bf16 MFMA inputs, fp32 accumulate / master / Adam
+    prioritized: bool = False      # refused: the quantile-Huber seed takes no per-row weight yet
 
     actor: PolicyProtocol = field(init=False)
     critic: QuantileQritic = field(init=False)
@@ -76,6 +77,11 @@ class TQC(OffPolicyAlgorithm):
     quantiles_total: int = field(init=False)
     learner: HipLearner = field(init=False, repr=False)
     _created: bool = False
+
+    def __post_init__(self) -> None:
+        if self.prioritized:
+            raise ValueError("TQC(prioritized=True): TQC does not train from prioritized replay yet — its quantile-Huber "
+                             "critic loss needs a weighted seed of its own (a follow-up); DDPG, TD3, SAC and REDQ do")
 
     def create(self) -> "TQC":
         dev = require_gpu(self.device)

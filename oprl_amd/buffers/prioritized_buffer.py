@@ -6,8 +6,11 @@ descent and updated from |TD errors| on the device, with no host round trip.  ``
 ``ReplayBufferProtocol`` and keeps the batch's slots (``e·L + t``, int32) and importance weights in ``last_slots`` /
 ``last_weights`` (device tensors); ``update_priorities(slots, td_abs)`` writes new priorities.
 
-No learner applies importance weights yet: the algorithms' ``update_from_buffer`` and the trainer refuse a
-prioritized buffer instead of sampling it without them."""
+DDPG, TD3, SAC and REDQ created with ``prioritized=True`` train from it: their ``update(..., weights=last_weights)``
+applies the importance weights in the critic loss and leaves |TD| in ``last_td_abs`` for ``update_priorities``;
+``update_from_buffer`` does the three steps in one C call (``oprl_learner_step_n_prio``, counter = the learner's update
+count, ``beta(u)`` from this buffer's ``beta0`` / ``beta_steps``).  Any other algorithm (TQC included) and the trainer
+refuse a prioritized buffer instead of sampling it without the weights."""
 from __future__ import annotations
 
 import ctypes as C

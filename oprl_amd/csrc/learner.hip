@@ -7,6 +7,7 @@
 //   DDPG  algos/ddpg.py:61-107      TD3  algos/td3.py:71-146
 //   SAC   algos/sac.py:75-155       TQC  algos/tqc.py:116-189
 #include "learner_internal.h"
+#include "per_seed.h"
 #include "philox.h"
 
 namespace oprl {
@@ -1094,9 +1095,65 @@ int whole_update(oprl_learner* h, StepRows& rows, DdpgArgs& fa, const FusedForm&
   return OPRL_OK;
 }
 
+// Step 3 of the generic critic phase under importance weights (rows.w; oprl_learner_update_weighted): the
+// launch that is forward + seed + backward there, as three — the critics' forward with the activations stored and q into
+// qpi (idle until the actor phase), k_td_weighted_seed (per_seed.hip) on those q and the target operands SEED_MSE_TD takes,
+// the critics' backward from the stored activations with the seed read from memory (SEED_PTR).  The same for_each_net
+// groupings and the same stores, so step 4's dW + Adam reads what it always reads.
+int weighted_critic_step(oprl_learner* h, const StepRows& rows, int B, int n_min, hipStream_t st) {
+  const oprl_learner_config& c = h->cfg;
+  const int S = h->S, A = h->A, nc = h->nc, algo = c.algo;
+  const bool redq = algo == OPRL_REDQ;
+  if (h->per_seed == nullptr || rows.td_abs == nullptr) { set_err("internal: weighted critic step without its buffers"); return OPRL_ERR_STATE; }
+  RC(for_each_net(h, nc, st, [&](int j, hipStream_t sj) {
+    MlpArgs f = base_args(h, c.critics[j], false, B);
+    f.do_fwd = 1;
+    f.x0 = rows.cur.s; f.k0 = S; f.x1 = rows.cur.a; f.k1 = A;
+    with_store(f, h->ws_critic[j], true, true);
+    f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
+    return launch(f, h->w_critic, sj);
+  }));
+  TdSeedArgs t;
+  memset((void*)&t, 0, sizeof t);
+  SeedArgs& sd = t.s;                       // (as critic_phase fills SEED_MSE_TD's)
+  sd.p0 = h->qn;
+  sd.p1 = nc > 1 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
+  if (redq) {
+    sd.p0 = n_min > 2 ? h->target : h->qn;
+    sd.p1 = n_min == 2 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
+  }
+  sd.p2 = (algo == OPRL_SAC || redq) ? h->logp2 : nullptr;
+  sd.log_alpha = alpha_ptr(h); sd.alpha_const = (float)c.hp.alpha_init;
+  sd.r = rows.cur.r; sd.d = rows.cur.d; sd.gamma = (float)c.hp.gamma;
+  sd.cval = 1.0f / (float)B;
+  sd.y_out = h->ydbg; sd.q_out = h->qdbg;
+  t.q = h->qpi; t.q_stride = h->Bmax;
+  t.w = rows.w;
+  t.seed = h->per_seed; t.seed_stride = h->Bmax;
+  t.td_abs = rows.td_abs;
+  t.partials = h->part_c;
+  t.nc = nc; t.B = B; t.n_slices = (B + kR - 1) / kR;
+  prof_begin(0, st);
+  hipError_t e = launch_td_weighted_seed(t, st);
+  prof_end(st);
+  HIPC(e);
+  return for_each_net(h, nc, st, [&](int j, hipStream_t sj) {
+    MlpArgs f = base_args(h, c.critics[j], false, B);
+    f.do_bwd = 1;
+    with_store(f, h->ws_critic[j], true, true);
+    f.seed_mode = SEED_PTR;
+    f.seed.p0 = h->per_seed + (size_t)j * h->Bmax; f.seed.ld0 = 1;
+    return launch(f, h->w_critic, sj);
+  });
+}
+
 int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
   const float *s = rows.cur.s, *a = rows.cur.a, *r = rows.cur.r, *d = rows.cur.d, *s2 = rows.cur.s2;
+  if (rows.w != nullptr && (use_fused(h, B) || c.algo == OPRL_TQC)) {      // (the entry point refuses both)
+    set_err("internal: importance weights reached a launch form that does not apply them");
+    return OPRL_ERR_STATE;
+  }
   if (use_fused(h, B)) {
     h->epoch += 1;
     if (h->epoch == 0 || h->epoch > 0xFFFFFFFFu - (unsigned)kChainMax) {   // the TD-target tag wrapped (or would inside a chain launch): retire every stale granule
@@ -1242,6 +1299,10 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
   // heads (k_lw_head: 80 workgroups on 256 CUs), with the noise and the counter actor_phase would give it
   h->rider_pending = false;
   h->rider_done = false;
+  if (rows.w != nullptr) {         // importance weights: the same step as three launches per grouping, then step 4
+    RC(weighted_critic_step(h, rows, B, n_min, st));
+    return dw_step(h, true, B, st);
+  }
   if (algo == OPRL_TQC && !h->sw.no_af_ride && !c.export_grads && actor_due(h)) {
     MlpArgs f = actor_forward_args(h, s, B, h->noise1_pending);
     if (f.tp_xbuf != nullptr) {

@@ -304,6 +304,10 @@ struct StepRows {
   bool stage_after_last = false;   // ... whether its last update stages the rows of the update after it ...
   const float* other_set[5] = {};  // ... and the other staging set (cur's s .. s2 are set 0 of the launch)
   bool staged = false;         // out: a launch that stages the next update's rows has gone out
+  // training from prioritized replay (oprl_learner_update_weighted): the rows' importance weights [B] and where their
+  // |TD| goes [B]; null: the plain update.  Generic launch sequence only (critic_phase).
+  const float* w = nullptr;
+  float* td_abs = nullptr;
 };
 inline StepRows plain_rows(const float* s, const float* a, const float* r, const float* d, const float* s2) {
   StepRows rows{};
@@ -361,6 +365,10 @@ struct oprl_learner {
   DwXchg dw_xchg;
   PrefetchJob prefetch;        // step_n on the generic path (TQC): the next update's rows as riders of this update's k_lw_dact launch
   bool prefetch_pending = false, prefetch_done = false;
+  // training from prioritized replay (learner_per.hip): one allocation of its own, made by the first weighted update —
+  // the weighted seeds [nc][Bmax], and step_n_prio's weights, |TD| and slots [Bmax] each; null on every other learner
+  float *per_seed = nullptr, *per_w = nullptr, *per_td = nullptr;
+  int* per_slots = nullptr;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)

@@ -14,6 +14,7 @@ import numpy as np
 import torch as t
 import torch.nn as nn
 
+from oprl_amd.algos.base_algorithm import refuse_prioritized, trains_prioritized
 from oprl_amd.algos.protocols import AlgorithmProtocol
 from oprl_amd.buffers.protocols import ReplayBufferProtocol
 from oprl_amd.distrib.queue import Queue, QueueHub
@@ -49,6 +50,11 @@ class EpochLearner:
 
     def train(self, i_epoch: int) -> None:
         n_updates = self.config.episode_length * self.config.num_env_workers
+        refuse_prioritized(self.algo, self.buffer)
+        if trains_prioritized(self.algo, self.buffer):      # draw by priority, weighted update, new priorities: one C call
+            self.algo.learner.step_n_prio(self.buffer.handle, n_updates, self.config.batch_size, seed=i_epoch,
+                                          beta0=self.buffer.beta0, beta_steps=self.buffer.beta_steps)
+            return
         fused = getattr(getattr(self.algo, "learner", None), "step_n", None)
         if fused is not None and hasattr(self.buffer, "handle"):
             fused(self.buffer.handle, n_updates, self.config.batch_size, seed=i_epoch)

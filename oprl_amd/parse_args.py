@@ -35,7 +35,22 @@ def _parser(title: str, extra) -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description=title)
     for flag, kind, default, text in (*_SHARED, *extra):
         parser.add_argument(flag, type=kind, default=default, help=text)
+    # extension: prioritized experience replay (buffers/prioritized_buffer.py)
+    parser.add_argument("--per", action="store_true",
+                        help="prioritized replay: sample by |TD| priority from the sum tree in HBM, importance-weighted "
+                             "critic loss (DDPG, TD3, SAC, REDQ; f32, one learner; not with --n-step > 1)")
     return parser
+
+
+def check_per(args: argparse.Namespace) -> bool:
+    """Is ``--per`` given?  Raises ValueError when it comes with ``--n-step > 1``: the replay refuses a sum tree over
+    n-step rows, and the scripts say so before anything is built."""
+    if not getattr(args, "per", False):
+        return False
+    if getattr(args, "n_step", 1) > 1:
+        raise ValueError(f"--per with --n-step {args.n_step}: n-step TD errors as priorities are not supported "
+                         "(the replay refuses a sum tree over n-step rows); give one of the two")
+    return True
 
 
 def parse_args() -> argparse.Namespace:

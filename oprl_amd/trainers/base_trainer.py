@@ -12,7 +12,7 @@ from typing import Callable
 import numpy as np
 import torch as t
 
-from oprl_amd.algos.base_algorithm import check_nstep_gamma, refuse_prioritized
+from oprl_amd.algos.base_algorithm import check_nstep_gamma, refuse_prioritized, trains_prioritized
 from oprl_amd.algos.protocols import AlgorithmProtocol
 from oprl_amd.buffers.protocols import ReplayBufferProtocol
 from oprl_amd.environment.protocols import EnvProtocol
@@ -90,9 +90,14 @@ class BaseTrainer(TrainerProtocol):
             wanted = step % self.eval_interval == 0 or step % self.stdout_log_every == 0
             return self.replay_buffer.sample(self.batch_size)[2] if wanted else None
         # (an algorithm with an update-to-data ratio, REDQ: that many sample + update pairs per environment step)
+        per = trains_prioritized(self.algo, self.replay_buffer)
         for _ in range(int(getattr(self.algo, "utd_ratio", 1))):
             batch = self.replay_buffer.sample(self.batch_size)
-            self.algo.update(*batch)
+            if per:      # the batch's importance weights into the critic loss, its |TD| back as priorities
+                self.algo.update(*batch, weights=self.replay_buffer.last_weights)
+                self.replay_buffer.update_priorities(self.replay_buffer.last_slots, self.algo.last_td_abs)
+            else:
+                self.algo.update(*batch)
         return batch[2]
 
     def _quiet(self, step: int) -> bool:
