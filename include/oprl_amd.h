@@ -191,6 +191,25 @@ int oprl_learner_step_act(oprl_learner* h, oprl_replay* replay, int32_t B, uint6
                           const float* obs_host, void* stream);
 int oprl_learner_act_wait(oprl_learner* h, float* out_host, int32_t n_out, int64_t timeout_us);
 
+/* ---- acting for many environments per launch ----------------------------------------------------
+ * The actor's forward of n_rows (1 .. OPRL_ACT_ROWS_MAX) observations in ONE launch (csrc/policy_act_rows.hip: a
+ * workgroup per 16 rows, exact-fp32 MFMA over the row-major MASTER weights — no packs are read, so the rows are the
+ * fp32 evaluation of the masters in every precision mode).  Observations are read from, and the raw last-layer rows
+ * written to, host-mapped pinned memory the learner allocates on the first such call; a row's bits do not depend on
+ * n_rows, its position or its neighbours.  The pending rows have their own area and ticket: a row of
+ * oprl_learner_step_act may be pending at the same time; one pending row batch per learner.  OPRL_ERR_INVALID: null
+ * arguments, n_rows outside 1 .. OPRL_ACT_ROWS_MAX, dims that are not the actor's, a bad K or B; OPRL_ERR_STATE:
+ * act_rows_wait with nothing pending or another n_rows than the pending one, a pending device error (as step_n).  A
+ * refused call changes nothing. */
+#define OPRL_ACT_ROWS_MAX 256
+/* enqueue the actor's forward of n_rows observations obs_host[n_rows][state_dim] with the weights as `stream` leaves them; nothing is waited for */
+int oprl_learner_act_rows(oprl_learner* h, const float* obs_host, int32_t n_rows, void* stream);
+/* oprl_learner_step_n(K) and, behind it in the same call, oprl_learner_act_rows */
+int oprl_learner_step_act_rows(oprl_learner* h, oprl_replay* replay, int32_t K, int32_t B, uint64_t seed,
+                               const float* obs_host, int32_t n_rows, void* stream);
+/* collect the raw last-layer rows out_host[n_rows][n_out]; bounded spin on the tickets (OPRL_ERR_STATE after timeout_us) */
+int oprl_learner_act_rows_wait(oprl_learner* h, float* out_host, int32_t n_rows, int32_t n_out, int64_t timeout_us);
+
 /* ---- packed learners: the reference's --seeds fan-out (runners/train.py:24-50) on ONE GPU ----------------
  * A group steps N independent fused DDPG, TD3 or SAC learners of one algorithm, shape and precision (own weights, own sampler keys
  * seeds[i], one shared HBM replay) with FOUR launches per update for all of them (grid.z = learner; the
@@ -304,6 +323,11 @@ int oprl_mlp_forward(const oprl_net* net, int32_t use_target, const float* x0, i
  * Gaussian mean).  Synchronous on `stream`. */
 int oprl_mlp_act(const oprl_net* net, const float* obs_host, int32_t k0, int32_t out_act,
                  float* out_host, int32_t n_out, void* stream);
+/* oprl_mlp_act for n_rows (1 .. OPRL_ACT_ROWS_MAX) observations at once, stand-alone and synchronous: any net of up to
+ * OPRL_MAX_LAYERS layers and widths <= 512 (a policy without a learner; theta alone is read), obs_host[n_rows][k0] ->
+ * the raw last-layer rows out_host[n_rows][n_out], through library-owned pinned staging. */
+int oprl_mlp_act_rows(const oprl_net* net, const float* obs_host, int32_t n_rows, int32_t k0,
+                      float* out_host, int32_t n_out, void* stream);
 /* Gradient of sum(out * dout) wrt every parameter (into net->grad) and, if
  * dx != NULL, wrt the concatenated input [B,dims[0]].  Test/debug entry that
  * exercises the same backward + dW kernels update() uses. */

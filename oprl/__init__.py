@@ -12,7 +12,7 @@ _SUBMODULES = [
     "buffers", "buffers.protocols", "buffers.episodic_buffer", "buffers.prioritized_buffer", "buffers.nstep_buffer",
     "environment", "environment.protocols", "environment.make_env",
     "runners", "runners.config", "runners.train", "runners.train_distrib",
-    "trainers", "trainers.protocols", "trainers.base_trainer",
+    "trainers", "trainers.protocols", "trainers.base_trainer", "trainers.vec_trainer",
     "distrib", "distrib.queue", "distrib.env_worker", "distrib.policy_update_worker",
 ]
 for _name in _SUBMODULES:

@@ -13,6 +13,7 @@ from pathlib import Path
 OPRL_ABI_VERSION = 4
 OPRL_MAX_LAYERS = 4
 OPRL_MAX_CRITICS = 10
+OPRL_ACT_ROWS_MAX = 256      # rows of one oprl_learner_act_rows / oprl_mlp_act_rows launch
 ALGO = {"ddpg": 0, "td3": 1, "sac": 2, "tqc": 3, "redq": 4}
 PRECISION = {"f32": 0, "bf16": 1, "x2": 2}
 ACT_NONE, ACT_TANH, ACT_GAUSS_MEAN = 0, 1, 4
@@ -82,6 +83,9 @@ SIGNATURES = {
     "oprl_learner_step_n": (C.c_int, [_P, _P, _I32, _I32, _U64, _P]),
     "oprl_learner_step_act": (C.c_int, [_P, _P, _I32, _U64, _P, _P]),
     "oprl_learner_act_wait": (C.c_int, [_P, _P, _I32, C.c_int64]),
+    "oprl_learner_act_rows": (C.c_int, [_P, _P, _I32, _P]),
+    "oprl_learner_step_act_rows": (C.c_int, [_P, _P, _I32, _I32, _U64, _P, _I32, _P]),
+    "oprl_learner_act_rows_wait": (C.c_int, [_P, _P, _I32, _I32, C.c_int64]),
     "oprl_group_create": (C.c_int, [C.POINTER(_P), _I32, C.POINTER(_P)]),
     "oprl_group_destroy": (C.c_int, [_P]),
     "oprl_group_step_n": (C.c_int, [_P, _P, _I32, _I32, C.POINTER(_U64), _P]),
@@ -103,6 +107,7 @@ SIGNATURES = {
     "oprl_learner_sync_params": (C.c_int, [_P, _P]),
     "oprl_mlp_forward": (C.c_int, [C.POINTER(OprlNet), _I32, _P, _I32, _P, _I32, _I32, _I32, _P, _P]),
     "oprl_mlp_act": (C.c_int, [C.POINTER(OprlNet), _P, _I32, _I32, _P, _I32, _P]),
+    "oprl_mlp_act_rows": (C.c_int, [C.POINTER(OprlNet), _P, _I32, _I32, _P, _I32, _P]),
     "oprl_mlp_backward": (C.c_int, [C.POINTER(OprlNet), _P, _I32, _P, _I32, _I32, _P, _P, _P]),
     "oprl_adam_step": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _D, _D, _D, _D, _D, _P]),
     "oprl_polyak": (C.c_int, [_P, _P, _I64, _D, _P]),

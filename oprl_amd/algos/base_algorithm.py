@@ -34,7 +34,7 @@ class OffPolicyAlgorithm(ABC):
     def _log_update(self, step: int) -> None:
         """Scalar logging at the algorithm's cadence (the only host sync of an update)."""
 
-    def update_from_buffer(self, replay_buffer, batch_size: int, act_next=None) -> None:
+    def update_from_buffer(self, replay_buffer, batch_size: int, act_next=None, n_updates: int = 1) -> None:
         """``update(*replay_buffer.sample(batch_size))`` as ONE C call (oprl_learner_step_n with
         K = 1): the slice kernels gather their own rows from the HBM replay with the sampler's
         Philox draw, so the per-step host work is one ctypes call instead of a gather launch, five
@@ -46,28 +46,54 @@ class OffPolicyAlgorithm(ABC):
         (oprl_learner_step_act) and the next ``actor.explore(act_next)`` — with this very array — only collects the
         row: one host wait per environment step instead of update-sync, act-launch, act-sync.
 
+        A 2-D ``act_next`` [N, S] (the next observations of N environments, trainers/vec_trainer.py) rides as ROWS
+        behind K = ``n_updates`` updates — one oprl_learner_step_act_rows call — and the next
+        ``actor.explore_rows(act_next)`` collects them.  ``n_updates`` > 1 without ``act_next``: one ``step_n(K)``.
+
         A ``prioritized`` algorithm over a prioritized buffer: one ``step_n_prio`` call instead (draw by priority,
         weighted update, new priorities); ``act_next`` is accepted but rides nowhere, ``explore`` runs its own forward."""
         refuse_prioritized(self, replay_buffer)
         check_nstep_gamma(self, replay_buffer)
+        K = int(n_updates)
+        if K < 1:
+            raise ValueError(f"n_updates={n_updates!r}: at least one update")
         if trains_prioritized(self, replay_buffer):
             step = self.update_step
-            step_prioritized(self, replay_buffer, 1, batch_size)
-            self._log_update(step)
+            step_prioritized(self, replay_buffer, K, batch_size)
+            self._log_updates(step, K)
             return
         handle = getattr(replay_buffer, "handle", None)
         if handle is None or self.learner.export_grads:
-            self.update(*replay_buffer.sample(batch_size))
+            for _ in range(K):
+                self.update(*replay_buffer.sample(batch_size))
             return
         step = self.update_step
         seed = int(getattr(replay_buffer, "seed", 0))
         mlp = self._actor_mlp() if act_next is not None else None
-        if mlp is not None:
+        if mlp is not None and np.ndim(act_next) == 2:
+            self.learner.step_act_rows(handle, K, int(batch_size), seed, act_next)
+            mlp.set_pending_rows(act_next, self.learner)
+        elif mlp is not None:
+            if K > 1:
+                self.learner.step_n(handle, K - 1, int(batch_size), seed=seed)
             self.learner.step_act(handle, int(batch_size), seed, act_next)
             mlp.set_pending(act_next, self.learner)
         else:
-            self.learner.step_n(handle, 1, int(batch_size), seed=seed)
-        self._log_update(step)
+            self.learner.step_n(handle, K, int(batch_size), seed=seed)
+        self._log_updates(step, K)
+
+    def _log_updates(self, step: int, K: int) -> None:
+        """``_log_update`` for the updates ``step .. step + K - 1`` of one call: at most one of them logs (the scalars
+        on the device are the last update's)."""
+        if K == 1:
+            self._log_update(step)
+            return
+        every = int(getattr(self, "log_every", 0) or 0)
+        if every <= 0:
+            return
+        first = -(-step // every) * every       # the first multiple of log_every at or after `step`
+        if first < step + K:
+            self._log_update(first)
 
     def _actor_mlp(self):
         """The actor's MLP when it is one the learner's policy kernel can run (the policy classes of nn_models.py)."""
@@ -133,6 +159,14 @@ def check_nstep_gamma(algo, replay_buffer) -> None:
         raise ValueError(f"the replay buffer samples {replay_buffer.n_step}-step returns with gamma={replay_buffer.gamma!r} "
                          f"but {type(algo).__name__} discounts with gamma={algo.gamma!r}: build the buffer with the "
                          "algorithm's gamma")
+
+
+def _rows_f32(obs) -> np.ndarray:
+    """Observation rows as one contiguous float32 [N, S] host array."""
+    x = np.ascontiguousarray(obs, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError(f"observation rows must be a 2-D array [N, S], got shape {x.shape}")
+    return x
 
 
 def require_gpu(device: str) -> t.device:
@@ -422,6 +456,31 @@ class HipLearner:
         out = np.empty(n_out, dtype=np.float32)
         _capi.check(self.lib.oprl_learner_act_wait(self.handle, out.ctypes.data_as(C.c_void_p), n_out, timeout_us),
                     "oprl_learner_act_wait")
+        return out
+
+    def act_rows(self, obs) -> None:
+        """Enqueue the actor's forward of the rows ``obs[N, S]`` (oprl_learner_act_rows): nothing is waited for;
+        ``act_rows_wait`` collects them."""
+        self.check_bound()
+        x = _rows_f32(obs)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_act_rows(self.handle, x.ctypes.data_as(C.c_void_p), x.shape[0],
+                                                       _capi.current_stream()), "oprl_learner_act_rows")
+
+    def step_act_rows(self, replay_handle, K: int, B: int, seed: int, obs) -> None:
+        """K sample()+update() iterations and, enqueued behind them, the actor's forward of the rows ``obs[N, S]`` with
+        the weights they leave (oprl_learner_step_act_rows)."""
+        self.check_bound()
+        x = _rows_f32(obs)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_step_act_rows(self.handle, replay_handle, K, B, seed,
+                                                            x.ctypes.data_as(C.c_void_p), x.shape[0],
+                                                            _capi.current_stream()), "oprl_learner_step_act_rows")
+
+    def act_rows_wait(self, n_rows: int, n_out: int, timeout_us: int = 5_000_000):
+        out = np.empty((n_rows, n_out), dtype=np.float32)
+        _capi.check(self.lib.oprl_learner_act_rows_wait(self.handle, out.ctypes.data_as(C.c_void_p), n_rows, n_out,
+                                                        timeout_us), "oprl_learner_act_rows_wait")
         return out
 
     def check(self) -> None:

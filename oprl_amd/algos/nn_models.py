@@ -263,6 +263,41 @@ class MLP(nn.Module):
         the next ``hip_act`` with the same array collects it instead of launching."""
         self.__dict__["_pending"] = (obs, learner)        # (not nn.Module.__setattr__: microseconds per env step)
 
+    def hip_act_rows(self, obs: npt.NDArray) -> npt.NDArray:
+        """N observations (host, [N, S], N <= 256) -> the N raw output rows (host, [N, dims[-1]]) in one launch
+        (csrc/policy_act_rows.hip): exact fp32 over the master weights, every row's bits independent of N, of its
+        position and of its neighbours.  Collects the rows a learner has in flight for this very array
+        (``set_pending_rows``); otherwise oprl_mlp_act_rows, synchronous."""
+        if not self._hip_ok:
+            raise RuntimeError("the HIP MLP kernels implement ReLU hidden / identity output only")
+        pending = self.__dict__.get("_pending_rows")
+        if pending is not None:
+            self.__dict__["_pending_rows"] = None
+            p_obs, learner = pending
+            raw = learner.act_rows_wait(int(np.shape(p_obs)[0]), self.dims[-1])
+            if p_obs is obs:
+                return raw
+        x = np.ascontiguousarray(obs, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.dims[0]:
+            raise ValueError(f"observation rows must be [N, {self.dims[0]}], got shape {x.shape}")
+        out = np.empty((x.shape[0], self.dims[-1]), dtype=np.float32)
+        dev = self._params()[0].device
+        theta = self.theta_ptr()
+        if self._desc is not None and self._desc_key is not None and self._desc_key[0] == theta:
+            desc = self._desc
+        else:
+            desc = _net_desc(self.dims, theta)       # (the masters alone are read: no packs, no repack)
+        with _capi.on_device(dev):
+            _capi.check(_capi.load().oprl_mlp_act_rows(C.byref(desc), x.ctypes.data_as(C.c_void_p), x.shape[0], x.shape[1],
+                                                       out.ctypes.data_as(C.c_void_p), self.dims[-1],
+                                                       _capi.current_stream()), "oprl_mlp_act_rows")
+        return out
+
+    def set_pending_rows(self, obs, learner) -> None:
+        """The learner has this net's forward of the rows ``obs`` in flight (oprl_learner_step_act_rows / act_rows):
+        the next ``hip_act_rows`` with the same array collects them instead of launching."""
+        self.__dict__["_pending_rows"] = (obs, learner)
+
     def forward(self, x: t.Tensor) -> t.Tensor:
         if x.is_cuda:
             return self.hip_forward(x)
@@ -354,6 +389,31 @@ class DeterministicPolicy(nn.Module):
                 raw = self.mlp(s)[0].numpy() + noise
         return np.clip(raw, -self._max_action, self._max_action)
 
+    def exploit_rows(self, states: npt.NDArray) -> npt.NDArray:
+        """``exploit`` for N observations [N, S] at once: [N, A]."""
+        return np.tanh(_raw_rows(self.mlp, states, self._device)).astype(np.float32)
+
+    def explore_rows(self, states: npt.NDArray) -> npt.NDArray:
+        """``explore`` for N observations [N, S] at once, the same semantics row by row (noise, clip, NO tanh).  The
+        noise is ONE ``t.randn(N, A)`` draw per call: these are not the draws N single ``explore`` calls would make."""
+        raw = _raw_rows(self.mlp, states, self._device)
+        noise = (t.randn(raw.shape[0], self._action_shape) * self._expl_noise).numpy()
+        return np.clip(raw + noise, -self._max_action, self._max_action)
+
+
+def _raw_rows(mlp: MLP, states: npt.NDArray, device) -> npt.NDArray:
+    """The raw last-layer rows of ``states[N, S]``: the row kernel for a net on the GPU, one batched torch forward for
+    a net on the CPU (the actor processes of the distributed setup)."""
+    if mlp.on_gpu():
+        if len(states) <= _capi.OPRL_ACT_ROWS_MAX:
+            return mlp.hip_act_rows(states)
+        x = np.ascontiguousarray(states, dtype=np.float32)      # (more rows than one launch takes: several)
+        return np.concatenate([mlp.hip_act_rows(x[i:i + _capi.OPRL_ACT_ROWS_MAX])
+                               for i in range(0, len(x), _capi.OPRL_ACT_ROWS_MAX)])
+    s = t.as_tensor(np.asarray(states), dtype=t.float32, device=device)
+    with t.no_grad():
+        return mlp.nn(s).numpy()
+
 
 class TanhNormal:
     """tanh-squashed diagonal Gaussian (reference nn_models.py:197-214)."""
@@ -428,3 +488,21 @@ class GaussianActor(nn.Module):
 
     def exploit(self, state: npt.NDArray) -> npt.NDArray:
         return self._act(state, sample=False)
+
+    def _act_rows(self, states: npt.NDArray, sample: bool) -> npt.NDArray:
+        """``_act`` for N observations [N, S] at once: the MLP's raw rows, the head on the host in numpy."""
+        raw = _raw_rows(self.net, states, self.device)
+        mean, log_std = raw[:, :self.action_dim], raw[:, self.action_dim:]
+        if not sample:
+            return np.tanh(mean).astype(np.float32)
+        std = np.exp(np.clip(log_std, *LOG_STD_MIN_MAX))
+        return np.tanh(mean + std * t.randn(raw.shape[0], self.action_dim).numpy()).astype(np.float32)
+
+    def explore_rows(self, states: npt.NDArray) -> npt.NDArray:
+        """``explore`` for N observations at once: a sample per row in train mode, tanh(mean) in eval mode.  The noise is
+        ONE ``t.randn(N, A)`` draw per call: these are not the draws N single ``explore`` calls would make."""
+        return self._act_rows(states, sample=self.training)
+
+    def exploit_rows(self, states: npt.NDArray) -> npt.NDArray:
+        """``exploit`` for N observations [N, S] at once: tanh(mean), [N, A]."""
+        return self._act_rows(states, sample=False)

@@ -16,6 +16,7 @@ from __future__ import annotations
 import math
 from dataclasses import dataclass, field
 
+import numpy as np
 import torch as t
 from torch import nn
 
@@ -144,13 +145,16 @@ class REDQ(OffPolicyAlgorithm):
             self.learner.update(state, action, reward, done, next_state, noise0=n0, noise1=n1)
         self._log_update(step)
 
-    def update_from_buffer(self, replay_buffer, batch_size: int, act_next=None) -> None:
+    def update_from_buffer(self, replay_buffer, batch_size: int, act_next=None, n_updates: int = 1) -> None:
         """``utd_ratio`` times ``update(*replay_buffer.sample(batch_size))`` as one ``step_n(K=utd_ratio)`` call.
         ``act_next``: the actor's forward of it rides behind the last update (``step_n(K - 1)`` + ``step_act``, the
-        same updates bit for bit)."""
+        same updates bit for bit).  ``n_updates``: that many environment steps' worth, K = ``n_updates x utd_ratio``;
+        a 2-D ``act_next`` [N, S] rides as rows behind all K (one ``step_act_rows`` call)."""
         refuse_prioritized(self, replay_buffer)
         check_nstep_gamma(self, replay_buffer)
-        K = int(self.utd_ratio)
+        if int(n_updates) < 1:
+            raise ValueError(f"n_updates={n_updates!r}: at least one update")
+        K = int(n_updates) * int(self.utd_ratio)
         if trains_prioritized(self, replay_buffer):      # (one step_n_prio call; act_next rides nowhere)
             step = self.update_step
             step_prioritized(self, replay_buffer, K, batch_size)
@@ -167,7 +171,10 @@ class REDQ(OffPolicyAlgorithm):
         step = self.update_step
         seed = int(getattr(replay_buffer, "seed", 0))
         mlp = self._actor_mlp() if act_next is not None else None
-        if mlp is not None:
+        if mlp is not None and np.ndim(act_next) == 2:
+            self.learner.step_act_rows(handle, K, int(batch_size), seed, act_next)
+            mlp.set_pending_rows(act_next, self.learner)
+        elif mlp is not None:
             if K > 1:
                 self.learner.step_n(handle, K - 1, int(batch_size), seed=seed)
             self.learner.step_act(handle, int(batch_size), seed, act_next)

@@ -399,6 +399,7 @@ extern "C" int oprl_learner_destroy(oprl_learner* h) {
   dev_free(h->uc_base);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->act_pin) (void)hipHostFree(h->act_pin);
+  if (h->rows_pin) (void)hipHostFree(h->rows_pin);
   if (h->p2p.window) p2p_destroy(h->p2p);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   for (int j = 1; j < OPRL_MAX_CRITICS; ++j) {

@@ -405,6 +405,12 @@ struct oprl_learner {
   float* act_map = nullptr;
   unsigned act_ticket = 0;
   bool act_pending = false;
+  // oprl_learner_act_rows / step_act_rows (csrc/policy_act_rows.hip): a pinned area of its own, allocated by the first such
+  // call [obs OPRL_ACT_ROWS_MAX x S floats | out OPRL_ACT_ROWS_MAX x n_out granules], its ticket and the pending rows (0: none)
+  float* rows_pin = nullptr;
+  float* rows_map = nullptr;
+  unsigned rows_ticket = 0;
+  int rows_pending = 0;
   unsigned long long* du_granules = nullptr;
   unsigned long long* g1_granules = nullptr;
   float* w3_snap = nullptr;

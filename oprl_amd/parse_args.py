@@ -21,6 +21,9 @@ _SHARED = (
 _SINGLE = (
     ("--seeds", int, 1, "how many seeds to train, one process each"),
     ("--start_seed", int, 0, "first seed; the others count up from it"),
+    # extension: N environments stepped per iteration, their actions from one policy launch (trainers/vec_trainer.py,
+    # DESIGN.md section 13); 1 = the reference's loop (trainers/base_trainer.py)
+    ("--num-envs", int, 1, "environments stepped per iteration, one policy launch for all (1..256; 1 = the reference's one-environment loop)"),
 )
 _DISTRIB = (
     ("--seed", int, 0, "random seed of the run"),

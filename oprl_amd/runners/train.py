@@ -18,6 +18,7 @@ from oprl_amd.environment.protocols import EnvProtocol
 from oprl_amd.logging import LoggerProtocol
 from oprl_amd.runners.config import CommonParameters
 from oprl_amd.trainers.base_trainer import BaseTrainer
+from oprl_amd.trainers.vec_trainer import VecTrainer
 
 
 def set_seed(seed: int) -> None:
@@ -27,7 +28,7 @@ def set_seed(seed: int) -> None:
 
 
 def _run_training_func(make_algo, make_env, make_replay_buffer, make_logger,
-                       config: CommonParameters, seed: int, **trainer_kwargs) -> None:
+                       config: CommonParameters, seed: int, num_envs: int = 1, **trainer_kwargs) -> None:
     set_seed(seed)
     env = make_env(seed)
     replay_buffer = make_replay_buffer()
@@ -42,10 +43,21 @@ def _run_training_func(make_algo, make_env, make_replay_buffer, make_logger,
         algo.set_seed(seed)
     if env.env_family not in ("dm_control", "gymnasium", "synthetic"):
         raise ValueError(f"Unsupported env family: {env.env_family}")
-    BaseTrainer(env=env, make_env_test=make_env, algo=algo, replay_buffer=replay_buffer,
-                num_steps=config.num_steps, eval_interval=config.eval_every, device=config.device,
-                estimate_q_every=config.estimate_q_every, stdout_log_every=config.log_every,
-                seed=seed, logger=logger, **trainer_kwargs).train()
+    common = dict(make_env_test=make_env, algo=algo, replay_buffer=replay_buffer,
+                  num_steps=config.num_steps, eval_interval=config.eval_every, device=config.device,
+                  estimate_q_every=config.estimate_q_every, stdout_log_every=config.log_every,
+                  seed=seed, logger=logger, **trainer_kwargs)
+    if num_envs > 1:
+        # N environments per iteration, one policy launch for all of them (trainers/vec_trainer.py)
+        VecTrainer(envs=[env, *[make_env(s) for s in env_seeds(seed, num_envs)[1:]]], **common).train()
+        return
+    BaseTrainer(env=env, **common).train()
+
+
+def env_seeds(seed: int, num_envs: int) -> list[int]:
+    """Seeds of the ``num_envs`` environments of run ``seed``: the run seed itself first, the others a prime stride
+    away (runs whose seeds count up from each other share no environment seed below 7919 runs)."""
+    return [seed + 7919 * i for i in range(num_envs)]
 
 
 def run_training(
@@ -56,10 +68,13 @@ def run_training(
     config: CommonParameters,
     seeds: int = 1,
     start_seed: int = 0,
+    num_envs: int = 1,
     **trainer_kwargs,
 ) -> None:
+    if not 1 <= num_envs <= 256:
+        raise ValueError(f"num_envs={num_envs}: expected 1..256 (one policy launch takes up to 256 rows)")
     if seeds == 1:
-        _run_training_func(make_algo, make_env, make_replay_buffer, make_logger, config, 0, **trainer_kwargs)
+        _run_training_func(make_algo, make_env, make_replay_buffer, make_logger, config, 0, num_envs, **trainer_kwargs)
         return
     # the seeds share ONE GPU: launches whose workgroups wait for each other inside the launch (clusters of eight, the
     # merged phase + tile launches, the whole-update launch: include/oprl_amd.h) need their workgroups co-resident, and a
@@ -69,7 +84,7 @@ def run_training(
     os.environ.setdefault("OPRL_AMD_FORM", "plain")
     ctx = get_context("spawn")   # a forked child cannot re-initialise the GPU runtime
     procs = [ctx.Process(target=_run_training_func,
-                         args=(make_algo, make_env, make_replay_buffer, make_logger, config, seed),
+                         args=(make_algo, make_env, make_replay_buffer, make_logger, config, seed, num_envs),
                          kwargs=trainer_kwargs)
              for seed in range(start_seed, start_seed + seeds)]
     for i, p in enumerate(procs):
