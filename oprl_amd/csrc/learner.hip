@@ -163,7 +163,7 @@ void dev_free(void* p) {
 }
 
 // (wide_too: also when only the wide layers' packs are stale — the launch about to run reads THOSE)
-int fresh32_tables(oprl_learner* h, int which /* bit 0 critics, bit 1 actor */, hipStream_t st, bool wide_too = false) {
+int fresh32_tables(oprl_learner* h, int which /* bit 0 critics, bit 1 actor */, hipStream_t st, bool wide_too) {
   if ((which & 1) && (h->stale32[0] || (wide_too && h->stale_wide))) {
     HIPC(launch_repack(h->rp_dev[1], h->rp_n[1], h->rp_blocks[1], st));
     h->stale32[0] = false;
@@ -296,7 +296,6 @@ bool tp_generic(const oprl_learner* h, const oprl_net& n, int B) {
 MlpArgs base_args(oprl_learner* h, const oprl_net& n, bool target, int B) {
   MlpArgs a;
   memset(&a, 0, sizeof a);
-  a.owner = h;
   if (tp_generic(h, n, B)) {
     a.tp_xbuf = h->xbuf;
     a.tp_tag_counter = &h->tp_tag;
@@ -334,49 +333,6 @@ void with_store(MlpArgs& a, const NetWs& ws, bool x, bool dy) {
   a.dY0_stride = ws.dY0_stride;
 }
 
-// launch-unique 26-bit tag for the cluster exchanges of one learner; on wrap-around every stale
-// granule is retired
-int next_tp_tag(unsigned* counter, unsigned long long* xbuf, size_t xbuf_bytes, hipStream_t st, unsigned* out) {
-  *counter += 1;
-  if ((*counter & 0x03FFFFFFu) == 0) {
-    *counter += 1;
-    HIPC(hipMemsetAsync(xbuf, 0, xbuf_bytes, st));
-  }
-  *out = *counter & 0x03FFFFFFu;
-  return OPRL_OK;
-}
-
-int launch(const MlpArgs& a0, int width, hipStream_t st) {
-  if (a0.tp_xbuf != nullptr && mlp_slice_tp_shape_ok(a0, width)) {
-    MlpArgs a = a0;
-    RC(next_tp_tag(a.tp_tag_counter, a.tp_xbuf, a.tp_xbuf_bytes, st, &a.tp_tag));
-    oprl_learner* own = (oprl_learner*)a.owner;
-    if (own != nullptr && own->pair_collect && own->pair_n < 2) {   // for_each_net over a pair: defer
-      own->pair_args[own->pair_n++] = a;
-      return OPRL_OK;
-    }
-    prof_begin(0, st);
-    hipError_t e = launch_mlp_slice_tp(a, st);
-    prof_end(st);
-    HIPC(e);
-    return OPRL_OK;
-  }
-  const MlpArgs& a = a0;
-  {
-    oprl_learner* own = (oprl_learner*)a.owner;
-    if (own != nullptr && own->multi_collect && own->multi_n < kMaxMulti) {
-      own->multi_width = width;
-      own->multi_args[own->multi_n++] = a;
-      return OPRL_OK;
-    }
-  }
-  prof_begin(0, st);
-  hipError_t e = launch_mlp_slice(a, width, st);
-  prof_end(st);
-  HIPC(e);
-  return OPRL_OK;
-}
-
 hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st) {
   if (h != nullptr) a.no_wide = h->sw.no_wide_dw ? 1 : 0;
   prof_begin(1, st);
@@ -385,178 +341,14 @@ hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st) {
   return e;
 }
 
-// launch_j(j0, st) and launch_j(j0 + 1, st): twin nets on the same slices — their cluster launches (slice_tp.hip) go
-// out as ONE launch
+// One round of the generic launch sequence: make_j(j) builds the arguments of net j in [0, n), and launch_round
+// (net_rounds.hip) decides from the list how they go out.
 template <class F>
-int pair_launch(oprl_learner* h, int j0, hipStream_t st, F& launch_j) {
-  h->pair_collect = true;
-  h->pair_n = 0;
-  int rc = launch_j(j0, st);
-  if (rc == OPRL_OK) rc = launch_j(j0 + 1, st);
-  h->pair_collect = false;
-  RC(rc);
-  if (h->pair_n == 2 && h->pair_args[0].B == h->pair_args[1].B) {
-    prof_begin(0, st);
-    hipError_t e = launch_mlp_slice_tp2(h->pair_args[0], h->pair_args[1], h->n_cus, st);
-    prof_end(st);
-    HIPC(e);
-  } else {
-    for (int k = 0; k < h->pair_n; ++k) {
-      prof_begin(0, st);
-      hipError_t e = launch_mlp_slice_tp(h->pair_args[k], st);
-      prof_end(st);
-      HIPC(e);
-    }
-  }
-  h->pair_n = 0;
-  return OPRL_OK;
-}
-
-// Run launch_j(j, stream) for j in [0, n): net 0 on the caller's stream, the others on
-// side streams forked from / joined back into it, so independent nets overlap on the GPU
-// (each k_mlp_slice launch occupies only ceil(B/16) of the 256 CUs).
-template <class F>
-int for_each_net(oprl_learner* h, int n, hipStream_t st, F&& launch_j) {
-  // measured: the event fork/join costs more than it saves for 2 nets (TD3 8.8k -> 7.7k/s),
-  // pays for the 5 quantile critics of TQC (673 -> 1206/s)
-  if (n == 2) return pair_launch(h, 0, st, launch_j);
-  if (n > 2 && n <= kMaxMulti) {
-    // equal nets on the same slices (TQC's quantile critics): one launch, grid (slices, nets)
-    h->multi_collect = true;
-    h->multi_n = 0;
-    int rc = OPRL_OK;
-    for (int j = 0; j < n && rc == OPRL_OK; ++j) rc = launch_j(j, st);
-    h->multi_collect = false;
-    RC(rc);
-    bool same = h->multi_n > 0;
-    for (int k = 1; k < h->multi_n; ++k)
-      same = same && h->multi_args[k].B == h->multi_args[0].B &&
-             h->multi_args[k].net.n_layers == h->multi_args[0].net.n_layers;
-    // wide nets go layer by layer over the whole chip (csrc/layerwise.hip); launches that keep no
-    // activations (target nets, the actor phase's critics) borrow the nets' dW exchange buffers,
-    // which nobody reads until the next storing launch overwrites them
-    if (same && !h->sw.no_layerwise && h->multi_width == 512 && h->multi_n <= h->nc) {
-      for (int k = 0; k < h->multi_n; ++k) {
-        MlpArgs& a = h->multi_args[k];
-        const NetWs& ws = h->ws_critic[k];
-        for (int l = 1; l < a.net.n_layers; ++l)
-          if (a.Xg[l] == nullptr)
-            a.Xg[l] = (!a.do_bwd && h->lw_scratch != nullptr)
-                          ? h->lw_scratch + ((size_t)k * (kMaxLayers - 1) + (l - 1)) * (size_t)h->Bmax * 512
-                          : ws.X[l];
-        for (int l = 0; l + 1 < a.net.n_layers; ++l)
-          if (a.dYg[l] == nullptr) a.dYg[l] = ws.dY[l];
-      }
-    }
-    if (same && !h->sw.no_layerwise && mlp_layerwise_ok(h->multi_args, h->multi_n, h->multi_width)) {
-      // bf16 learners: the hidden layers (all but the first and the last) through their bf16 packs
-      bool lw16 = h->bf16 || h->x2;
-      for (int k = 0; k < h->multi_n; ++k) {
-        const MlpArgs& a = h->multi_args[k];
-        for (int l = 1; l + 1 < a.net.n_layers; ++l)
-          lw16 = lw16 && a.pf16[l] != nullptr && (!a.do_bwd || a.pb16[l] != nullptr);
-      }
-      if (lw16)
-        for (int k = 0; k < h->multi_n; ++k) {
-          MlpArgs& a = h->multi_args[k];
-          for (int l = 1; l + 1 < a.net.n_layers; ++l) { a.net.pf[l] = a.pf16[l]; if (a.pb16[l]) a.net.pb[l] = a.pb16[l]; }
-        }
-      prof_begin(0, st);
-      // a pending TD-target job (critic_phase) rides on this launch's heads when it is the target critics' forward
-      const TqcJob* job = nullptr;
-      if (h->tqc_job_pending && !h->multi_args[0].do_bwd && h->multi_args[0].do_fwd && h->multi_n == h->tqc_job.n_nets &&
-          h->multi_args[0].out == h->tqc_job.z) {
-        job = &h->tqc_job;
-        h->tqc_job_pending = false;
-      }
-      // a pending rider (critic_phase: the actor's forward on s) goes with the storing launch's heads
-      const MlpArgs* rider = nullptr;
-      if (h->rider_pending && h->multi_args[0].do_bwd && h->multi_args[0].do_fwd &&
-          mlp_layerwise_rider_ok(h->multi_args, h->multi_n, h->rider, h->n_cus)) {
-        rider = &h->rider;
-        h->rider_pending = false;
-        h->rider_done = true;
-      }
-      const bool first_done = h->fin_done && h->multi_args[0].do_bwd && h->multi_args[0].do_fwd && h->multi_args[0].Xg[0] != nullptr;
-      if (first_done) h->fin_done = false;
-      const bool second_done = first_done && h->fin_l2_done;
-      if (first_done) h->fin_l2_done = false;
-      // the part of the online critics' early first launch that did not fit beside the actor's forward rides on the
-      // target pass's heads (forward-only launch, 80 workgroups)
-      const MlpArgs* tail = nullptr;
-      int tail0 = 0;
-      if (h->fin_tail0 >= 0 && !h->multi_args[0].do_bwd && h->multi_args[0].do_fwd) {
-        const int slices = (h->multi_args[0].B + kR - 1) / kR;
-        const int rest = h->nc - h->fin_tail0;
-        if (mlp_layerwise_fin_fit(h->fin_args, h->nc, slices * h->multi_n, h->n_cus) >= rest) {   // all resident at once
-          tail = h->fin_args; tail0 = h->fin_tail0;
-          h->fin_tail0 = -1;
-        }
-      }
-      // step_n: the next update's rows ride on the launch sequence that ends in k_lw_dact (the actor step's critics)
-      const PrefetchJob* pf = nullptr;
-      if (h->prefetch_pending && h->multi_args[0].do_bwd && h->multi_args[0].dact_cols > 0 && h->prefetch.B == h->multi_args[0].B) {
-        pf = &h->prefetch;
-        h->prefetch_pending = false;
-        h->prefetch_done = true;
-      }
-      hipError_t e = launch_mlp_layerwise(h->multi_args, h->multi_n, h->multi_width, h->n_cus, st, lw16 ? (h->x2 ? 2 : 1) : 0, job, rider, first_done,
-                                          tail, h->nc, tail0, h->fin16 ? (h->x2 ? 2 : 1) : 0, pf, &h->lw_pairs, second_done,
-                                          tail != nullptr ? &h->fin_l2_done : nullptr,
-                                          (h->bwd_rider_pending && h->multi_args[0].do_bwd && h->multi_args[0].dact_cols > 0) ? &h->bwd_rider : nullptr,
-                                          &h->bwd_rider_done, h->bwd_tiles_pending ? &h->bwd_tiles : nullptr, h->bwd_tile_wgs, &h->bwd_tiles_done);
-      h->bwd_rider_pending = false;
-      h->bwd_tiles_pending = false;
-      // (a tag per pair launch; 2^32 launches on: every flag is retired before a tag can come round again)
-      if (h->lw_pairs.next_tag + (unsigned)h->lw_pairs.used < h->lw_pairs.next_tag && h->lw_pairs.flags != nullptr)
-        (void)hipMemsetAsync(h->lw_pairs.flags, 0, (size_t)h->lw_pairs.n_flags * sizeof(unsigned long long), st);
-      h->lw_pairs.next_tag += (unsigned)h->lw_pairs.used;
-      if (h->lw_pairs.next_tag == 0) h->lw_pairs.next_tag = 1;
-      h->lw_pairs.used = 0;
-      prof_end(st);
-      HIPC(e);
-    } else if (same) {
-      // (these kernels read the fp32 packs: a 16-bit TQC learner's wide critics leave theirs stale)
-      if (h->stale_wide && h->multi_width == h->w_critic) RC(fresh32_tables(h, 1, st, true));
-      prof_begin(0, st);
-      hipError_t e = launch_mlp_slice_multi(h->multi_args, h->multi_n, h->multi_width, st);
-      prof_end(st);
-      HIPC(e);
-    } else {
-      if (h->stale_wide && h->multi_width == h->w_critic) RC(fresh32_tables(h, 1, st, true));
-      for (int k = 0; k < h->multi_n; ++k) {
-        prof_begin(0, st);
-        hipError_t e = launch_mlp_slice(h->multi_args[k], h->multi_width, st);
-        prof_end(st);
-        HIPC(e);
-      }
-    }
-    h->multi_n = 0;
-    return OPRL_OK;
-  }
-  if (n > kMaxMulti && h->tp_generic_on) {
-    // more nets than a multi launch takes (REDQ's ensemble): in pairs on the caller's stream, each pair one k_mlp_slice_tp2
-    // launch (side by side, each net in its own exchange area, while both fit the chip).  Not on the side streams: every
-    // cluster launch of a learner exchanges through the same area of xbuf, and two such launches running at once would
-    // overwrite each other's granules
-    for (int j0 = 0; j0 < n; j0 += 2) {
-      RC(j0 + 1 == n ? launch_j(j0, st) : pair_launch(h, j0, st, launch_j));
-    }
-    return OPRL_OK;
-  }
-  if (n <= 2 || !h->have_side) {
-    for (int j = 0; j < n; ++j) RC(launch_j(j, st));
-    return OPRL_OK;
-  }
-  HIPC(hipEventRecord(h->ev_fork, st));
-  for (int j = 1; j < n; ++j) HIPC(hipStreamWaitEvent(h->side[j], h->ev_fork, 0));
-  for (int j = 0; j < n; ++j) {
-    hipStream_t sj = j == 0 ? st : h->side[j];
-    RC(launch_j(j, sj));
-    if (j > 0) HIPC(hipEventRecord(h->ev_join[j], sj));
-  }
-  for (int j = 1; j < n; ++j) HIPC(hipStreamWaitEvent(st, h->ev_join[j], 0));
-  return OPRL_OK;
+int for_each_net(oprl_learner* h, int n, int width, hipStream_t st, F&& make_j) {
+  MlpArgs a[OPRL_MAX_CRITICS];
+  if (n > OPRL_MAX_CRITICS) { set_err("internal: a round of %d nets", n); return OPRL_ERR_STATE; }
+  for (int j = 0; j < n; ++j) a[j] = make_j(j);
+  return launch_round(h, a, n, width, st);
 }
 
 const double* alpha_ptr(const oprl_learner* h) {
@@ -1095,38 +887,52 @@ int whole_update(oprl_learner* h, StepRows& rows, DdpgArgs& fa, const FusedForm&
   return OPRL_OK;
 }
 
-// Step 3 of the generic critic phase under importance weights (rows.w; oprl_learner_update_weighted, DESIGN.md §11): the
-// launch that is forward + seed + backward there, as three — the critics' forward with the activations stored and q into
-// qpi (idle until the actor phase), k_td_weighted_seed (per_seed.hip) on those q and the target operands SEED_MSE_TD takes,
-// the critics' backward from the stored activations with the seed read from memory (SEED_PTR).  The same for_each_net
-// groupings and the same stores, so step 4's dW + Adam reads what it always reads.
-int weighted_critic_step(oprl_learner* h, const StepRows& rows, int B, int n_min, hipStream_t st) {
+// online critic j on (s, a), activations and dY stored for its dW launch: the critic step's forward, with the backward or not
+MlpArgs critic_sa_args(oprl_learner* h, int j, const float* s, const float* a, int B, bool bwd) {
+  MlpArgs f = base_args(h, h->cfg.critics[j], false, B);
+  f.do_fwd = 1; f.do_bwd = bwd ? 1 : 0;
+  f.x0 = s; f.k0 = h->S; f.x1 = a; f.k1 = h->A;
+  with_store(f, h->ws_critic[j], true, true);
+  return f;
+}
+
+// SEED_MSE_TD's operands, all but the debug rows y_out / q_out.  n_min: REDQ's target critics (else unused)
+SeedArgs mse_td_seed(const oprl_learner* h, const float* r, const float* d, int B, int n_min) {
   const oprl_learner_config& c = h->cfg;
-  const int S = h->S, A = h->A, nc = h->nc, algo = c.algo;
-  const bool redq = algo == OPRL_REDQ;
-  if (h->per_seed == nullptr || rows.td_abs == nullptr) { set_err("internal: weighted critic step without its buffers"); return OPRL_ERR_STATE; }
-  RC(for_each_net(h, nc, st, [&](int j, hipStream_t sj) {
-    MlpArgs f = base_args(h, c.critics[j], false, B);
-    f.do_fwd = 1;
-    f.x0 = rows.cur.s; f.k0 = S; f.x1 = rows.cur.a; f.k1 = A;
-    with_store(f, h->ws_critic[j], true, true);
-    f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
-    return launch(f, h->w_critic, sj);
-  }));
-  TdSeedArgs t;
-  memset((void*)&t, 0, sizeof t);
-  SeedArgs& sd = t.s;                       // (as critic_phase fills SEED_MSE_TD's)
+  const bool redq = c.algo == OPRL_REDQ;
+  SeedArgs sd;
+  memset((void*)&sd, 0, sizeof sd);
   sd.p0 = h->qn;
-  sd.p1 = nc > 1 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
-  if (redq) {
+  sd.p1 = h->nc > 1 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
+  if (redq) {      // the minimum over the subset's slots: one or two rows here, else k_redq_min's row
     sd.p0 = n_min > 2 ? h->target : h->qn;
     sd.p1 = n_min == 2 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
   }
-  sd.p2 = (algo == OPRL_SAC || redq) ? h->logp2 : nullptr;
+  sd.p2 = (c.algo == OPRL_SAC || redq) ? h->logp2 : nullptr;
   sd.log_alpha = alpha_ptr(h); sd.alpha_const = (float)c.hp.alpha_init;
-  sd.r = rows.cur.r; sd.d = rows.cur.d; sd.gamma = (float)c.hp.gamma;
+  sd.r = r; sd.d = d; sd.gamma = (float)c.hp.gamma;
   sd.cval = 1.0f / (float)B;
-  sd.y_out = h->ydbg; sd.q_out = h->qdbg;
+  return sd;
+}
+
+// Step 3 of the generic critic phase under importance weights (rows.w; oprl_learner_update_weighted, DESIGN.md §11): the
+// launch that is forward + seed + backward there, as three — the critics' forward with the activations stored and q into
+// qpi (idle until the actor phase), k_td_weighted_seed (per_seed.hip) on those q and the target operands SEED_MSE_TD takes,
+// the critics' backward from the stored activations with the seed read from memory (SEED_PTR).  The same rounds
+// (for_each_net) and the same stores, so step 4's dW + Adam reads what it always reads.
+int weighted_critic_step(oprl_learner* h, const StepRows& rows, int B, int n_min, hipStream_t st) {
+  const oprl_learner_config& c = h->cfg;
+  const int nc = h->nc;
+  if (h->per_seed == nullptr || rows.td_abs == nullptr) { set_err("internal: weighted critic step without its buffers"); return OPRL_ERR_STATE; }
+  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
+    MlpArgs f = critic_sa_args(h, j, rows.cur.s, rows.cur.a, B, false);
+    f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
+    return f;
+  }));
+  TdSeedArgs t;
+  memset((void*)&t, 0, sizeof t);
+  t.s = mse_td_seed(h, rows.cur.r, rows.cur.d, B, n_min);
+  t.s.y_out = h->ydbg; t.s.q_out = h->qdbg;
   t.q = h->qpi; t.q_stride = h->Bmax;
   t.w = rows.w;
   t.seed = h->per_seed; t.seed_stride = h->Bmax;
@@ -1137,13 +943,13 @@ int weighted_critic_step(oprl_learner* h, const StepRows& rows, int B, int n_min
   hipError_t e = launch_td_weighted_seed(t, st);
   prof_end(st);
   HIPC(e);
-  return for_each_net(h, nc, st, [&](int j, hipStream_t sj) {
+  return for_each_net(h, nc, h->w_critic, st, [&](int j) {
     MlpArgs f = base_args(h, c.critics[j], false, B);
     f.do_bwd = 1;
     with_store(f, h->ws_critic[j], true, true);
     f.seed_mode = SEED_PTR;
     f.seed.p0 = h->per_seed + (size_t)j * h->Bmax; f.seed.ld0 = 1;
-    return launch(f, h->w_critic, sj);
+    return f;
   });
 }
 
@@ -1229,10 +1035,7 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
         h->lw_scratch != nullptr && h->w_critic == 512 && f.tp_xbuf != nullptr) {
       fin16 = h->bf16 || h->x2;
       for (int j = 0; j < nc; ++j) {
-        MlpArgs g = base_args(h, c.critics[j], false, B);
-        g.do_fwd = 1; g.do_bwd = 1;
-        g.x0 = s; g.k0 = S; g.x1 = a; g.k1 = A;
-        with_store(g, h->ws_critic[j], true, true);
+        MlpArgs g = critic_sa_args(h, j, s, a, B, true);
         for (int l = 1; l + 1 < g.net.n_layers; ++l) fin16 = fin16 && g.pf16[l] != nullptr && g.pb16[l] != nullptr;
         fin_args[j] = g;
       }
@@ -1271,12 +1074,12 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
   const bool redq = algo == OPRL_REDQ;
   const int n_min = redq ? c.hp.n_min : 0;
   if (redq) redq_subset(h->noise_seed, h->noise_rank, (uint64_t)h->update_count, nc, n_min, h->redq_subset);
-  RC(for_each_net(h, redq ? n_min : nc, st, [&](int j, hipStream_t sj) {
+  RC(for_each_net(h, redq ? n_min : nc, h->w_critic, st, [&](int j) {
     MlpArgs f = base_args(h, c.critics[redq ? h->redq_subset[j] : j], true, B);
     f.do_fwd = 1;
     f.x0 = s2; f.k0 = S; f.x1 = h->a2; f.k1 = A;
     f.out = h->qn + (size_t)j * h->Bmax * h->ldq; f.ldo = h->ldq;
-    return launch(f, h->w_critic, sj);
+    return f;
   }));
   // (M > 2: their minimum as one row, k_redq_min, into the TQC target's buffer, which REDQ does not use)
   if (redq && n_min > 2) HIPC(launch_redq_min(h->qn, (long)h->Bmax * h->ldq, h->ldq, n_min, B, h->target, st));
@@ -1311,11 +1114,8 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
       h->rider_pending = true;
     }
   }
-  RC(for_each_net(h, nc, st, [&](int j, hipStream_t sj) {
-    MlpArgs f = base_args(h, c.critics[j], false, B);
-    f.do_fwd = 1; f.do_bwd = 1;
-    f.x0 = s; f.k0 = S; f.x1 = a; f.k1 = A;
-    with_store(f, h->ws_critic[j], true, true);
+  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
+    MlpArgs f = critic_sa_args(h, j, s, a, B, true);
     f.partials = h->part_c + (size_t)j * n_slices * 4;
     SeedArgs& sd = f.seed;
     if (algo == OPRL_TQC) {
@@ -1325,19 +1125,10 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
       sd.cval = 1.0f / ((float)B * (float)nc * (float)Q * (float)M);
     } else {
       f.seed_mode = SEED_MSE_TD;
-      sd.p0 = h->qn;
-      sd.p1 = nc > 1 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
-      if (redq) {      // the minimum over the subset's slots: one or two rows here, else k_redq_min's row
-        sd.p0 = n_min > 2 ? h->target : h->qn;
-        sd.p1 = n_min == 2 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
-      }
-      sd.p2 = (algo == OPRL_SAC || redq) ? h->logp2 : nullptr;
-      sd.log_alpha = alpha_ptr(h); sd.alpha_const = (float)c.hp.alpha_init;
-      sd.r = r; sd.d = d; sd.gamma = (float)c.hp.gamma;
-      sd.cval = 1.0f / (float)B;
+      sd = mse_td_seed(h, r, d, B, n_min);
       if (j == 0) { sd.y_out = h->ydbg; sd.q_out = h->qdbg; }
     }
-    return launch(f, h->w_critic, sj);
+    return f;
   }));
   h->rider_pending = false;          // (not taken: actor_phase launches the forward itself)
   if (h->fin_done) {                 // the early first launch was not picked up: step 3 did not run layer by layer
@@ -1438,15 +1229,15 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
   }
   // 6./7. critics on (s, pi): gradient wrt the action columns
   if (algo == OPRL_SAC) {
-    RC(for_each_net(h, nc, st, [&](int j, hipStream_t sj) {   // both q's before either seed (min)
+    RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {   // both q's before either seed (min)
       MlpArgs f = base_args(h, c.critics[j], false, B);
       f.do_fwd = 1;
       f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
       with_store(f, h->ws_critic[j], true, false);
       f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
-      return launch(f, h->w_critic, sj);
+      return f;
     }));
-    RC(for_each_net(h, nc, st, [&](int j, hipStream_t sj) {
+    RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
       MlpArgs f = base_args(h, c.critics[j], false, B);
       f.do_bwd = 1;
       with_store(f, h->ws_critic[j], true, false);
@@ -1455,7 +1246,7 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
       f.seed.cval = 1.0f / (float)B;
       f.dact_col0 = S; f.dact_cols = A; f.dact = h->da + (size_t)j * h->Bmax * A; f.lddact = A;
       if (j == 0) f.partials = h->part_a;
-      return launch(f, h->w_critic, sj);
+      return f;
     }));
   } else {
     // TQC: the actor's backward (step 8) consumes the action gradients the launch sequence below ends with (k_lw_dact):
@@ -1484,7 +1275,7 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
         }
       }
     }
-    RC(for_each_net(h, n_q, st, [&](int j, hipStream_t sj) {
+    RC(for_each_net(h, n_q, h->w_critic, st, [&](int j) {
       MlpArgs f = base_args(h, c.critics[j], false, B);
       f.do_fwd = 1; f.do_bwd = 1;
       f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
@@ -1495,7 +1286,7 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
       f.dact_col0 = S; f.dact_cols = A; f.dact = h->da + (size_t)j * h->Bmax * A; f.lddact = A;
       if (j == 0) f.partials = h->part_a;
       if (algo == OPRL_REDQ) f.partials = h->part_a + (size_t)j * ((B + kR - 1) / kR) * 4;   // (read_scalars: mean over all N)
-      return launch(f, h->w_critic, sj);
+      return f;
     }));
   }
   // 8. actor backward from the stored activations — unless it rode on the k_lw_dact launch above

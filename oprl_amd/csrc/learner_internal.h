@@ -1,6 +1,6 @@
 // learner_internal.h — what the host-side translation units share: the learner's state (struct oprl_learner), the
 // launchers' declarations, small layout helpers, and the internals of learner.hip that learner_create.hip,
-// learner_dp.hip, learner_group.hip and learner_misc.hip call (namespace oprl_host; defined in learner.hip).
+// learner_dp.hip, learner_group.hip, learner_misc.hip and net_rounds.hip call (namespace oprl_host; defined in learner.hip).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -354,10 +354,6 @@ struct oprl_learner {
   const float* noise1_pending = nullptr;   // update()'s injected actor-phase draws: SAC's role C runs in phase 1
   bool tp_generic_on = false;  // the generic per-net launches may run on clusters of 4 (csrc/slice_tp.hip)
   unsigned tp_tag = 0;         // launch-unique tag source of the cluster exchanges (fused and generic)
-  // for_each_net over two nets: their cluster launches are collected and go out as one (k_mlp_slice_tp2)
-  bool pair_collect = false;
-  int pair_n = 0;
-  MlpArgs pair_args[2];
   P2pState p2p;                // one-shot all-reduce windows (csrc/p2p.hip); used when p2p_ok
   bool p2p_ok = false, p2p_tested = false, p2p_inline = false;
   int p2p_max_tiles = 0;
@@ -378,20 +374,17 @@ struct oprl_learner {
   LwPairBuf lw_pairs = {nullptr, 0, 1u, 1 << 20, nullptr, 3, 0};   // k_lw_mid_pair: flags (own allocation), tags; OPRL_AMD_LW_PAIR: bit 0 forward, bit 1 backward pairs (default 3)
   float* lw_scratch = nullptr; // [critics][layers 1 .. L-1][Bmax x 512]: activations of forward-only layer-by-layer launches (the target pass) — not the nets' dW exchange buffers, which the early first launch has already filled
   MlpArgs rider;               // TQC: the actor's forward on s, prepared in critic_phase to ride on the critic step's head launch ...
-  bool rider_pending = false;  // ... offered to the next for_each_net; taken: rider_done, and actor_phase skips its step 5
+  bool rider_pending = false;  // ... offered to the next round (launch_layerwise_round); taken: rider_done, and actor_phase skips its step 5
   bool rider_done = false;
   MlpArgs bwd_rider;           // TQC: the actor's backward, prepared in actor_phase to ride on the k_lw_dact launch whose rows it consumes (r06-16) ...
-  bool bwd_rider_pending = false;   // ... offered to the for_each_net with the action gradients; taken: bwd_rider_done, and step 8 is skipped
+  bool bwd_rider_pending = false;   // ... offered to the round with the action gradients; taken: bwd_rider_done, and step 8 is skipped
   bool bwd_rider_done = false;
   DwKArgs bwd_tiles;           // ... and its dW + Adam tiles (the actor's step 9) behind it (r06-18): offered with the rider; taken: bwd_tiles_done
   int bwd_tile_wgs = 0;
   bool bwd_tiles_pending = false, bwd_tiles_done = false;
   TqcJob tqc_job;              // TQC: the TD target as the tail of the target critics' head launch (kernels.h) ...
-  bool tqc_job_pending = false; // ... offered to the next for_each_net; still set afterwards: k_tqc_target as a launch of its own
+  bool tqc_job_pending = false; // ... offered to the next round; still set afterwards: k_tqc_target as a launch of its own
   unsigned long long* tqc_counter = nullptr;   // [slices at Bmax] arrival counters, zeroed once
-  bool multi_collect = false;  // for_each_net over > 2 single-CU nets: one k_mlp_slice_multi launch
-  int multi_n = 0, multi_width = 0;
-  MlpArgs multi_args[kMaxMulti];
   unsigned long long* y_granules = nullptr;   // [Bmax] TD-target hand-off (fused DDPG)
   unsigned epoch = 0;          // monotonically increasing, never reset
   int ncl = 1;                 // CUs per slice cluster in the fused path (csrc/tp3.h)
@@ -517,7 +510,11 @@ void dw_commit(oprl_learner* h, bool critic, const DwArgs& dw, int steps);
 bool alpha_rides(const oprl_learner* h);
 AlphaJob alpha_job(const oprl_learner* h, int B, int step);
 hipError_t alpha_step(const oprl_learner* h, int B, int step, float grad_scale, hipStream_t st);
-int launch(const MlpArgs& a0, int width, hipStream_t st);
+int fresh32_tables(oprl_learner* h, int which /* bit 0 critics, bit 1 actor */, hipStream_t st, bool wide_too = false);
+// net_rounds.hip: one net pass as a launch of its own (a cluster launch with a fresh tag where the shape takes one), and a
+// round of them — the n equal nets of one pass — from their finished arguments (tags and borrowed buffers are written into a[])
+int launch(const MlpArgs& a, int width, hipStream_t st);
+int launch_round(oprl_learner* h, MlpArgs* a, int n, int width, hipStream_t st);
 // learners with lazily maintained fp32 packs (fresh32)
 extern std::mutex g_lazy_mu;
 extern std::vector<oprl_learner*> g_lazy;
