@@ -64,4 +64,5 @@ class TrainingScript:
     def run(self) -> None:
         run_training(make_algo=self.make_algo, make_env=self.make_env, make_replay_buffer=self.make_replay_buffer,
                      make_logger=self.make_logger, config=self.config, seeds=self.args.seeds,
-                     start_seed=self.args.start_seed, num_envs=self.args.num_envs)
+                     start_seed=self.args.start_seed, num_envs=self.args.num_envs,
+                     open_episodes=self.args.open_episodes)

@@ -425,6 +425,17 @@ int oprl_replay_write_flush(oprl_replay* h, int32_t ep, int32_t t, const float* 
 int oprl_replay_write_block(oprl_replay* h, int32_t ep, int32_t t0, int32_t n, const float* rows_host,
                             int32_t row_stride, void* stream);
 int oprl_replay_flush(oprl_replay* h, void* stream);
+/* One step of n <= 256 open episodes in one call and one ingest launch: record i is step t[i] of
+ * episode ep[i] — state s[i], action a[i], reward r[i], done d[i] — and s2[i] the state it led to, stored as
+ * states[ep[i], t[i] + 1], so the next state of the last stored step of a running or truncated episode is in storage.
+ * All pointers are host pointers.  On `stream`, in this order: rows the other write entry points staged
+ * (oprl_replay_flush), these records, the episode table (oprl_replay_set_lens(ep_lens_host, episodes_counter)) and, on a
+ * prioritized replay, the leaves.  OPRL_ERR_INVALID, with nothing staged, launched or changed, for a null pointer, n
+ * outside 1 .. 256, an ep outside [0, E), a t outside [0, L), two records with one ep, and whatever
+ * oprl_replay_set_lens refuses. */
+int oprl_replay_write_rows(oprl_replay* h, int32_t n, const int32_t* ep, const int32_t* t, const float* s,
+                           const float* a, const float* r, const float* d, const float* s2,
+                           const int32_t* ep_lens_host, int32_t episodes_counter, void* stream);
 /* Upload ep_lens[0:episodes_counter] (episodic_buffer.py:114-116); the device
  * keeps the cumulative ends for the flat-index -> (episode, step) map. */
 int oprl_replay_set_lens(oprl_replay* h, const int32_t* ep_lens_host, int32_t episodes_counter,

@@ -15,7 +15,10 @@ differently:
   ``sample`` is the gather kernel (``oprl_replay_sample``): uniform flat
   indices -> (episode, step) by binary search over cumulative episode ends ->
   one contiguous [s | s'] run + action + reward + done per sample, staged
-  through LDS and written coalesced.
+  through LDS and written coalesced;
+* several open episodes (extension): ``open_lanes(n)`` gives each of n lanes a slot of its
+  own and ``add_step_rows`` writes one step of every lane — next states included — with one library call
+  (``oprl_replay_write_rows``) and one ingest launch.
 
 Storage is zero-filled instead of ``t.empty`` so the reference's reads of
 never-written ``t+1`` slots are at least deterministic.
@@ -34,6 +37,7 @@ from oprl_amd import _capi
 from oprl_amd.buffers.protocols import ReplayBufferProtocol
 
 Transition = tuple[npt.NDArray, npt.NDArray, float, bool, npt.NDArray]
+MAX_LANES = 256      # csrc/replay_internal.h kRowsMax: the records of one oprl_replay_write_rows call
 
 
 @dataclass
@@ -52,6 +56,7 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
     _ep_pointer: int = 0
     _number_transitions = 0
     _created: bool = False
+    _lanes = None                   # open_lanes: the slot of every lane's running episode (None / empty: no lanes)
 
     def create(self) -> "EpisodicReplayBuffer":
         E = self._max_episodes = self.buffer_size_transitions // self.max_episode_lenth
@@ -67,6 +72,7 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         self._handle = None
         self._lens_dirty = True
         self._sample_counter = 0
+        self._lanes = []
         self._on_gpu = dev.type == "cuda"
         if self._on_gpu:
             self._dev = dev if dev.index is not None else t.device("cuda", t.cuda.current_device())
@@ -132,6 +138,8 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         done: bool,
         episode_done: bool | None = None,
     ) -> None:
+        if self._lanes:
+            self._refuse_with_lanes("add_transition")
         e, l = self._ep_pointer, self.ep_lens[self._ep_pointer]
         if l >= self.max_episode_lenth:
             raise IndexError(f"episode slot {e} is full ({l} steps, max_episode_lenth={self.max_episode_lenth})")
@@ -175,6 +183,8 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         ``add_transition`` calls and ONE library call for the data (oprl_replay_write_block); with
         ``episode_done`` the episode is closed after the last one.  What the learner ranks of the distributed
         setup use to take in a whole actor episode (extension; the reference adds transitions one by one)."""
+        if self._lanes:
+            self._refuse_with_lanes("add_transitions")
         rows = np.ascontiguousarray(rows, dtype=np.float32)
         n, S, A = len(rows), self.state_dim, self.action_dim
         if rows.ndim != 2 or rows.shape[1] < S + A + 2:
@@ -212,9 +222,113 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         self._touch_len(self._ep_pointer)
 
     def add_episode(self, episode: list[Transition]) -> None:
+        if self._lanes:
+            self._refuse_with_lanes("add_episode")
         for s, a, r, d, _ in episode:
             self.add_transition(s, a, r, d, episode_done=d)
         self._inc_episode()
+
+    # several open episodes ---------------------------------
+    def _refuse_with_lanes(self, what: str) -> None:
+        raise RuntimeError(f"{what}: this buffer has {len(self._lanes)} open lanes (open_lanes); their episodes are "
+                           "written by add_step_rows only")
+
+    def open_lanes(self, n: int) -> None:
+        """``n`` episodes open at once, one per lane: lane i takes slot i.  From here on the buffer is written by
+        ``add_step_rows`` alone.  Needs an empty buffer; a second call with the same ``n`` does nothing."""
+        self.check_created()
+        E = self._max_episodes
+        if isinstance(n, bool) or int(n) != n or not 1 <= n <= MAX_LANES or n > E - 1:
+            raise ValueError(f"open_lanes({n!r}): expected 1 .. {min(MAX_LANES, E - 1)} (at most {MAX_LANES} lanes, and "
+                             f"one of the {E} episode slots must stay free for the lane that closes)")
+        n = int(n)
+        if self._lanes:
+            if len(self._lanes) == n:
+                return
+            raise RuntimeError(f"open_lanes({n}): {len(self._lanes)} lanes are open already")
+        if self._number_transitions > 0 or any(self.ep_lens):
+            raise RuntimeError(f"open_lanes({n}): the buffer already holds transitions")
+        self._lanes = list(range(n))
+        self._ep_pointer = n - 1
+        self.episodes_counter = n
+        self._lens_touched = True       # (the table's length changed)
+
+    def _close_lane(self, i: int, held: set[int]) -> None:
+        """Lane i's episode is over: the ring pointer moves on to the next slot no lane holds (lane i's own old slot
+        counts as held until it has its new one), that slot is evicted and becomes lane i's."""
+        E, p = self._max_episodes, self._ep_pointer
+        while True:
+            p = (p + 1) % E
+            if p not in held:
+                break
+        self._ep_pointer = p
+        self._number_transitions -= self.ep_lens[p]
+        self.ep_lens[p] = 0
+        self._touch_len(p)
+        held.discard(self._lanes[i])
+        held.add(p)
+        self._lanes[i] = p
+        self.episodes_counter = min(self.episodes_counter + 1, E)
+
+    def add_step_rows(self, states: npt.NDArray, actions: npt.NDArray, rewards: npt.NDArray, dones: npt.NDArray,
+                      next_states: npt.NDArray, episode_over: npt.NDArray) -> None:
+        """One step of every lane: row i is the next step of lane i's episode and ``next_states[i]`` the state it led
+        to, stored as ``states[slot, t + 1]`` — so the sampler finds s' behind the last stored step of a running
+        episode and behind the last step of a truncated one.  Lanes whose ``episode_over`` is set move on to a fresh
+        slot, in lane order.  ONE library call (oprl_replay_write_rows): the rows, the episode table and, on a
+        prioritized replay, the leaves reach HBM with one ingest launch."""
+        self.check_created()
+        lanes = self._lanes
+        if not lanes:
+            raise RuntimeError("add_step_rows: no lanes are open (open_lanes)")
+        N, S, A, L = len(lanes), self.state_dim, self.action_dim, self.max_episode_lenth
+        s = np.ascontiguousarray(states, dtype=np.float32)
+        a = np.ascontiguousarray(actions, dtype=np.float32)
+        s2 = np.ascontiguousarray(next_states, dtype=np.float32)
+        r = np.ascontiguousarray(rewards, dtype=np.float32).reshape(-1)
+        d = np.ascontiguousarray(dones, dtype=np.float32).reshape(-1)
+        over = np.asarray(episode_over, dtype=bool).reshape(-1)
+        if s.shape != (N, S) or s2.shape != (N, S) or a.shape != (N, A) or not len(r) == len(d) == len(over) == N:
+            raise ValueError(f"add_step_rows: expected states / next_states [{N}, {S}], actions [{N}, {A}] and {N} "
+                             f"rewards, dones and episode_over; got {s.shape}, {s2.shape}, {a.shape}, {len(r)}, "
+                             f"{len(d)}, {len(over)}")
+        eps = np.asarray(lanes, dtype=np.int32)
+        ts = np.asarray([self.ep_lens[e] for e in lanes], dtype=np.int32)
+        if int(ts.max()) >= L:
+            i = int(ts.argmax())
+            raise IndexError(f"lane {i}: episode slot {lanes[i]} is full ({int(ts[i])} steps, max_episode_lenth={L})")
+        # nothing can fail from here on
+        for e in lanes:
+            self.ep_lens[e] += 1
+        mirror = getattr(self, "_lens_np", None)       # (_touch_len for all lanes at once)
+        if mirror is None or len(mirror) != len(self.ep_lens):
+            self._lens_dirty = True
+        else:
+            mirror[eps] = ts + 1
+        self._number_transitions += N
+        if over.any():
+            held = set(lanes)
+            for i in np.flatnonzero(over):
+                self._close_lane(int(i), held)
+        if self._handle is None:        # host container only (no GPU): plain row stores
+            e_ix, t_ix = t.from_numpy(eps.astype(np.int64)), t.from_numpy(ts.astype(np.int64))
+            self._tensors["states"][e_ix, t_ix] = t.from_numpy(s)
+            self._tensors["states"][e_ix, t_ix + 1] = t.from_numpy(s2)
+            self._tensors["actions"][e_ix, t_ix] = t.from_numpy(a)
+            self._tensors["rewards"][e_ix, t_ix, 0] = t.from_numpy(r)
+            self._tensors["dones"][e_ix, t_ix, 0] = t.from_numpy(d)
+            return
+        if self._lens_dirty or getattr(self, "_lens_np", None) is None:
+            self._lens_np = np.asarray(self.ep_lens, dtype=np.int32).copy()
+            self._lens_dirty = False
+        i32, f32 = C.POINTER(C.c_int32), C.c_void_p
+        with _capi.on_device(self._dev):
+            _capi.check(self._lib.oprl_replay_write_rows(
+                self._handle, N, eps.ctypes.data_as(i32), ts.ctypes.data_as(i32), s.ctypes.data_as(f32),
+                a.ctypes.data_as(f32), r.ctypes.data_as(f32), d.ctypes.data_as(f32), s2.ctypes.data_as(f32),
+                self._lens_np.ctypes.data_as(i32), self.episodes_counter, _capi.current_stream()),
+                "oprl_replay_write_rows")
+        self._lens_touched = False
 
     # read path ------------------------------------------------------------------
     def _touch_len(self, e: int) -> None:
@@ -298,6 +412,7 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
             "ep_lens": list(self.ep_lens), "episodes_counter": self.episodes_counter,
             "ep_pointer": self._ep_pointer, "number_transitions": self._number_transitions,
             "sample_counter": self._sample_counter, "seed": self.seed,
+            "lanes": list(self._lanes or []),      # the slot of every lane's running episode (open_lanes)
         }
 
     def load_state_dict(self, sd: dict) -> None:
@@ -314,6 +429,7 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         self._number_transitions = int(sd["number_transitions"])
         self._sample_counter = int(sd["sample_counter"])
         self.seed = int(sd["seed"])
+        self._lanes = [int(e) for e in sd.get("lanes", [])]     # (absent in older checkpoints: no lanes)
         self._lens_dirty = True
 
     @property

@@ -168,8 +168,8 @@ __global__ void k_replay_ingest(const float* rows, int n, int rowlen, float* sta
   for (int i = ends_first + (int)(blockIdx.x * blockDim.x + threadIdx.x); i < ends_n; i += (int)(gridDim.x * blockDim.x))
     ends_dst[i] = ends_src[i];
 }
-constexpr int kDirectRows = 16;       // staged rows / changed table entries up to which the ingest kernel reads the pinned buffers itself
-constexpr int kDirectEnds = 2048;
+using oprl::kDirectRows;              // staged rows / changed table entries up to which the ingest kernel reads the pinned buffers itself
+using oprl::kDirectEnds;
 
 }  // namespace
 
@@ -206,6 +206,7 @@ extern "C" int oprl_replay_destroy(oprl_replay* h) {
   if (!h) return OPRL_OK;
   (void)hipDeviceSynchronize();
   oprl::prio_free(h->prio);
+  oprl::rows_free(h);
   (void)hipFree(h->ends_dev);
   for (int i = 0; i < 2; ++i) {
     (void)hipHostFree(h->stage_host[i]);
@@ -244,7 +245,7 @@ extern "C" int oprl_replay_flush(oprl_replay* h, void* stream) {
   }
   if (h->prio) {       // the sum tree of prioritized replay follows the rows and the table (replay_prio.hip)
     const float* rows = n > 0 ? (direct ? h->stage_map[c] : h->stage_dev[c]) : nullptr;
-    int rc = oprl::prio_flush(h, rows, n, e_first, e_n, st);
+    int rc = oprl::prio_flush(h, rows, n, h->rowlen, e_first, e_n, st);
     if (rc != OPRL_OK) return rc;
   }
   if (n > 0) {
@@ -257,7 +258,13 @@ extern "C" int oprl_replay_flush(oprl_replay* h, void* stream) {
       h->stage_busy[h->cur] = false;
     }
   }
+  return oprl::ends_sent(h, st);
+}
+
+namespace oprl {
+int ends_sent(oprl_replay* h, hipStream_t st) {
   if (h->ends_pending) {
+    const int ec = h->ends_cur;
     HIPC(hipEventRecord(h->ends_ev[ec], st));
     h->ends_busy[ec] = true;
     h->ends_cur ^= 1;
@@ -265,6 +272,17 @@ extern "C" int oprl_replay_flush(oprl_replay* h, void* stream) {
   }
   return OPRL_OK;
 }
+
+int check_lens(const oprl_replay* h, const int32_t* ep_lens_host, int32_t episodes_counter, const char* who) {
+  if (!h || !ep_lens_host || episodes_counter < 0 || episodes_counter > h->E) {
+    set_err("%s: invalid argument", who);
+    return OPRL_ERR_INVALID;
+  }
+  for (int i = 0; i < episodes_counter; ++i)
+    if (ep_lens_host[i] < 0 || ep_lens_host[i] > h->L) { set_err("ep_lens[%d]=%d out of range", i, ep_lens_host[i]); return OPRL_ERR_INVALID; }
+  return OPRL_OK;
+}
+}  // namespace oprl
 
 extern "C" int oprl_replay_write(oprl_replay* h, int32_t ep, int32_t t, const float* state_host,
                                  const float* action_host, float reward, float done) {
@@ -333,15 +351,11 @@ extern "C" int oprl_replay_write_block(oprl_replay* h, int32_t ep, int32_t t0, i
 
 extern "C" int oprl_replay_set_lens(oprl_replay* h, const int32_t* ep_lens_host,
                                     int32_t episodes_counter, void* stream) {
-  if (!h || !ep_lens_host || episodes_counter < 0 || episodes_counter > h->E) {
-    set_err("oprl_replay_set_lens: invalid argument");
-    return OPRL_ERR_INVALID;
-  }
   (void)stream;      // (the table goes up with the next flush — every reader flushes first — on ITS stream)
   // validate the whole table BEFORE touching the mirrors: a bad entry midway must not leave ends_last ahead of what
   // the device holds (the next valid call would then see "no difference" and never upload those entries)
-  for (int i = 0; i < episodes_counter; ++i)
-    if (ep_lens_host[i] < 0 || ep_lens_host[i] > h->L) { set_err("ep_lens[%d]=%d out of range", i, ep_lens_host[i]); return OPRL_ERR_INVALID; }
+  const int ok = oprl::check_lens(h, ep_lens_host, episodes_counter, "oprl_replay_set_lens");
+  if (ok != OPRL_OK) return ok;
   const int c = h->ends_cur;
   if (!h->ends_pending && h->ends_busy[c]) { HIPC(hipEventSynchronize(h->ends_ev[c])); h->ends_busy[c] = false; }
   long acc = 0;

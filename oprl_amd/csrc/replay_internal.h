@@ -33,11 +33,23 @@ struct PrioTree {
 
 // Keep the leaves in step with a flush: the staged rows `rows` (n_rows records of `rowlen` floats, [ep, t] as int
 // bits first; device-readable) and the episode-table entries [ends_first, ends_n) it uploaded (ends_n = 0: none).
-// Called by oprl_replay_flush after its copies, on its stream.
+// Called by oprl_replay_flush and oprl_replay_write_rows after their copies, on their stream.
 constexpr int kNstepMax = 16;       // largest n of the n-step sampler (replay_nstep.hip: one lane per (sample, step))
 
-int prio_flush(oprl_replay* h, const float* rows, int n_rows, int ends_first, int ends_n, hipStream_t st);
+int prio_flush(oprl_replay* h, const float* rows, int n_rows, int rowlen, int ends_first, int ends_n, hipStream_t st);
 void prio_free(PrioTree* p);
+
+// staged rows / changed table entries up to which an ingest kernel reads the pinned buffers itself (replay.hip,
+// replay_rows.hip); beyond them the rows are copied to device staging first
+constexpr int kDirectRows = 16;
+constexpr int kDirectEnds = 2048;
+constexpr int kRowsMax = 256;       // records of one oprl_replay_write_rows call (replay_rows.hip)
+
+// what oprl_replay_set_lens refuses, without touching the handle (`who` names the caller in the message)
+int check_lens(const oprl_replay* h, const int32_t* ep_lens_host, int32_t episodes_counter, const char* who);
+// the table range a launch or copy on `st` just took from ends_host[ends_cur]: event, buffer switch, nothing pending
+int ends_sent(oprl_replay* h, hipStream_t st);
+void rows_free(oprl_replay* h);     // the staging of oprl_replay_write_rows, if it was ever allocated
 
 }  // namespace oprl
 
@@ -66,4 +78,13 @@ struct oprl_replay {
   // n-step mode (oprl_replay_set_nstep): with nstep > 1 oprl_replay_sample gathers n-step rows
   int nstep = 1;
   double nstep_gamma = 1.0;
+  // oprl_replay_write_rows (replay_rows.hip): double-buffered pinned staging of its own for up to kRowsMax
+  // records of reclen floats, allocated by the first call
+  bool rows_ready = false;
+  int reclen = 0, rows_cur = 0;
+  float* rows_host[2] = {nullptr, nullptr};
+  float* rows_dev[2] = {nullptr, nullptr};
+  float* rows_map[2] = {nullptr, nullptr};
+  hipEvent_t rows_ev[2];
+  bool rows_ev_made[2] = {false, false}, rows_busy[2] = {false, false};
 };

@@ -306,7 +306,7 @@ int need_prio(const oprl_replay* h, const char* what) {
 
 namespace oprl {
 
-int prio_flush(oprl_replay* h, const float* rows, int n_rows, int ends_first, int ends_n, hipStream_t st) {
+int prio_flush(oprl_replay* h, const float* rows, int n_rows, int rowlen, int ends_first, int ends_n, hipStream_t st) {
   PrioTree* p = h->prio;
   // the episodes whose length may have changed: the uploaded part of the table, and those that entered or left
   // [0, episodes_counter)
@@ -323,7 +323,7 @@ int prio_flush(oprl_replay* h, const float* rows, int n_rows, int ends_first, in
   if (grid == 0) return OPRL_OK;
   FlushArgs a;
   a.leaves = p->tree; a.dirty1 = p->dirty; a.lens = p->lens; a.ends = h->ends_dev; a.p_max = p->p_max;
-  a.rows = rows; a.n_rows = n_rows; a.rowlen = h->rowlen; a.L = h->L; a.n_eps = h->n_eps; a.ep_lo = lo;
+  a.rows = rows; a.n_rows = n_rows; a.rowlen = rowlen; a.L = h->L; a.n_eps = h->n_eps; a.ep_lo = lo;
   a.row_blocks = row_blocks;
   hipLaunchKernelGGL(k_prio_flush, dim3(grid), dim3(kThreads), 0, st, a);
   HIPC(hipGetLastError());

@@ -58,7 +58,12 @@ def check_per(args: argparse.Namespace) -> bool:
 
 def parse_args() -> argparse.Namespace:
     """Flags of the single-process scripts (configs/ddpg.py ...)."""
-    return _parser("Run training", _SINGLE).parse_args()
+    parser = _parser("Run training", _SINGLE)
+    # extension: one open replay episode per environment (buffers/episodic_buffer.py open_lanes, DESIGN.md section 14)
+    parser.add_argument("--open-episodes", action="store_true",
+                        help="with --num-envs N > 1: N open episodes in the replay, every iteration's N transitions "
+                             "written at once (next states included) instead of whole episodes when they end")
+    return parser.parse_args()
 
 
 def parse_args_distrib() -> argparse.Namespace:

@@ -28,7 +28,8 @@ def set_seed(seed: int) -> None:
 
 
 def _run_training_func(make_algo, make_env, make_replay_buffer, make_logger,
-                       config: CommonParameters, seed: int, num_envs: int = 1, **trainer_kwargs) -> None:
+                       config: CommonParameters, seed: int, num_envs: int = 1, open_episodes: bool = False,
+                       **trainer_kwargs) -> None:
     set_seed(seed)
     env = make_env(seed)
     replay_buffer = make_replay_buffer()
@@ -49,7 +50,8 @@ def _run_training_func(make_algo, make_env, make_replay_buffer, make_logger,
                   seed=seed, logger=logger, **trainer_kwargs)
     if num_envs > 1:
         # N environments per iteration, one policy launch for all of them (trainers/vec_trainer.py)
-        VecTrainer(envs=[env, *[make_env(s) for s in env_seeds(seed, num_envs)[1:]]], **common).train()
+        VecTrainer(envs=[env, *[make_env(s) for s in env_seeds(seed, num_envs)[1:]]], open_episodes=open_episodes,
+                   **common).train()
         return
     BaseTrainer(env=env, **common).train()
 
@@ -69,12 +71,17 @@ def run_training(
     seeds: int = 1,
     start_seed: int = 0,
     num_envs: int = 1,
+    open_episodes: bool = False,
     **trainer_kwargs,
 ) -> None:
     if not 1 <= num_envs <= 256:
         raise ValueError(f"num_envs={num_envs}: expected 1..256 (one policy launch takes up to 256 rows)")
+    if open_episodes and num_envs == 1:
+        raise ValueError("open_episodes with num_envs=1: the one-environment loop has one open episode already; "
+                         "give num_envs > 1 or drop the flag")
     if seeds == 1:
-        _run_training_func(make_algo, make_env, make_replay_buffer, make_logger, config, 0, num_envs, **trainer_kwargs)
+        _run_training_func(make_algo, make_env, make_replay_buffer, make_logger, config, 0, num_envs, open_episodes,
+                           **trainer_kwargs)
         return
     # the seeds share ONE GPU: launches whose workgroups wait for each other inside the launch (clusters of eight, the
     # merged phase + tile launches, the whole-update launch: include/oprl_amd.h) need their workgroups co-resident, and a
@@ -84,7 +91,7 @@ def run_training(
     os.environ.setdefault("OPRL_AMD_FORM", "plain")
     ctx = get_context("spawn")   # a forked child cannot re-initialise the GPU runtime
     procs = [ctx.Process(target=_run_training_func,
-                         args=(make_algo, make_env, make_replay_buffer, make_logger, config, seed, num_envs),
+                         args=(make_algo, make_env, make_replay_buffer, make_logger, config, seed, num_envs, open_episodes),
                          kwargs=trainer_kwargs)
              for seed in range(start_seed, start_seed + seeds)]
     for i, p in enumerate(procs):

@@ -10,7 +10,11 @@ behind them in the same C call.
 Episodes.  The replay has one open episode, so the transitions of each environment are assembled on the host
 (``EpisodeAssembler``) and enter the replay as one ``add_transitions(rows, episode_done=True)`` when that environment's
 episode ends — how the learner ranks of the distributed runner take in actor episodes.  Data therefore becomes
-visible to the sampler ONE EPISODE LATE: nothing of an environment's running episode can be drawn."""
+visible to the sampler ONE EPISODE LATE: nothing of an environment's running episode can be drawn.
+
+``open_episodes=True`` lifts that: the replay opens one episode per environment
+(``replay_buffer.open_lanes(N)``) and every iteration's N transitions go in with ONE ``add_step_rows`` call, next states
+included, so the learner trains from the first iteration whose end finds a batch in the buffer."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -58,6 +62,7 @@ class EpisodeAssembler:
 class VecTrainer(BaseTrainer):
     envs: list[EnvProtocol]
     env: EnvProtocol | None = None      # (BaseTrainer's single environment: unused here, envs[0] when not given)
+    open_episodes: bool = False         # one open replay episode per environment instead of the host-side assembler
 
     def __post_init__(self) -> None:
         if not self.envs:
@@ -73,10 +78,12 @@ class VecTrainer(BaseTrainer):
         n = len(self.envs)
         obs = np.stack([np.asarray(env.reset()[0], dtype=np.float32) for env in self.envs])
         assembler = EpisodeAssembler(n)
+        if self.open_episodes:
+            self.replay_buffer.open_lanes(n)
         steps = 0
         while steps < self.num_steps:
             prev = steps
-            obs = self._collect_rows(prev, obs, assembler)
+            obs = self._collect_open(prev, obs) if self.open_episodes else self._collect_rows(prev, obs, assembler)
             steps += n
             if len(self.replay_buffer) < self.batch_size:
                 continue
@@ -98,6 +105,28 @@ class VecTrainer(BaseTrainer):
                 self.replay_buffer.add_transitions(rows, episode_done=True)
                 o2, _ = env.reset()
             nxt[i] = o2
+        return nxt
+
+    def _collect_open(self, steps: int, obs: np.ndarray) -> np.ndarray:
+        """One step of every environment and ONE ``add_step_rows`` for all of them.  s' is the observation the
+        environment returned — the terminal or truncation observation where an episode ended; the observations handed
+        back are the reset ones there."""
+        if steps < self.start_steps:
+            actions = [env.sample_action() for env in self.envs]
+        else:
+            actions = self.algo.actor.explore_rows(obs)
+        n = len(self.envs)
+        acts = np.stack([np.asarray(a, dtype=np.float32).reshape(-1) for a in actions])
+        s2, nxt = np.empty_like(obs), np.empty_like(obs)
+        rewards, dones, over = np.empty(n, np.float32), np.empty(n, np.float32), np.zeros(n, bool)
+        for i, env in enumerate(self.envs):
+            o2, reward, terminated, truncated, _ = env.step(actions[i])
+            s2[i], rewards[i], dones[i] = o2, reward, float(terminated)
+            over[i] = bool(terminated or truncated)
+            if over[i]:
+                o2, _ = env.reset()
+            nxt[i] = o2
+        self.replay_buffer.add_step_rows(obs, acts, rewards, dones, s2, over)
         return nxt
 
     def _due(self, prev: int, cur: int) -> dict[str, int | None]:
