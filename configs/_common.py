@@ -4,6 +4,7 @@ line, importing everything through the ``oprl`` alias package exactly as a refer
 from __future__ import annotations
 
 import sys
+from argparse import Namespace
 from dataclasses import dataclass, fields
 from pathlib import Path
 from typing import Callable
@@ -31,10 +32,16 @@ class TrainingScript:
     algo_name: str
     estimate_q_every: int
     log_every: int
+    extra_flags: tuple = ()                  # the script's own flags, (flag, type, default, help) each (parse_args)
+    algo_kwargs: Callable[[Namespace], dict] | None = None   # ... and the algorithm's fields they set
+    takes_per: bool = True                   # False: the algorithm applies no importance weights, --per is refused
 
     def __post_init__(self) -> None:
-        self.args = parse_args()
+        self.args = parse_args(self.extra_flags)
         self.per = check_per(self.args)      # --per: prioritized replay and an algorithm that applies its weights
+        if self.per and not self.takes_per:
+            raise ValueError(f"--per: {self.algo_name} does not train from prioritized replay (its loss takes no "
+                             "importance weights yet)")
         probe = self.make_env(seed=0)
         self.state_dim = int(probe.observation_space.shape[0])
         self.action_dim = int(probe.action_space.shape[0])
@@ -49,6 +56,7 @@ class TrainingScript:
     def make_algo(self, logger):
         return self.algo_cls(logger=logger, state_dim=self.state_dim, action_dim=self.action_dim,
                              device=self.args.device, precision=self.args.precision,
+                             **(self.algo_kwargs(self.args) if self.algo_kwargs is not None else {}),
                              **({"prioritized": True} if self.per else {})).create()
 
     def make_replay_buffer(self):

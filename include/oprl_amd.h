@@ -45,8 +45,12 @@ typedef enum oprl_status {
 /* OPRL_REDQ: an ensemble of n_critics scalar critics (<= OPRL_MAX_CRITICS) with SAC's tanh-Gaussian actor; the TD
  * target takes the minimum over hp.n_min target critics drawn afresh for every update (oprl_redq_subset), the critic
  * targets move on every update and the actor (+ temperature) steps on every hp.policy_freq-th (Chen et al., ICLR 2021;
- * DESIGN.md "REDQ").  F32 only, no gradient export, never a fused form. */
-typedef enum oprl_algo { OPRL_DDPG = 0, OPRL_TD3 = 1, OPRL_SAC = 2, OPRL_TQC = 3, OPRL_REDQ = 4 } oprl_algo;
+ * DESIGN.md "REDQ").  F32 only, no gradient export, never a fused form.
+ * OPRL_D4PG: DDPG with ONE categorical critic (Bellemare et al. 2017; Barth-Maron et al. 2018): the critic's
+ * N = dims[n_layers] outputs (2 .. 48) are logits over the atoms z_i = hp.v_min + i (hp.v_max - hp.v_min) / (N - 1); the
+ * critic loss is the cross-entropy against the projected target distribution, the actor ascends Q = sum_j z_j p_j.  F32
+ * only, the generic launch sequence only, no gradient export, no group membership, no importance weights. */
+typedef enum oprl_algo { OPRL_DDPG = 0, OPRL_TD3 = 1, OPRL_SAC = 2, OPRL_TQC = 3, OPRL_REDQ = 4, OPRL_D4PG = 5 } oprl_algo;
 
 /* Arithmetic mode of the MLP GEMMs.
  *   F32  = exact-fp32 MFMA (v_mfma_f32_16x16x4_f32), the parity mode: Q-values and gradients within
@@ -120,6 +124,7 @@ typedef struct oprl_hparams {
   int32_t tune_alpha;                            /* SAC (sac.py:65-70); TQC always 1 */
   int32_t n_quantiles, top_quantiles_to_drop;    /* TQC (tqc.py:71-73) */
   int32_t n_min;                                 /* REDQ: target critics in the minimum (M, 1..n_critics) */
+  double v_min, v_max;                           /* D4PG: the first and the last atom (v_max > v_min); read for OPRL_D4PG only */
 } oprl_hparams;
 
 typedef struct oprl_learner_config {
@@ -128,7 +133,7 @@ typedef struct oprl_learner_config {
   int32_t precision;        /* oprl_precision */
   int32_t state_dim, action_dim;
   int32_t max_batch;        /* workspace is sized for this many rows */
-  int32_t n_critics;        /* 1 DDPG, 2 TD3/SAC, n_nets TQC, the ensemble's size REDQ */
+  int32_t n_critics;        /* 1 DDPG / D4PG, 2 TD3/SAC, n_nets TQC, the ensemble's size REDQ */
   int32_t no_fuse;          /* 1: always use the generic per-net launch sequence (DDPG
                                otherwise runs the fused two-kernel path, csrc/fused_ddpg.hip) */
   int32_t export_grads;     /* 1: update() stops before Adam and leaves grads in
@@ -493,14 +498,25 @@ int oprl_replay_prio_read(oprl_replay* h, float* tree_out, int64_t n, int64_t* n
 /* Restore leaves[E·L] (device; the entries of dead slots are taken as 0) and p_max (> 0); the nodes are rebuilt. */
 int oprl_replay_prio_load(oprl_replay* h, const float* leaves, float p_max, void* stream);
 
+/* ---- D4PG's categorical critic seed, stand-alone ---------------------------------------------------
+ * k_c51_critic_seed (csrc/c51_seed.hip) on caller-supplied device rows, as the learner's critic step runs it: target
+ * logits zt[B][ld] and online logits z[B][ld] over N atoms from v_min to v_max, r[B], d[B].  Out: seed[B][ld] =
+ * (softmax(z) - m) / B with the pad columns N .. ld - 1 written as zero, m[B][ld] the target distribution projected onto
+ * the atoms (Tz_i = clamp(r + ((1 - d) gamma) z_i, v_min, v_max); pad columns zero) and loss[B] = -sum_j m_j log
+ * softmax(z)_j; m_out and loss_out may be NULL.  Nothing is written for rows >= B.  OPRL_ERR_INVALID: a null pointer,
+ * N outside 2 .. 48, ld outside N .. 64, B < 1, v_max <= v_min.  Tests reach the kernel's corners through it. */
+int oprl_c51_seed(const float* zt, const float* z, const float* r, const float* d, double gamma, double v_min,
+                  double v_max, int32_t N, int32_t B, int32_t ld, float* seed_out, float* m_out, float* loss_out,
+                  void* stream);
+
 /* ---- training from prioritized replay ("Training from it") -----------------------------------------
  * One reference-semantics update whose critic loss is (1/B) sum_b w[b] (Q(s,a) - y)^2 per critic, w[B] on the device;
  * the actor and temperature losses are not weighted (Schaul et al.).  td_abs_out[B] (device) receives
  * (sum_j |Q_j(s,a) - y|) / n_critics.  With w = 1 everywhere the update is oprl_learner_update's on a no_fuse learner,
  * bit for bit.  The critic step runs the generic launch sequence as forward | k_td_weighted_seed | backward, so:
  * OPRL_ERR_STATE for a learner whose fused form is on (create it with no_fuse), for export_grads / data-parallel
- * learners and members of a group; OPRL_ERR_INVALID for TQC (its quantile-Huber seed takes no per-row weight yet) and
- * for a precision other than OPRL_PREC_F32.  A refused call changes nothing. */
+ * learners and members of a group; OPRL_ERR_INVALID for TQC (its quantile-Huber seed takes no per-row weight yet), for
+ * D4PG (its cross-entropy seed takes none either) and for a precision other than OPRL_PREC_F32.  A refused call changes nothing. */
 int oprl_learner_update_weighted(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
                                  const float* s2, const float* w, int32_t B, const float* noise0, const float* noise1,
                                  float* td_abs_out, void* stream);

@@ -14,7 +14,7 @@ OPRL_ABI_VERSION = 4
 OPRL_MAX_LAYERS = 4
 OPRL_MAX_CRITICS = 10
 OPRL_ACT_ROWS_MAX = 256      # rows of one oprl_learner_act_rows / oprl_mlp_act_rows launch
-ALGO = {"ddpg": 0, "td3": 1, "sac": 2, "tqc": 3, "redq": 4}
+ALGO = {"ddpg": 0, "td3": 1, "sac": 2, "tqc": 3, "redq": 4, "d4pg": 5}
 PRECISION = {"f32": 0, "bf16": 1, "x2": 2}
 ACT_NONE, ACT_TANH, ACT_GAUSS_MEAN = 0, 1, 4
 
@@ -47,6 +47,7 @@ class OprlHparams(C.Structure):
         ("tune_alpha", C.c_int32),
         ("n_quantiles", C.c_int32), ("top_quantiles_to_drop", C.c_int32),
         ("n_min", C.c_int32),
+        ("v_min", C.c_double), ("v_max", C.c_double),
     ]
 
 
@@ -144,6 +145,7 @@ SIGNATURES = {
     "oprl_replay_prio_load": (C.c_int, [_P, _P, _F, _P]),
     "oprl_learner_update_weighted": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "oprl_learner_step_n_prio": (C.c_int, [_P, _P, _I32, _I32, _U64, _D, _D, _P]),
+    "oprl_c51_seed": (C.c_int, [_P, _P, _P, _P, _D, _D, _D, _I32, _I32, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,9 @@
+"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG`` is also served from here, resolved on
+first use so that importing the package stays free of torch."""
+
+
+def __getattr__(name: str):
+    if name == "D4PG":
+        from oprl_amd.algos.d4pg import D4PG
+        return D4PG
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

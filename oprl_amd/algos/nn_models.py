@@ -328,6 +328,36 @@ class Critic(nn.Module):
         return _forward_sa(self.q1, states, actions)
 
 
+class CategoricalCritic(nn.Module):
+    """D4PG's distributional critic: MLP(S + A -> 256 -> 256 -> n_atoms) whose outputs are LOGITS over the fixed atoms
+    ``z_i = v_min + i (v_max - v_min) / (n_atoms - 1)`` (Bellemare et al. 2017).  ``forward`` returns the logits
+    [B, n_atoms]; ``Q1`` the expectation sum_i z_i softmax(logits)_i as [B, 1]."""
+
+    def __init__(
+        self,
+        state_dim: int,
+        action_dim: int,
+        n_atoms: int = 41,
+        v_min: float = -150.0,
+        v_max: float = 150.0,
+        hidden_units: tuple[int, ...] = (256, 256),
+        hidden_activation: nn.Module = nn.ReLU(inplace=True),
+    ) -> None:
+        super().__init__()
+        self.q1 = MLP(state_dim + action_dim, n_atoms, hidden_units, hidden_activation)
+        self.n_atoms, self.v_min, self.v_max = int(n_atoms), float(v_min), float(v_max)
+
+    def atoms(self, like: t.Tensor) -> t.Tensor:
+        return t.linspace(self.v_min, self.v_max, self.n_atoms, dtype=like.dtype, device=like.device)
+
+    def forward(self, states: t.Tensor, actions: t.Tensor) -> t.Tensor:
+        return _forward_sa(self.q1, states, actions)
+
+    def Q1(self, states: t.Tensor, actions: t.Tensor) -> t.Tensor:
+        logits = self.forward(states, actions)
+        return (t.softmax(logits, dim=-1) * self.atoms(logits)).sum(dim=-1, keepdim=True)
+
+
 class DoubleCritic(nn.Module):
     def __init__(
         self,

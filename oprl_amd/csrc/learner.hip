@@ -8,6 +8,7 @@
 //   SAC   algos/sac.py:75-155       TQC  algos/tqc.py:116-189
 #include "learner_internal.h"
 #include "per_seed.h"
+#include "c51_seed.h"
 #include "philox.h"
 
 namespace oprl {
@@ -953,10 +954,57 @@ int weighted_critic_step(oprl_learner* h, const StepRows& rows, int B, int n_min
   });
 }
 
+// D4PG's seed operands: the atoms, the row count and the logits / seed rows of this learner (c51_seed.h)
+C51Args c51_args(const oprl_learner* h, int B) {
+  const oprl_net& q = h->cfg.critics[0];
+  C51Args a;
+  memset((void*)&a, 0, sizeof a);
+  a.z = h->c51_logits;
+  a.seed = h->c51_seed;
+  a.gamma = (float)h->cfg.hp.gamma; a.v_min = (float)h->cfg.hp.v_min; a.v_max = (float)h->cfg.hp.v_max;
+  a.inv_B = 1.0f / (float)B;
+  a.N = q.dims[q.n_layers]; a.B = B; a.ld = h->ldq;
+  a.n_slices = (B + kR - 1) / kR;
+  return a;
+}
+
+// the critic's backward-only launch from the seed rows k_c51_*_seed left (SEED_PTR, ld0 = ldq)
+MlpArgs c51_backward_args(oprl_learner* h, int B, bool store_dy) {
+  MlpArgs f = base_args(h, h->cfg.critics[0], false, B);
+  f.do_bwd = 1;
+  with_store(f, h->ws_critic[0], true, store_dy);
+  f.seed_mode = SEED_PTR;
+  f.seed.p0 = h->c51_seed; f.seed.ld0 = h->ldq;
+  return f;
+}
+
+// Step 3 of the generic critic phase for D4PG's categorical critic, in weighted_critic_step's form: the
+// critic's forward with the activations stored and its logits into c51_logits, k_c51_critic_seed (c51_seed.hip) on those
+// logits and the target critic's (qn), the critic's backward from the stored activations with the seed rows read from
+// memory.  Step 4's dW + Adam reads what it always reads.
+int c51_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st) {
+  if (h->c51_logits == nullptr || h->c51_seed == nullptr) { set_err("internal: categorical critic step without its buffers"); return OPRL_ERR_STATE; }
+  RC(for_each_net(h, 1, h->w_critic, st, [&](int j) {
+    MlpArgs f = critic_sa_args(h, j, rows.cur.s, rows.cur.a, B, false);
+    f.out = h->c51_logits; f.ldo = h->ldq;
+    return f;
+  }));
+  C51Args t = c51_args(h, B);
+  t.zt = h->qn;
+  t.r = rows.cur.r; t.d = rows.cur.d;
+  t.q_out = h->qdbg; t.y_out = h->ydbg;
+  t.partials = h->part_c;
+  prof_begin(3, st);
+  hipError_t e = launch_c51_critic_seed(t, st);
+  prof_end(st);
+  HIPC(e);
+  return for_each_net(h, 1, h->w_critic, st, [&](int) { return c51_backward_args(h, B, true); });
+}
+
 int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
   const float *s = rows.cur.s, *a = rows.cur.a, *r = rows.cur.r, *d = rows.cur.d, *s2 = rows.cur.s2;
-  if (rows.w != nullptr && (use_fused(h, B) || c.algo == OPRL_TQC)) {      // (the entry point refuses both)
+  if (rows.w != nullptr && (use_fused(h, B) || c.algo == OPRL_TQC || c.algo == OPRL_D4PG)) {      // (the entry point refuses all three)
     set_err("internal: importance weights reached a launch form that does not apply them");
     return OPRL_ERR_STATE;
   }
@@ -1016,12 +1064,12 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
   const int n_slices = (B + kR - 1) / kR;
   // 1. next action
   {
-    const bool use_target_actor = (algo == OPRL_DDPG || algo == OPRL_TD3);
+    const bool use_target_actor = (algo == OPRL_DDPG || algo == OPRL_TD3 || algo == OPRL_D4PG);
     MlpArgs f = base_args(h, c.actor, use_target_actor, B);
     f.do_fwd = 1;
     f.x0 = s2; f.k0 = S;
     f.out = h->a2; f.ldo = A;
-    if (algo == OPRL_DDPG) f.out_act = ACT_TANH;
+    if (algo == OPRL_DDPG || algo == OPRL_D4PG) f.out_act = ACT_TANH;
     else if (algo == OPRL_TD3) { f.out_act = ACT_TANH_SMOOTH; seed_rng(f, h, noise0, 1); }
     else { f.out_act = ACT_GAUSS; f.logp = h->logp2; seed_rng(f, h, noise0, 1); }
     // TQC: this launch is 64 workgroups on 256 CUs, and the online critics' first two layers on (s, a) — the
@@ -1104,6 +1152,10 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
   h->rider_done = false;
   if (rows.w != nullptr) {         // importance weights: the same step as three launches per grouping, then step 4
     RC(weighted_critic_step(h, rows, B, n_min, st));
+    return dw_step(h, true, B, st);
+  }
+  if (algo == OPRL_D4PG) {         // the categorical critic: forward | k_c51_critic_seed | backward, then step 4
+    RC(c51_critic_step(h, rows, B, st));
     return dw_step(h, true, B, st);
   }
   if (algo == OPRL_TQC && !h->sw.no_af_ride && !c.export_grads && actor_due(h)) {
@@ -1195,7 +1247,7 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
   const int S = h->S, A = h->A, nc = h->nc;
   const int algo = c.algo;
   const bool gauss = gauss_actor(h);
-  const int n_q = (algo == OPRL_TD3 || algo == OPRL_DDPG) ? 1 : nc;   // TD3 uses Q1 only
+  const int n_q = (algo == OPRL_TD3 || algo == OPRL_DDPG || algo == OPRL_D4PG) ? 1 : nc;   // TD3 uses Q1 only
   // (the offers to the riding launches below never outlive this update: after an error return the next must not find one)
   struct ClearOffers {
     oprl_learner* h;
@@ -1246,6 +1298,29 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
       f.seed.cval = 1.0f / (float)B;
       f.dact_col0 = S; f.dact_cols = A; f.dact = h->da + (size_t)j * h->Bmax * A; f.lddact = A;
       if (j == 0) f.partials = h->part_a;
+      return f;
+    }));
+  } else if (algo == OPRL_D4PG) {
+    // the categorical critic on (s, pi): its logits, then the seed -(1/B) p_j (z_j - Q) of the loss -(1/B) sum_b Q_b
+    // (k_c51_actor_seed), then the backward that leaves the action gradients
+    if (h->c51_logits == nullptr || h->c51_seed == nullptr) { set_err("internal: categorical actor step without its buffers"); return OPRL_ERR_STATE; }
+    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
+      MlpArgs f = base_args(h, c.critics[0], false, B);
+      f.do_fwd = 1;
+      f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
+      with_store(f, h->ws_critic[0], true, false);
+      f.out = h->c51_logits; f.ldo = h->ldq;
+      return f;
+    }));
+    C51Args t = c51_args(h, B);
+    t.partials = h->part_a;
+    prof_begin(3, st);
+    hipError_t e = launch_c51_actor_seed(t, st);
+    prof_end(st);
+    HIPC(e);
+    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
+      MlpArgs f = c51_backward_args(h, B, false);
+      f.dact_col0 = S; f.dact_cols = A; f.dact = h->da; f.lddact = A;
       return f;
     }));
   } else {

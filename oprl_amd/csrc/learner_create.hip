@@ -1,6 +1,7 @@
 // learner_create.hip — oprl_learner_create / destroy / sync_params and the pack helpers of the C-ABI: the workspace
 // pool, the uncached areas, the tile and repack tables.  Split from learner.hip (round 4).
 #include "learner_internal.h"
+#include "c51_seed.h"
 
 namespace oprl_host {
 // the one place the learner's switches are read (learner_internal.h Switches)
@@ -37,9 +38,9 @@ Switches read_switches() {
 extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner** out) {
   if (!cfg || !out) { set_err("oprl_learner_create: null argument"); return OPRL_ERR_INVALID; }
   if (cfg->abi_version != OPRL_ABI_VERSION) { set_err("ABI version mismatch: caller %d, library %d", cfg->abi_version, OPRL_ABI_VERSION); return OPRL_ERR_INVALID; }
-  if (cfg->algo < OPRL_DDPG || cfg->algo > OPRL_REDQ) { set_err("unknown algo %d", cfg->algo); return OPRL_ERR_INVALID; }
+  if (cfg->algo < OPRL_DDPG || cfg->algo > OPRL_D4PG) { set_err("unknown algo %d", cfg->algo); return OPRL_ERR_INVALID; }
   if (cfg->precision != OPRL_PREC_F32 && cfg->precision != OPRL_PREC_BF16 && cfg->precision != OPRL_PREC_X2) { set_err("precision %d unknown", cfg->precision); return OPRL_ERR_INVALID; }
-  const int nc_expect = cfg->algo == OPRL_DDPG ? 1 : ((cfg->algo == OPRL_TQC || cfg->algo == OPRL_REDQ) ? cfg->n_critics : 2);
+  const int nc_expect = (cfg->algo == OPRL_DDPG || cfg->algo == OPRL_D4PG) ? 1 : ((cfg->algo == OPRL_TQC || cfg->algo == OPRL_REDQ) ? cfg->n_critics : 2);
   if (cfg->n_critics != nc_expect || cfg->n_critics < 1 || cfg->n_critics > OPRL_MAX_CRITICS) {
     set_err("n_critics=%d invalid for algo %d", cfg->n_critics, cfg->algo);
     return OPRL_ERR_INVALID;
@@ -55,6 +56,20 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
       if (cfg->critics[j].n_layers < 1 || cfg->critics[j].n_layers > OPRL_MAX_LAYERS || cfg->critics[j].dims[cfg->critics[j].n_layers] != 1) {
         set_err("REDQ: critic %d is not a scalar critic", j); return OPRL_ERR_INVALID;
       }
+  }
+  if (cfg->algo == OPRL_D4PG) {
+    // (the generic launch sequence in exact fp32 only, this rank's own Adam step only: DESIGN.md §15)
+    const oprl_net& q = cfg->critics[0];
+    if (q.n_layers < 1 || q.n_layers > OPRL_MAX_LAYERS) { set_err("D4PG: the critic has %d layers (1..%d)", q.n_layers, OPRL_MAX_LAYERS); return OPRL_ERR_INVALID; }
+    const int N = q.dims[q.n_layers];
+    if (N < 2 || N > kC51MaxAtoms) {
+      set_err("D4PG: %d atoms outside 2..%d (the critic's output is one of the engine's narrow outputs, at most kNarrowMax = %d columns)", N, kC51MaxAtoms, kNarrowMax);
+      return OPRL_ERR_INVALID;
+    }
+    // (compared as the kernels see them: floats)
+    if (!((float)cfg->hp.v_max > (float)cfg->hp.v_min)) { set_err("D4PG: v_max=%g is not above v_min=%g", cfg->hp.v_max, cfg->hp.v_min); return OPRL_ERR_INVALID; }
+    if (cfg->precision != OPRL_PREC_F32) { set_err("D4PG: precision %d unsupported (f32 only)", cfg->precision); return OPRL_ERR_INVALID; }
+    if (cfg->export_grads) { set_err("D4PG: export_grads (data-parallel) unsupported"); return OPRL_ERR_INVALID; }
   }
   auto* h = new oprl_learner();
   h->cfg = *cfg;
@@ -116,8 +131,8 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
              cfg->critics[0].n_layers == 3;
 
   const int B = h->Bmax, S = h->S, A = h->A, nc = h->nc;
-  // scalar critics: q' is read with stride 1 by the TD seed; TQC: [B][ldq] quantile rows
-  h->ldq = cfg->algo == OPRL_TQC ? round_up(cfg->critics[0].dims[cfg->critics[0].n_layers], 4) : 1;
+  // scalar critics: q' is read with stride 1 by the TD seed; TQC: [B][ldq] quantile rows; D4PG: [B][ldq] rows of logits
+  h->ldq = (cfg->algo == OPRL_TQC || cfg->algo == OPRL_D4PG) ? round_up(cfg->critics[0].dims[cfg->critics[0].n_layers], 4) : 1;
   const int n_slices = (B + kR - 1) / kR;
   size_t floats = net_ws_floats(cfg->actor, B);
   for (int j = 0; j < nc; ++j) floats += net_ws_floats(cfg->critics[j], B);
@@ -126,6 +141,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   const int n_part_a = cfg->algo == OPRL_REDQ ? nc : 1;   // (REDQ: every critic's actor-step sums, the ensemble mean)
   floats += (size_t)(nc + n_part_a) * n_slices * 4 + 16;
   floats += (size_t)B * (2 * S + A + 2);
+  if (cfg->algo == OPRL_D4PG) floats += 2 * ((size_t)B * h->ldq + 64);     // (the online logits and their seed rows)
   floats += 64 * 32 + 8 * (size_t)B + 512;      // (granule arrays: y, q1, q2, the twin's seeds; 256 gate flags)
   const int Bm = B < 256 ? B : 256;             // merged phase 2 serves one 256-row chunk
   const bool merge2_bufs = h->fused && cfg->algo != OPRL_SAC && A <= kDuLd;
@@ -195,6 +211,10 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
     h->chain_b16 = p.take<float>(4 * kMaxLayers * 256);
     h->critic_b16 = h->chain_b16 + 2 * kMaxLayers * 256;
     h->w3buf1 = p.take<float>(16 * 256);
+  }
+  if (cfg->algo == OPRL_D4PG) {
+    h->c51_logits = p.take<float>((size_t)B * h->ldq);
+    h->c51_seed = p.take<float>((size_t)B * h->ldq);
   }
   h->bs = p.take<float>((size_t)B * S);
   h->ba = p.take<float>((size_t)B * A);

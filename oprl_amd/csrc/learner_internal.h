@@ -365,6 +365,9 @@ struct oprl_learner {
   // the weighted seeds [nc][Bmax], and step_n_prio's weights, |TD| and slots [Bmax] each; null on every other learner
   float *per_seed = nullptr, *per_w = nullptr, *per_td = nullptr;
   int* per_slots = nullptr;
+  // D4PG (c51_seed.hip): the online critic's logits [Bmax][ldq] between its forward-only and backward-only launches, and
+  // the seed rows SEED_PTR reads; in the pool, null on every other learner
+  float *c51_logits = nullptr, *c51_seed = nullptr;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)

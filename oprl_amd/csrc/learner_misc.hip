@@ -1,6 +1,7 @@
 // learner_misc.hip — scalars, counters, traces and debug views of a learner, and the stand-alone building blocks of
 // the C-ABI (oprl_mlp_forward / act / backward, oprl_adam_step, oprl_polyak).  Split from learner.hip (round 4).
 #include "learner_internal.h"
+#include "c51_seed.h"
 
 extern "C" int oprl_learner_read_scalars(oprl_learner* h, float* out_host, int32_t n, void* stream) {
   if (!h || !out_host || n < 1) { set_err("oprl_learner_read_scalars: invalid argument"); return OPRL_ERR_INVALID; }
@@ -163,6 +164,27 @@ extern "C" int oprl_learner_debug_form(oprl_learner* h, int32_t B, int32_t* out)
   out[9] = h->xcd_local ? 1 : 0;
   if (h->cfg.export_grads) out[11] = form_code(fused_form(h, B, true));
   out[12] = f.rt2;
+  return OPRL_OK;
+}
+
+// D4PG's critic seed on the caller's rows (include/oprl_amd.h): the kernel and the launch checks of the learner's critic step
+extern "C" int oprl_c51_seed(const float* zt, const float* z, const float* r, const float* d, double gamma, double v_min,
+                             double v_max, int32_t N, int32_t B, int32_t ld, float* seed_out, float* m_out, float* loss_out,
+                             void* stream) {
+  if (!zt || !z || !r || !d || !seed_out) { set_err("oprl_c51_seed: null argument"); return OPRL_ERR_INVALID; }
+  if (N < 2 || N > kC51MaxAtoms || ld < N || ld > 64 || B < 1 || !((float)v_max > (float)v_min)) {
+    set_err("oprl_c51_seed: need 2 <= N <= %d atoms (N=%d), N <= ld <= 64 (ld=%d), B >= 1 (B=%d) and v_max > v_min (%g, %g)",
+            kC51MaxAtoms, N, ld, B, v_max, v_min);
+    return OPRL_ERR_INVALID;
+  }
+  C51Args a;
+  memset((void*)&a, 0, sizeof a);
+  a.z = z; a.zt = zt; a.r = r; a.d = d;
+  a.gamma = (float)gamma; a.v_min = (float)v_min; a.v_max = (float)v_max;
+  a.inv_B = 1.0f / (float)B;
+  a.N = N; a.B = B; a.ld = ld;
+  a.seed = seed_out; a.m = m_out; a.loss_row = loss_out;
+  HIPC(launch_c51_critic_seed(a, (hipStream_t)stream));
   return OPRL_OK;
 }
 

@@ -13,6 +13,10 @@ int per_check(const oprl_learner* h, const char* who) {
     set_err("%s: TQC's quantile-Huber seed takes no per-row weight yet (a follow-up); DDPG, TD3, SAC and REDQ train from prioritized replay", who);
     return OPRL_ERR_INVALID;
   }
+  if (h->cfg.algo == OPRL_D4PG) {
+    set_err("%s: D4PG's cross-entropy seed takes no per-row weight yet (a follow-up: the per-row cross-entropy as priority)", who);
+    return OPRL_ERR_INVALID;
+  }
   if (h->bf16 || h->x2) {
     set_err("%s: prioritized training runs the exact-fp32 generic launch sequence only (precision f32)", who);
     return OPRL_ERR_INVALID;

@@ -56,9 +56,10 @@ def check_per(args: argparse.Namespace) -> bool:
     return True
 
 
-def parse_args() -> argparse.Namespace:
-    """Flags of the single-process scripts (configs/ddpg.py ...)."""
-    parser = _parser("Run training", _SINGLE)
+def parse_args(extra=()) -> argparse.Namespace:
+    """Flags of the single-process scripts (configs/ddpg.py ...).  ``extra``: a script's own flags, as (flag, type,
+    default, help) tuples (configs/d4pg.py: the atoms of its critic)."""
+    parser = _parser("Run training", (*_SINGLE, *extra))
     # extension: one open replay episode per environment (buffers/episodic_buffer.py open_lanes, DESIGN.md section 14)
     parser.add_argument("--open-episodes", action="store_true",
                         help="with --num-envs N > 1: N open episodes in the replay, every iteration's N transitions "
