@@ -6,6 +6,8 @@
  *
  *   oprl_learner_*   AlgorithmProtocol.update()           algos/protocols.py:21-41
  *                    DDPG/TD3/SAC/TQC.update()            algos/ddpg.py:61, td3.py:71, sac.py:75, tqc.py:116
+ *   oprl_learner_set_bc / read_bc, oprl_bc_seed   no counterpart: TD3+BC's actor loss as a mode of a TD3 learner
+ *                    (Fujimoto & Gu 2021), for training from a fixed dataset
  *   oprl_replay_*    ReplayBufferProtocol                 buffers/protocols.py:6-26
  *                    EpisodicReplayBuffer.{add_transition,sample}  buffers/episodic_buffer.py:81-133
  *   oprl_mlp_*       MLP / Critic / policies forward      algos/nn_models.py:27-194
@@ -528,6 +530,32 @@ int oprl_learner_update_weighted(oprl_learner* h, const float* s, const float* a
  * beta_steps <= 0 (OPRL_ERR_INVALID). */
 int oprl_learner_step_n_prio(oprl_learner* h, oprl_replay* replay, int32_t K, int32_t B, uint64_t seed, double beta0,
                              double beta_steps, void* stream);
+
+/* ---- TD3 + BC: a behaviour-cloning term in a TD3 learner's actor loss (Fujimoto & Gu 2021) ----------
+ * A MODE of a TD3 learner, not an algorithm of its own: with alpha > 0 every later actor step minimises
+ *   -lambda (1/B) sum_b Q1(s_b, pi(s_b)) + (1/(B A)) sum_{b,k} (pi(s_b)_k - a_bk)^2,  lambda = alpha / ((1/B) sum_b |Q1(s_b, pi(s_b))|),
+ * lambda a constant for the gradient and with NO epsilon in its denominator (the authors' code has none); a is the
+ * minibatch's action.  The critic step, the target smoothing noise, policy_freq and the Polyak steps are TD3's, through
+ * every entry point (update, update_weighted, step_n, step_n_prio).  alpha = 0 turns the mode off: TD3 again, bit for
+ * bit.  The first call with alpha > 0 allocates the mode's rows; no update allocates.  The actor step runs the generic
+ * launch sequence as actor forward | critic 0 forward | k_bc_seed | critic 0 backward (SEED_PTR) | k_bc_mix | actor
+ * backward | dW + Adam + Polyak (csrc/bc_seed.hip), so: OPRL_ERR_INVALID for any algorithm but TD3 (DDPG shares the
+ * branch: a follow-up), for a precision other than OPRL_PREC_F32, for a negative or non-finite alpha; OPRL_ERR_STATE for
+ * a learner whose fused form is on (create it with no_fuse), for export_grads / data-parallel learners and members of a
+ * group; oprl_group_create refuses a learner with the mode on.  A refused call changes nothing. */
+int oprl_learner_set_bc(oprl_learner* h, double alpha);
+/* Of the last actor step with the mode on: out_host[0] = lambda, [1] = (1/B) sum_b |Q1(s_b, pi(s_b))|, [2] =
+ * (1/(B A)) sum (pi - a)^2 (k_bc_mix's partial sums added in slice order), [3] = 0 (spare).  Synchronises `stream`.
+ * OPRL_ERR_STATE for a learner on which the mode was never on. */
+int oprl_learner_read_bc(oprl_learner* h, float out_host[4], void* stream);
+/* k_bc_seed and k_bc_mix on caller-supplied device rows, as the learner's actor step runs them: q[B], pi[B][A], a[B][A],
+ * da[B][A] (in / out: da += (2 / (B A)) (pi - a)).  Out: seed_out[B] = -lambda / B; scal_out[0] = lambda, [1] = mean |q|
+ * ([2], [3] are left alone); part_q_out[(B + 15) / 16][4] = (0, sum q, 0, untouched) per slice of 16 rows;
+ * part_sq_out[(B A + 15) / 16] = the sums of (pi - a)^2 over 16 adjacent elements.  Nothing is written past those
+ * extents.  OPRL_ERR_INVALID: a null pointer, B < 1, A < 1, B A > 2^30, alpha not finite or <= 0.  Tests reach the
+ * kernels' corners through it. */
+int oprl_bc_seed(const float* q, const float* pi, const float* a, float* da, double alpha, int32_t B, int32_t A,
+                 float* seed_out, float* scal_out, float* part_q_out, float* part_sq_out, void* stream);
 
 #ifdef __cplusplus
 }

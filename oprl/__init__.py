@@ -8,11 +8,12 @@ import sys as _sys
 _SUBMODULES = [
     "logging", "parse_args",
     "algos", "algos.protocols", "algos.base_algorithm", "algos.nn_models", "algos.nn_functions",
-    "algos.ddpg", "algos.td3", "algos.sac", "algos.tqc", "algos.redq", "algos.d4pg",
+    "algos.ddpg", "algos.td3", "algos.sac", "algos.tqc", "algos.redq", "algos.d4pg", "algos.td3_bc",
     "buffers", "buffers.protocols", "buffers.episodic_buffer", "buffers.prioritized_buffer", "buffers.nstep_buffer",
+    "buffers.offline_dataset",
     "environment", "environment.protocols", "environment.make_env",
     "runners", "runners.config", "runners.train", "runners.train_distrib",
-    "trainers", "trainers.protocols", "trainers.base_trainer", "trainers.vec_trainer",
+    "trainers", "trainers.protocols", "trainers.base_trainer", "trainers.vec_trainer", "trainers.offline_trainer",
     "distrib", "distrib.queue", "distrib.env_worker", "distrib.policy_update_worker",
 ]
 for _name in _SUBMODULES:

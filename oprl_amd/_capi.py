@@ -146,6 +146,9 @@ SIGNATURES = {
     "oprl_learner_update_weighted": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P, _P]),
     "oprl_learner_step_n_prio": (C.c_int, [_P, _P, _I32, _I32, _U64, _D, _D, _P]),
     "oprl_c51_seed": (C.c_int, [_P, _P, _P, _P, _D, _D, _D, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "oprl_learner_set_bc": (C.c_int, [_P, _D]),
+    "oprl_learner_read_bc": (C.c_int, [_P, C.POINTER(C.c_float), _P]),
+    "oprl_bc_seed": (C.c_int, [_P, _P, _P, _P, _D, _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

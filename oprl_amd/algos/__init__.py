@@ -1,9 +1,12 @@
-"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG`` is also served from here, resolved on
-first use so that importing the package stays free of torch."""
+"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG`` and ``TD3BC`` are also served from here,
+resolved on first use so that importing the package stays free of torch."""
 
 
 def __getattr__(name: str):
     if name == "D4PG":
         from oprl_amd.algos.d4pg import D4PG
         return D4PG
+    if name == "TD3BC":
+        from oprl_amd.algos.td3_bc import TD3BC
+        return TD3BC
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -521,6 +521,20 @@ class HipLearner:
                 "q1_mean", "log_pi_mean", "gauss_actor_loss", "alpha_loss")
         return dict(zip(keys, (float(x) for x in buf)))
 
+    def set_bc(self, alpha: float) -> None:
+        """The behaviour-cloning mode of a TD3 learner's actor step (oprl_learner_set_bc; TD3+BC):
+        ``alpha > 0`` turns it on, ``0`` turns it off."""
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_set_bc(self.handle, float(alpha)), "oprl_learner_set_bc")
+
+    def read_bc(self) -> dict[str, float]:
+        """lambda, mean |Q1(s, pi(s))| and the mean squared pi(s) - a of the last actor step with the mode on
+        (oprl_learner_read_bc)."""
+        buf = (C.c_float * 4)()
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_read_bc(self.handle, buf, _capi.current_stream()), "oprl_learner_read_bc")
+        return {"bc_lambda": float(buf[0]), "q_abs_mean": float(buf[1]), "bc_mse": float(buf[2])}
+
     @property
     def update_count(self) -> int:
         n = C.c_int64()

@@ -1,0 +1,57 @@
+"""TD3+BC on the MI355X-native learner (Fujimoto & Gu, "A Minimalist Approach to Offline Reinforcement Learning",
+NeurIPS 2021): TD3 exactly as algos/td3.py runs it — critic step, target smoothing noise, ``policy_freq``, Polyak with
+the actor — whose actor step minimises
+
+    -lambda (1/B) sum_b Q1(s_b, pi(s_b)) + (1/(B A)) sum_{b,k} (pi(s_b)_k - a_bk)^2,
+    lambda = bc_alpha / ((1/B) sum_b |Q1(s_b, pi(s_b))|),
+
+with lambda a constant for the gradient and, as in the authors' code, no epsilon in its denominator; ``a`` is the
+minibatch's action.  It is what makes training from a fixed dataset work (buffers/offline_dataset.py,
+trainers/offline_trainer.py).  On the device the cloning term is a MODE of a TD3 learner (``HipLearner.set_bc``; csrc/
+bc_seed.hip): f32, the generic launch sequence (``no_fuse``), one learner, no prioritized replay."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+from oprl_amd import _capi
+from oprl_amd.algos.td3 import TD3
+
+
+@dataclass
+class TD3BC(TD3):
+    bc_alpha: float = 2.5          # the weight of the Q term against the cloning term (the paper's alpha)
+
+    def __post_init__(self) -> None:
+        check_config(self)
+
+    def create(self) -> "TD3BC":
+        check_config(self)
+        self.no_fuse = True        # the BC step exists on the generic launch sequence only
+        super().create()
+        self.learner.set_bc(float(self.bc_alpha))
+        return self
+
+    def _log_update(self, step: int) -> None:
+        super()._log_update(step)
+        if step % self.log_every == 0 and step % self.policy_freq == 0:
+            bc = self.learner.read_bc()
+            self.logger.log_scalar("algo/bc_lambda", bc["bc_lambda"], step)
+            self.logger.log_scalar("algo/bc_mse", bc["bc_mse"], step)
+
+
+def check_config(algo: TD3BC) -> None:
+    """What the learner would refuse, said before anything touches the GPU."""
+    if algo.precision != "f32":
+        if algo.precision not in _capi.PRECISION:
+            raise ValueError(f"precision={algo.precision!r}: expected one of {sorted(_capi.PRECISION)}")
+        raise ValueError(f"TD3BC: precision={algo.precision!r} unsupported (f32 only: the BC step runs the generic "
+                         "launch sequence)")
+    if algo.export_grads:
+        raise ValueError("TD3BC: export_grads (data-parallel learners) unsupported")
+    if algo.prioritized:
+        raise ValueError("TD3BC(prioritized=True): prioritized replay through TD3BC is not built (a fixed dataset is "
+                         "sampled uniformly)")
+    alpha = float(algo.bc_alpha)
+    if not (math.isfinite(alpha) and alpha > 0.0):
+        raise ValueError(f"TD3BC: bc_alpha={algo.bc_alpha!r} is not a finite number above 0")

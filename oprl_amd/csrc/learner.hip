@@ -9,6 +9,7 @@
 #include "learner_internal.h"
 #include "per_seed.h"
 #include "c51_seed.h"
+#include "bc_seed.h"
 #include "philox.h"
 
 namespace oprl {
@@ -1323,6 +1324,47 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
       f.dact_col0 = S; f.dact_cols = A; f.dact = h->da; f.lddact = A;
       return f;
     }));
+  } else if (h->bc_alpha > 0.0) {
+    // TD3 + BC (oprl_learner_set_bc): where TD3 runs one forward + backward launch of critic 0 from
+    // SEED_CONST -1/B, the seed is -lambda/B with lambda = alpha / mean |Q1(s, pi)|, which needs every row's q first — so
+    // critic 0's forward with the activations stored and q into qpi (idle since the critic step), k_bc_seed, critic 0's
+    // backward from the seed rows (SEED_PTR, ld0 = 1), and k_bc_mix, which adds (2 / (B A)) (pi - a) to the action gradients
+    if (algo != OPRL_TD3 || h->bc_seed == nullptr) { set_err("internal: behaviour-cloning actor step without its buffers"); return OPRL_ERR_STATE; }
+    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
+      MlpArgs f = base_args(h, c.critics[0], false, B);
+      f.do_fwd = 1;
+      f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
+      with_store(f, h->ws_critic[0], true, false);
+      f.out = h->qpi; f.ldo = 1;
+      return f;
+    }));
+    BcSeedArgs t;
+    memset((void*)&t, 0, sizeof t);
+    t.q = h->qpi; t.alpha = (float)h->bc_alpha;
+    t.B = B; t.n_slices = (B + kR - 1) / kR;
+    t.seed = h->bc_seed; t.scal = h->bc_scal; t.partials = h->part_a;
+    prof_begin(3, st);
+    hipError_t e = launch_bc_seed(t, st);
+    prof_end(st);
+    HIPC(e);
+    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
+      MlpArgs f = base_args(h, c.critics[0], false, B);
+      f.do_bwd = 1;
+      with_store(f, h->ws_critic[0], true, false);
+      f.seed_mode = SEED_PTR;
+      f.seed.p0 = h->bc_seed; f.seed.ld0 = 1;
+      f.dact_col0 = S; f.dact_cols = A; f.dact = h->da; f.lddact = A;
+      return f;
+    }));
+    BcMixArgs m;
+    memset((void*)&m, 0, sizeof m);
+    m.pi = h->pi; m.a = rows.cur.a; m.da = h->da; m.part = h->bc_part;
+    m.B = B; m.A = A;
+    prof_begin(3, st);
+    e = launch_bc_mix(m, st);
+    prof_end(st);
+    HIPC(e);
+    h->bc_parts = bc_mix_slices(B, A); h->bc_B = B;
   } else {
     // TQC: the actor's backward (step 8) consumes the action gradients the launch sequence below ends with (k_lw_dact):
     // offered as a rider of that launch (r06-16; the tag its launch would draw, now)

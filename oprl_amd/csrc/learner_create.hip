@@ -416,6 +416,7 @@ extern "C" int oprl_learner_destroy(oprl_learner* h) {
   if (h->lw_pairs.flags) (void)hipFree(h->lw_pairs.flags);
   dev_free(h->batch_alt);
   if (h->per_seed) (void)hipFree(h->per_seed);
+  if (h->bc_seed) (void)hipFree(h->bc_seed);
   dev_free(h->uc_base);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->act_pin) (void)hipHostFree(h->act_pin);

@@ -368,6 +368,12 @@ struct oprl_learner {
   // D4PG (c51_seed.hip): the online critic's logits [Bmax][ldq] between its forward-only and backward-only launches, and
   // the seed rows SEED_PTR reads; in the pool, null on every other learner
   float *c51_logits = nullptr, *c51_seed = nullptr;
+  // the behaviour-cloning mode of a TD3 learner's actor step (oprl_learner_set_bc, bc_seed.hip): alpha (0:
+  // off), and one allocation of its own, made when the mode is first turned on — the seed rows [Bmax] | lambda, mean |Q|
+  // and two spares [4] | k_bc_mix's partial sums [bc_mix_slices(Bmax, A)]; bc_parts: how many the last actor step wrote
+  double bc_alpha = 0.0;
+  float *bc_seed = nullptr, *bc_scal = nullptr, *bc_part = nullptr;
+  int bc_parts = 0, bc_B = 0;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)

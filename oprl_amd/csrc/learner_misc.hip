@@ -2,6 +2,10 @@
 // the C-ABI (oprl_mlp_forward / act / backward, oprl_adam_step, oprl_polyak).  Split from learner.hip (round 4).
 #include "learner_internal.h"
 #include "c51_seed.h"
+#include "bc_seed.h"
+
+#include <cmath>
+#include <vector>
 
 extern "C" int oprl_learner_read_scalars(oprl_learner* h, float* out_host, int32_t n, void* stream) {
   if (!h || !out_host || n < 1) { set_err("oprl_learner_read_scalars: invalid argument"); return OPRL_ERR_INVALID; }
@@ -185,6 +189,82 @@ extern "C" int oprl_c51_seed(const float* zt, const float* z, const float* r, co
   a.N = N; a.B = B; a.ld = ld;
   a.seed = seed_out; a.m = m_out; a.loss_row = loss_out;
   HIPC(launch_c51_critic_seed(a, (hipStream_t)stream));
+  return OPRL_OK;
+}
+
+// ---------------------------------------------------------------- TD3 + BC
+// The behaviour-cloning mode of a TD3 learner's actor step (learner.hip actor_phase).  Every refusal comes before any GPU
+// work and changes nothing.
+extern "C" int oprl_learner_set_bc(oprl_learner* h, double alpha) {
+  if (!h) { set_err("oprl_learner_set_bc: null learner handle"); return OPRL_ERR_INVALID; }
+  if (h->cfg.algo != OPRL_TD3) {
+    set_err("oprl_learner_set_bc: the behaviour-cloning actor step is a mode of TD3 learners (algo %d); DDPG shares the branch and is a follow-up", h->cfg.algo);
+    return OPRL_ERR_INVALID;
+  }
+  if (h->bf16 || h->x2) { set_err("oprl_learner_set_bc: the BC step runs the exact-fp32 generic launch sequence only (precision f32)"); return OPRL_ERR_INVALID; }
+  // (as the kernel sees it, a float: neither overflowing nor flushed to zero)
+  if (!std::isfinite(alpha) || alpha < 0.0 || !std::isfinite((float)alpha) || (alpha > 0.0 && !((float)alpha > 0.f))) {
+    set_err("oprl_learner_set_bc: alpha=%g is not a finite number >= 0 (0 turns the mode off)", alpha);
+    return OPRL_ERR_INVALID;
+  }
+  // (a member of a group is a fused learner: said first, so that the message names the reason that cannot be lifted)
+  if (h->group_member) { set_err("oprl_learner_set_bc: the learner is a member of a group (packed learners run the fused launches, which have no BC step)"); return OPRL_ERR_STATE; }
+  if (h->fused) {
+    set_err("oprl_learner_set_bc: the learner's fused launch form is on, which has no BC step; create it with no_fuse");
+    return OPRL_ERR_STATE;
+  }
+  if (h->cfg.export_grads || h->rccl.comm != nullptr || h->p2p_ok) {
+    set_err("oprl_learner_set_bc: gradient-exporting (export_grads) / data-parallel learners have no BC step");
+    return OPRL_ERR_STATE;
+  }
+  if (alpha > 0.0 && h->bc_seed == nullptr) {      // the mode's rows, once: no update allocates
+    const size_t n = (size_t)h->Bmax + 4 + (size_t)bc_mix_slices(h->Bmax, h->A);
+    float* p = nullptr;
+    if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) { set_err("hipMalloc(%zu) failed (behaviour-cloning rows)", n * sizeof(float)); return OPRL_ERR_NOMEM; }
+    hipError_t e = hipMemset(p, 0, n * sizeof(float));
+    if (e != hipSuccess) { (void)hipFree(p); HIPC(e); }
+    h->bc_seed = p;
+    h->bc_scal = p + h->Bmax;
+    h->bc_part = h->bc_scal + 4;
+  }
+  h->bc_alpha = alpha;
+  return OPRL_OK;
+}
+
+extern "C" int oprl_learner_read_bc(oprl_learner* h, float out_host[4], void* stream) {
+  if (!h || !out_host) { set_err("oprl_learner_read_bc: null argument"); return OPRL_ERR_INVALID; }
+  if (h->bc_seed == nullptr) { set_err("oprl_learner_read_bc: the behaviour-cloning mode was never on (oprl_learner_set_bc)"); return OPRL_ERR_STATE; }
+  hipStream_t st = (hipStream_t)stream;
+  const int n = h->bc_parts;
+  std::vector<float> host(4 + (size_t)n, 0.f);
+  HIPC(hipMemcpyAsync(host.data(), h->bc_scal, sizeof(float) * (4 + (size_t)n), hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  RC(check_device_error(h));
+  double sq = 0.0;                                  // k_bc_mix's partial sums, in slice order
+  for (int i = 0; i < n; ++i) sq += (double)host[4 + i];
+  out_host[0] = host[0];                            // lambda
+  out_host[1] = host[1];                            // mean |Q1(s, pi(s))|
+  out_host[2] = n > 0 ? (float)(sq / ((double)h->bc_B * (double)h->A)) : 0.f;   // mean (pi - a)^2
+  out_host[3] = 0.f;
+  return OPRL_OK;
+}
+
+extern "C" int oprl_bc_seed(const float* q, const float* pi, const float* a, float* da, double alpha, int32_t B, int32_t A,
+                            float* seed_out, float* scal_out, float* part_q_out, float* part_sq_out, void* stream) {
+  if (!q || !pi || !a || !da || !seed_out || !scal_out || !part_q_out || !part_sq_out) { set_err("oprl_bc_seed: null argument"); return OPRL_ERR_INVALID; }
+  if (B < 1 || A < 1 || (int64_t)B * A > (1 << 30) || !std::isfinite(alpha) || !((float)alpha > 0.f) || !std::isfinite((float)alpha)) {
+    set_err("oprl_bc_seed: need B >= 1 (B=%d), A >= 1 (A=%d), B A <= 2^30 and a finite alpha > 0 (%g)", B, A, alpha);
+    return OPRL_ERR_INVALID;
+  }
+  BcSeedArgs t;
+  memset((void*)&t, 0, sizeof t);
+  t.q = q; t.alpha = (float)alpha; t.B = B; t.n_slices = (B + kR - 1) / kR;
+  t.seed = seed_out; t.scal = scal_out; t.partials = part_q_out;
+  HIPC(launch_bc_seed(t, (hipStream_t)stream));
+  BcMixArgs m;
+  memset((void*)&m, 0, sizeof m);
+  m.pi = pi; m.a = a; m.da = da; m.part = part_sq_out; m.B = B; m.A = A;
+  HIPC(launch_bc_mix(m, (hipStream_t)stream));
   return OPRL_OK;
 }
 

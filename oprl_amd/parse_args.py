@@ -37,7 +37,10 @@ _DISTRIB = (
 def _parser(title: str, extra) -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description=title)
     for flag, kind, default, text in (*_SHARED, *extra):
-        parser.add_argument(flag, type=kind, default=default, help=text)
+        if kind is bool:      # a switch (configs/td3_bc.py --no-normalize)
+            parser.add_argument(flag, action="store_true", help=text)
+        else:
+            parser.add_argument(flag, type=kind, default=default, help=text)
     # extension: prioritized experience replay (buffers/prioritized_buffer.py)
     parser.add_argument("--per", action="store_true",
                         help="prioritized replay: sample by |TD| priority from the sum tree in HBM, importance-weighted "
@@ -58,7 +61,7 @@ def check_per(args: argparse.Namespace) -> bool:
 
 def parse_args(extra=()) -> argparse.Namespace:
     """Flags of the single-process scripts (configs/ddpg.py ...).  ``extra``: a script's own flags, as (flag, type,
-    default, help) tuples (configs/d4pg.py: the atoms of its critic)."""
+    default, help) tuples (configs/d4pg.py: the atoms of its critic); type ``bool`` makes a switch."""
     parser = _parser("Run training", (*_SINGLE, *extra))
     # extension: one open replay episode per environment (buffers/episodic_buffer.py open_lanes, DESIGN.md section 14)
     parser.add_argument("--open-episodes", action="store_true",

@@ -1,11 +1,12 @@
 """update() throughput of the algorithms at the BASELINE.json configs
-(parity-test cases 2-4 + DDPG, REDQ, D4PG), fixed synthetic minibatch resident in HBM, noise
+(parity-test cases 2-4 + DDPG, REDQ, D4PG, TD3BC), fixed synthetic minibatch resident in HBM, noise
 drawn on device — one Python call per update, so the fast paths are bound by the
 call rate — and, second column, oprl_learner_step_n (sampling from an HBM replay +
 update, K steps per call).  Not the headline bench (bench.py); numbers for DESIGN.md.
 
     python tools/bench_algos.py [n] [name filter] [precisions]      one case after the other
     python tools/bench_algos.py 2000 D4PG DDPG                      a comparison on the GENERIC launch sequence
+    python tools/bench_algos.py 2000 TD3BC TD3                      
 
 Two or more algorithm names: each names the first case that starts with it, created as a ``no_fuse`` learner so that
 all of them take the generic launch sequence (D4PG has no other), and the timed passes alternate
@@ -20,6 +21,7 @@ from oprl_amd.algos.ddpg import DDPG
 from oprl_amd.algos.redq import REDQ
 from oprl_amd.algos.sac import SAC
 from oprl_amd.algos.td3 import TD3
+from oprl_amd.algos.td3_bc import TD3BC
 from oprl_amd.algos.tqc import TQC
 from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
 from oprl_amd.logging import NullLogger
@@ -30,7 +32,8 @@ CASES = [("DDPG walker B=256", DDPG, 24, 6, 256, {}),
          ("SAC walker tuned B=256", SAC, 24, 6, 256, dict(log_every=10 ** 9, tune_alpha=True)),
          ("TQC walker B=256", TQC, 24, 6, 256, dict(log_every=10 ** 9)),
          ("REDQ walker N=10 M=2 B=256", REDQ, 24, 6, 256, dict(log_every=10 ** 9)),
-         ("D4PG walker N=41 B=256", D4PG, 24, 6, 256, {})]
+         ("D4PG walker N=41 B=256", D4PG, 24, 6, 256, {}),
+         ("TD3BC cheetah B=256", TD3BC, 17, 6, 256, dict(log_every=10 ** 9))]
 PRECISIONS = ("f32", "bf16", "x2")
 
 
@@ -109,7 +112,7 @@ def main():
     for name, cls, S, A, B, kw in [(f"{c[0]} [{p}]", *c[1:5], dict(c[5], precision=p)) for c in CASES for p in precs]:
         if only and only not in name:
             continue
-        if cls is D4PG and kw["precision"] != "f32":
+        if cls in (D4PG, TD3BC) and kw["precision"] != "f32":
             continue                    # (f32 only)
         b = Bench(name, cls, S, A, B, kw)
         for _rep in range(2):           # best of two passes (the first one still sees clock ramp-up)
