@@ -130,7 +130,7 @@ struct DwX2Tile {
     n_stamp = 0;
     stamp();
     const int tiles_k = cdiv(I.K, TK);
-    const int tn = lt / tiles_k, tk = lt - tn * tiles_k;
+    const int tn = small_div(lt, tiles_k), tk = lt - tn * tiles_k;      // (idiv.h: a layer's fan-in is a few 64-column blocks)
     const int n_base = tn * kDwTileN, k_base = tk * TK;
     const bool polyak = ad.do_polyak && I.w_t != nullptr;
     // ---- this thread's element (nl, kl) of the epilogue and its Adam state, requested now
@@ -191,7 +191,7 @@ struct DwX2Tile {
   const DwGate& G = KA->gate;
   const DwItem I = KA->items[item];
   const int tiles_k = cdiv(I.K, TK);
-  const int tn = lt / tiles_k, tk = lt - tn * tiles_k;
+  const int tn = small_div(lt, tiles_k), tk = lt - tn * tiles_k;      // (idiv.h: a layer's fan-in is a few 64-column blocks)
   const int n_base = tn * kDwTileN, k_base = tk * TK;
   const bool polyak = ad.do_polyak && I.w_t != nullptr;
   const bool e_ok = n_base + (tid >> 6) < I.N && k_base + (tid & 63) < I.K;

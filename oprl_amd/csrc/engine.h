@@ -31,6 +31,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "idiv.h"
 
 namespace oprl {
 
@@ -577,11 +578,13 @@ __device__ __forceinline__ void load_rows(float* __restrict__ Xs, int ldx, int c
 }
 
 // ... with coherent loads (rows another workgroup of the same launch staged)
+// (MK: the row index through the host's multiplier for k — idiv.h row_div_magic(k) — instead of a division)
+template <bool MK = false>
 __device__ __forceinline__ void load_rows_c(float* __restrict__ Xs, int ldx, int c0,
                                             const float* __restrict__ G, int ldg, int k, int row0,
-                                            int B) {
+                                            int B, unsigned mk = 0u) {
   for (int idx = threadIdx.x; idx < kR * k; idx += kThreads) {
-    const int row = idx / k, col = idx - row * k;
+    const int row = MK ? row_div(idx, mk) : idx / k, col = idx - row * k;
     const int gr = row0 + row;
     Xs[row * ldx + c0 + col] = gr < B ? ldc(G + (size_t)gr * ldg + col) : 0.f;
   }
@@ -598,10 +601,12 @@ __device__ __forceinline__ void store_rows(const float* __restrict__ Xs, int ldx
 }
 
 // ... written through (agent-scope stores): rows a workgroup of the SAME launch reads behind a flag
+// (MK: as load_rows_c)
+template <bool MK = false>
 __device__ __forceinline__ void store_rows_wt(const float* __restrict__ Xs, int ldx,
-                                              float* __restrict__ G, int ldg, int k, int row0, int B) {
+                                              float* __restrict__ G, int ldg, int k, int row0, int B, unsigned mk = 0u) {
   for (int idx = threadIdx.x; idx < kR * k; idx += kThreads) {
-    const int row = idx / k, col = idx - row * k;
+    const int row = MK ? row_div(idx, mk) : idx / k, col = idx - row * k;
     const int gr = row0 + row;
     if (gr < B) __hip_atomic_store(G + (size_t)gr * ldg + col, Xs[row * ldx + col], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

@@ -1137,6 +1137,7 @@ struct PassCtx {
   const float* cb[3];           // the critic's biases as this update's tiles leave them (uncached copies)
   long long* trace;
   const float* pb1_32 = nullptr;   // (bf16 learners) the actor's second hidden layer as its fp32 W^T pack: the unit-seed rows' B operand
+  unsigned mS = 0, mA = 0;         // (k_ddpg_chain) the host's multipliers for row = index / S, / A (idiv.h row_div)
 };
 // GE (k_ddpg_chain): the first hidden layer's dY leaves this pass as UNIT-SEED rows G_j = dz1 / d(du_j), j < A — the
 // actor's backward is linear in du — computed and stored BEFORE the critic's new weights arrive (the pass's members sit
@@ -1253,14 +1254,15 @@ __device__ __forceinline__ int ddpg_phase2m_body(const DdpgArgs& A, const KA* D,
       if (row0 + 4 * kk + r < B) gm1[r] = ldc(A.aX[1] + (size_t)(row0 + 4 * kk + r) * kW4 + 32 * c + 16 * (wave & 1) + i);
   }
   // [s | pi]: loads first, then the zero fill and the stores
-  const int rs_ = tid / S, cs_ = tid - rs_ * S;
+  // (GE — k_ddpg_chain: the row indices through the host's multipliers, no divide)
+  const int rs_ = GE ? row_div(tid, cx.mS) : tid / S, cs_ = tid - rs_ * S;
   const bool oks = tid < kR * S && row0 + rs_ < B;
   const float vs = oks ? ldc(A.aX[0] + (size_t)(row0 + rs_) * A.aldx0 + cs_) : 0.f;
   const int tid2 = tid + kThreads;
-  const int rs2_ = tid2 / S, cs2_ = tid2 - rs2_ * S;
+  const int rs2_ = GE ? row_div(tid2, cx.mS) : tid2 / S, cs2_ = tid2 - rs2_ * S;
   const bool oks2 = tid2 < kR * S && row0 + rs2_ < B;
   const float vs2 = oks2 ? ldc(A.aX[0] + (size_t)(row0 + rs2_) * A.aldx0 + cs2_) : 0.f;
-  const int rp_ = tid / Ad, cp_ = tid - rp_ * Ad;
+  const int rp_ = GE ? row_div(tid, cx.mA) : tid / Ad, cp_ = tid - rp_ * Ad;
   const bool okp = tid < kR * Ad && row0 + rp_ < B;
   const float vp = okp ? ldc(A.pi + (size_t)(row0 + rp_) * Ad + cp_) : 0.f;
   lds_zero(xa, kR * kX0Ld);
@@ -1526,8 +1528,8 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
   using LY = FusedLds<256>;
   constexpr int HB = kR * kWL4;
   const int slices = (int)gridDim.x, slice = (int)blockIdx.x;
-  const int R = C.rows;                      // grid rows per update: A 8 | B 4 | C 4 | T (tile-only rows: small batches)
-  const int u = (int)blockIdx.y / R, yy = chain_row((int)blockIdx.y - u * R, C.order);
+  // grid (slices, rows per update: A 8 | B 4 | C 4 | T (tile-only rows: small batches), updates)
+  const int u = (int)blockIdx.z, yy = chain_row((int)blockIdx.y, C.order);
   const int B = A.B, S = A.S, Ad = A.A, tid = threadIdx.x, row0 = slice * kR;
   const unsigned ep = A.epoch + (unsigned)u;
   const unsigned tag1 = A.cluster_tag + 2u * (unsigned)u, tag2 = tag1 + 1u;
@@ -1583,9 +1585,9 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
     lds_zero(xa, 2 * kR * kX0Ld);   // xa and xb are adjacent
     __syncthreads();
     // (coherent loads: another workgroup of this launch staged these rows — engine.h ld4c / ldc)
-    load_rows_c(xa, kX0Ld, 0, ps, S, S, row0, B);
-    load_rows_c(xa, kX0Ld, S, pa, Ad, Ad, row0, B);
-    load_rows_c(xb, kX0Ld, 0, ps2, S, S, row0, B);
+    load_rows_c<true>(xa, kX0Ld, 0, ps, S, S, row0, B, C.mS);
+    load_rows_c<true>(xa, kX0Ld, S, pa, Ad, Ad, row0, B, C.mA);
+    load_rows_c<true>(xb, kX0Ld, 0, ps2, S, S, row0, B, C.mS);
     if (tid < kR) {
       const int gr = row0 + tid;
       rS[tid] = gr < B ? ldc(pr + gr) : 0.f;
@@ -1612,7 +1614,7 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
     tp.local = cluster_on_one_xcd(A);
     tp4_forward<Coh<P>, 8>(A.actor_t, xb, h1, h2, outS, scr, tp, nostore, row0, B, stamp, bias_of(1));
     for (int idx = tid; idx < kR * Ad; idx += kThreads) {
-      const int row = idx / Ad, col = idx - row * Ad, gr = row0 + row;
+      const int row = row_div(idx, C.mA), col = idx - row * Ad, gr = row0 + row;
       xb[row * kX0Ld + S + col] = gr < B ? tanhf(outS[row * kOutLd + col]) : 0.f;
     }
     // role B's q granules are requested from inside the second pass (after its layer-1 stage)
@@ -1676,12 +1678,11 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
     __syncthreads();       // (the pass below reuses this workgroup's LDS)
     // ---- ... and goes on as member `member` of this slice's critic pass (update and member formed again from the block
     // index: nothing of the role stays in a register through the pass)
-    int by2 = (int)blockIdx.y;
-    asm volatile("" : "+s"(by2));
-    const int u2 = by2 / C.rows;
+    int by2 = (int)blockIdx.y, u2 = (int)blockIdx.z;
+    asm volatile("" : "+s"(by2), "+s"(u2));
     const PassCtx cx{A.epoch + (unsigned)u2, A.cluster_tag + 2u * (unsigned)u2 + 1u, C.w3buf[u2 & 1], {C.b16[2][0], C.b16[2][1], C.b16[2][2]},
-                     (kTraceOn && u2 == C.trace_u) ? A.trace2 : nullptr, A.actor_pb1_f32};
-    (void)ddpg_phase2m_body<P, DwKArgs4, false, true>(A, Dap, chain_row(by2 - u2 * C.rows, C.order), cx);      // (GE: its pass runs on Coh<P>)
+                     (kTraceOn && u2 == C.trace_u) ? A.trace2 : nullptr, A.actor_pb1_f32, C.mS, C.mA};
+    (void)ddpg_phase2m_body<P, DwKArgs4, false, true>(A, Dap, chain_row(by2, C.order), cx);      // (GE: its pass runs on Coh<P>)
     return;
   }
 
@@ -1693,7 +1694,7 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
     if (lead) {        // (the input rows for the critic's first-layer tiles: out before the pass)
       __syncthreads();
       for (int idx = tid; idx < kR * (S + Ad); idx += kThreads) {
-        const int row = idx / (S + Ad), col = idx - row * (S + Ad), gr = row0 + row;
+        const int row = row_div(idx, C.mSA), col = idx - row * (S + Ad), gr = row0 + row;
         if (gr < B) __hip_atomic_store(A.cX[0] + (size_t)gr * A.cldx0 + col, xa[row * kX0Ld + col], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
@@ -1715,10 +1716,10 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
     tp4_forward<Coh<P>>(A.actor, xa, h1, h2, outS, scr, tp, st, row0, B, stamp, bias_of(0));
     if (lead) {
       for (int idx = tid; idx < kR * Ad; idx += kThreads) {
-        const int row = idx / Ad, col = idx - row * Ad, gr = row0 + row;
+        const int row = row_div(idx, C.mA), col = idx - row * Ad, gr = row0 + row;
         if (gr < B) st_ag(A.pi + (size_t)gr * Ad + col, tanhf(outS[row * kOutLd + col]));
       }
-      store_rows_wt(xa, kX0Ld, A.aX[0], A.aldx0, S, row0, B);
+      store_rows_wt<true>(xa, kX0Ld, A.aX[0], A.aldx0, S, row0, B, C.mS);
       // update 0: the row-major output layer as the launch before left it -> w3buf[0] (later updates: the output
       // layer's tiles of the update before wrote w3buf[parity] themselves)
       if (u == 0 && slice == 0)
@@ -1735,10 +1736,10 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
   // ---- from here on the workgroup is (update, index among the 8 x slices workgroups of roles B and C) and nothing else:
   // both are formed AGAIN from the block index, laundered through an empty asm, so that no value of the role above stays
   // in a register through the tiles (these kernels sit at the scalar-register limit; what does not fit is spilled)
-  int by2 = (int)blockIdx.y, bx2 = (int)blockIdx.x, nx2 = (int)gridDim.x;
-  asm volatile("" : "+s"(by2), "+s"(bx2), "+s"(nx2));
+  int by2 = (int)blockIdx.y, bx2 = (int)blockIdx.x, nx2 = (int)gridDim.x, u2 = (int)blockIdx.z;
+  asm volatile("" : "+s"(by2), "+s"(bx2), "+s"(nx2), "+s"(u2));
   // (index among the tile workgroups: role B slice-major, role C behind it, then T's rows)
-  const int u2 = by2 / C.rows, y2 = chain_row(by2 - u2 * C.rows, C.order);
+  const int y2 = chain_row(by2, C.order);
   const int wg2 = y2 < 16 ? ((y2 >= 12) ? 4 * nx2 : 0) + bx2 * 4 + ((y2 - 8) & 3) : 8 * nx2 + (y2 - 16) * nx2 + bx2;
   const int n_bc = 8 * nx2;
   const unsigned ep2 = A.epoch + (unsigned)u2;
@@ -1773,9 +1774,9 @@ __global__ __launch_bounds__(kThreads) void k_ddpg_chain(const DdpgArgs A, const
     }
   }
   {
-    int by3 = (int)blockIdx.y, bx3 = (int)blockIdx.x, nx3 = (int)gridDim.x;
-    asm volatile("" : "+s"(by3), "+s"(bx3), "+s"(nx3));
-    const int u3 = by3 / C.rows, y3 = chain_row(by3 - u3 * C.rows, C.order);
+    int by3 = (int)blockIdx.y, bx3 = (int)blockIdx.x, nx3 = (int)gridDim.x, u3 = (int)blockIdx.z;
+    asm volatile("" : "+s"(by3), "+s"(bx3), "+s"(nx3), "+s"(u3));
+    const int y3 = chain_row(by3, C.order);
     const int wg3 = y3 < 16 ? ((y3 >= 12) ? 4 * nx3 : 0) + bx3 * 4 + ((y3 - 8) & 3) : 8 * nx3 + (y3 - 16) * nx3 + bx3;
     const int tile = wg3 < Dap->tile_end[kDwFusedItems - 1] ? wg3 : -1;
     if (tile >= 0) {
@@ -1953,10 +1954,27 @@ bool fused_ddpg_is_lean(int nc, int no_lean, int S, int A, bool sac) {
 }
 bool fused_ddpg_is_lean(const DdpgArgs& a) { return fused_ddpg_is_lean(a.nc, a.no_lean, a.S, a.A, a.sac != 0); }
 
+// The divide-free quotients of idiv.h small_div hold for divisors up to kSmallDivMaxD and answer anything beyond without
+// a diagnostic: every launcher of code that forms them says so first.  The cluster-of-eight passes split their narrow
+// exchange by the action size (tp4.h tp4_allreduce_narrow); the 16 x 64 tiles (dw_tile_x2.h) find their coordinates by
+// the 64-column blocks of a layer's fan-in.
+static_assert(kDuLd <= kSmallDivMaxD, "the chain launch's action sizes are narrow-exchange divisors");
+static_assert((16 * kMaxS0 + 63) / 64 <= kSmallDivMaxD && kW4 / 64 <= kSmallDivMaxD, "the lean shapes' fan-ins are tile divisors");
+static bool narrow8_ok(const DdpgArgs& a) { return a.A >= 1 && a.A <= kSmallDivMaxD; }
+template <class KA>
+static bool tiles64_ok(const KA& d) {
+  if (d.n_items < 1 || d.n_items > KA::kItems) return false;
+  if (d.tile_end[d.n_items - 1] >= kSmallDivMaxN) return false;
+  for (int j = 0; j < d.n_items; ++j)
+    if (d.items[j].K < 1 || (d.items[j].K + kDwX2TileK - 1) / kDwX2TileK > kSmallDivMaxD) return false;
+  return true;
+}
+
 // phase 1 with the critic's dW + Adam tiles as extra grid rows (DdpgArgs::merged bit 0; `d` = fill_dw_kargs of
 // that launch with its gate filled in)
 hipError_t launch_ddpg_phase1_dw(const DdpgArgs& a, const DwKArgs& d, hipStream_t st) {
   const bool wide = (a.wide & 1) != 0;
+  if ((wide && !narrow8_ok(a)) || (kMergedTile64 && !tiles64_ok(d))) return hipErrorInvalidValue;
   if (!lean_ok(a) || a.sac || a.n_critics < 1 || a.n_critics > 2 || (a.merged & 1) == 0 || (wide && (!a.x2 || a.xnc < 8 || a.n_critics != 1))) return hipErrorInvalidValue;
   const int slices = (a.B + kR - 1) / kR;
   const int tiles = d.tile_end[kDwMaxItems - 1];
@@ -1980,6 +1998,7 @@ hipError_t launch_ddpg_phase1_dw(const DdpgArgs& a, const DwKArgs& d, hipStream_
 hipError_t launch_ddpg_phase2_dw(const DdpgArgs& a, const DwKArgs& d, hipStream_t st) {
   if (!lean_ok(a) || a.sac || !a.x2 || !kDwTileX2 || (a.merged & 2) == 0 || (a.wide & 2) == 0 || a.xnc < 8 || a.A > kDuLd || a.B > 256)
     return hipErrorInvalidValue;
+  if (!narrow8_ok(a) || !tiles64_ok(d)) return hipErrorInvalidValue;
   const int slices = (a.B + kR - 1) / kR;
   const int tiles = d.tile_end[kDwMaxItems - 1];
   const dim3 grid(slices, 8 + (a.prefetch_next ? 1 : 0) + (tiles + slices - 1) / slices);
@@ -1999,7 +2018,12 @@ hipError_t launch_ddpg_chain(const DdpgArgs& a, const DwKArgs4& dc, const DwKArg
   const int mt = tc > ta ? tc : ta;
   const int rows = 16 + chain_tile_rows(mt, slices);    // A 8 | B 4 | C 4 | T
   if (c.rows != rows) return hipErrorInvalidValue;
-  const dim3 grid(slices, rows * c.n_upd);
+  if (!narrow8_ok(a) || !tiles64_ok(dc) || !tiles64_ok(da)) return hipErrorInvalidValue;
+  // (the kernel's index arithmetic runs on the host's multipliers: idiv.h)
+  if (!row_div_ok(a.S + a.A) || c.mS != row_div_magic(a.S) || c.mA != row_div_magic(a.A) || c.mSA != row_div_magic(a.S + a.A)) return hipErrorInvalidValue;
+  // update u = grid plane u: blocks are dealt out x, then y, then z — the order of a (slices, rows * n_upd) grid — and the
+  // kernel reads (row, update) off the block index instead of dividing
+  const dim3 grid(slices, rows, c.n_upd);
   if (a.x2) hipLaunchKernelGGL((k_ddpg_chain<PrecX2>), grid, dim3(kThreads), fused_ddpg_lds_bytes(), st, a, dc, da, c);
   else if (a.bf16) hipLaunchKernelGGL((k_ddpg_chain<PrecBF16>), grid, dim3(kThreads), fused_ddpg_lds_bytes(), st, a, dc, da, c);
   else hipLaunchKernelGGL((k_ddpg_chain<PrecF32>), grid, dim3(kThreads), fused_ddpg_lds_bytes(), st, a, dc, da, c);
@@ -2012,7 +2036,7 @@ hipError_t launch_ddpg_phase1(const DdpgArgs& a, hipStream_t st) {
   const size_t lds = fused_ddpg_lds_bytes();
   const int pf = a.prefetch_p1 ? 1 : 0;
   if ((a.wide & 1) != 0) {      // role A on clusters of 8 (DDPG, lean passes; learner.hip decides)
-    if (!lean_ok(a) || a.sac || a.bf16 || a.n_critics != 1 || a.xnc < 8) return hipErrorInvalidValue;
+    if (!lean_ok(a) || a.sac || a.bf16 || a.n_critics != 1 || a.xnc < 8 || !narrow8_ok(a)) return hipErrorInvalidValue;
     const dim3 grid(slices, a.nc + 8 + a.nc + pf);
     if (a.x2) hipLaunchKernelGGL((k_ddpg_phase1<256, true, false, PrecX2, true>), grid, blk, lds, st, a);
     else hipLaunchKernelGGL((k_ddpg_phase1<256, true, false, PrecF32, true>), grid, blk, lds, st, a);
@@ -2059,7 +2083,7 @@ hipError_t launch_ddpg_phase2(const DdpgArgs& a, hipStream_t st) {
   const size_t lds = fused_ddpg_lds_bytes();
   // SAC side by side: one cluster per online critic; + the next-minibatch gather row
   if ((a.wide & 2) != 0) {      // the critic pass on clusters of 8 (DDPG / TD3, lean passes)
-    if (!lean_ok(a) || a.sac || a.bf16 || a.xnc < 8) return hipErrorInvalidValue;
+    if (!lean_ok(a) || a.sac || a.bf16 || a.xnc < 8 || !narrow8_ok(a)) return hipErrorInvalidValue;
     const dim3 grid(slices, 8 + (a.prefetch_next ? 1 : 0));
     if (a.x2) hipLaunchKernelGGL((k_ddpg_phase2<256, true, false, PrecX2, true>), grid, blk, lds, st, a);
     else hipLaunchKernelGGL((k_ddpg_phase2<256, true, false, PrecF32, true>), grid, blk, lds, st, a);

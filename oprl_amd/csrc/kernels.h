@@ -312,6 +312,7 @@ using DwKArgsG2 = DwKArgsN<kDwGroupItems2>;
 // whole-update launch carries two of them beside its DdpgArgs
 constexpr int kDwFusedItems = 4;
 struct DwKArgs4 {
+  static constexpr int kItems = kDwFusedItems;
   int tile_end[kDwFusedItems];
   DwItem items[kDwFusedItems];
   int n_items, B, n_part, dy_tiled;
@@ -444,6 +445,7 @@ struct ChainArgs {
   int trace_u;                         // trace build: the update whose stages are stamped
   int rows;                            // grid rows per update: 16 (roles A 8 | B 4 | C 4) + the tile-only rows of small batches
   int order;                           // dispatch order of an update's role rows: 0 A | B | C, 1 B | A | C, 2 B | C | A, 3 A | C | B (fused_ddpg.hip chain_row)
+  unsigned mS, mA, mSA;                // row_div_magic (idiv.h) of S, A and S + A: the roles' row / column index arithmetic without a divide
   float c_step[kChainMax], c_bc2[kChainMax];   // Adam's lr / (1 - b1^t) and sqrt(1 - b2^t) of the critic's step, per update
   float a_step[kChainMax], a_bc2[kChainMax];   // ... of the actor's
   const float* set0[5];                // staging rows s, a, r, d, s2: update u reads set (u & 1), its prefetch fills the other

@@ -835,6 +835,7 @@ int whole_update(oprl_learner* h, StepRows& rows, DdpgArgs& fa, const FusedForm&
   ca.trace_u = U - 1;
   ca.rows = 16 + t_rows;
   ca.order = h->sw.chain_order;
+  ca.mS = row_div_magic(fa.S); ca.mA = row_div_magic(fa.A); ca.mSA = row_div_magic(fa.S + fa.A);      // (idiv.h)
   // (the optimisers' step counts advance once per update and net: only Adam's bias-correction terms change from update
   // to update — a table build per update and net was 8 of the 17 us a step_n(20) call took to enqueue)
   AdamScalars sc_ = kc.ad, sa_ = ka.ad;

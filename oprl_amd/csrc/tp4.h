@@ -25,6 +25,7 @@
 // Summation order: members in index order (as tp3.h), inside a member even/odd-step chains.
 #pragma once
 #include "tp3.h"
+#include "idiv.h"
 
 namespace oprl {
 
@@ -168,7 +169,7 @@ __device__ __forceinline__ f32x4 tp4_allreduce_regs(const f32x4 mine, int col, b
 // (tp4_narrow_elem: the k-th valid column of lane slot j — what the caller needs to fetch a per-column bias EARLY.)
 __device__ __forceinline__ int tp4_narrow_elem(int j, int ncols) {
   const int e = (int)(threadIdx.x & 63) + 64 * j;
-  return e < 16 * ncols ? e % ncols : -1;
+  return e < 16 * ncols ? e - small_div(e, ncols) * ncols : -1;      // (e < 128: idiv.h)
 }
 template <int NM>
 __device__ __forceinline__ void tp4_allreduce_narrow(const f32x4 mine, int i_first, int ncols, int cc_first,
@@ -191,7 +192,7 @@ __device__ __forceinline__ void tp4_allreduce_narrow(const f32x4 mine, int i_fir
   for (int j = 0; j < 2; ++j) {
     const int e = lane + 64 * j;
     have[j] = e < n;
-    const int row = have[j] ? e / ncols : 0, k = have[j] ? e - row * ncols : 0;
+    const int row = have[j] ? small_div(e, ncols) : 0, k = have[j] ? e - row * ncols : 0;      // (e < 128: idiv.h)
     val[j] = wscr[row * 16 + i_first + k];
     off[j] = ((row & 3) * 4 + (row >> 2)) * kNarrowMax + cc_first + k;     // (r * 4 + kk) * kNarrowMax + col
     oidx[j] = row * kOutLd + cc_first + k;
