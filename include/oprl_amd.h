@@ -8,6 +8,8 @@
  *                    DDPG/TD3/SAC/TQC.update()            algos/ddpg.py:61, td3.py:71, sac.py:75, tqc.py:116
  *   oprl_learner_set_bc / read_bc, oprl_bc_seed   no counterpart: TD3+BC's actor loss as a mode of a TD3 learner
  *                    (Fujimoto & Gu 2021), for training from a fixed dataset
+ *   oprl_learner_set_iql / read_iql / get_iql_step / set_iql_step, oprl_iql_seed   no counterpart: implicit Q-learning
+ *                    (Kostrikov et al. 2021) as a mode of a TD3 learner with a caller-owned value net
  *   oprl_replay_*    ReplayBufferProtocol                 buffers/protocols.py:6-26
  *                    EpisodicReplayBuffer.{add_transition,sample}  buffers/episodic_buffer.py:81-133
  *   oprl_mlp_*       MLP / Critic / policies forward      algos/nn_models.py:27-194
@@ -556,6 +558,46 @@ int oprl_learner_read_bc(oprl_learner* h, float out_host[4], void* stream);
  * kernels' corners through it. */
 int oprl_bc_seed(const float* q, const float* pi, const float* a, float* da, double alpha, int32_t B, int32_t A,
                  float* seed_out, float* scal_out, float* part_q_out, float* part_sq_out, void* stream);
+
+/* ---- Implicit Q-learning: an expectile value net and an advantage-weighted actor (Kostrikov et al. 2021)
+ * A MODE of a TD3 learner, like the one above: a non-null `value` turns it on, NULL turns it off (TD3 again, bit for
+ * bit).  `value` is a caller-owned net V(s) with dims [state_dim, ..., 1]: theta, Adam moments and fragment pack, no
+ * target, no gradient arena.  With qt = min_j Qtarget_j(s, a) on the minibatch's own action, u = qt - V(s) and V(s')
+ * both taken with V as it is BEFORE this update's V step, one update is
+ *   V:       one Adam step (lr_value, its own step count) on (1/B) sum_b omega_b u_b^2, omega_b = 1 - expectile where
+ *            u_b < 0 and expectile otherwise; V has no target net and takes no Polyak step;
+ *   critics: TD3's step with y = r + ((1 - d) gamma) V(s'): no target actor, no smoothing noise;
+ *   actor:   one Adam step on (1/B) sum_b w_b sum_k (pi(s_b)_k - a_bk)^2, w_b = min(exp(beta u_b), adv_clip) a constant;
+ *   Polyak on the critic targets (and the actor's, which nothing reads), every update.
+ * No action outside the minibatch is evaluated.  The call that turns the mode on allocates its rows (once per shape of
+ * V); no update allocates.  oprl_learner_sync_params rebuilds V's pack too while the mode is on.  12 launches per update
+ * on the generic launch sequence (csrc/iql_seed.hip holds the two new kernels), so: OPRL_ERR_INVALID for any algorithm but
+ * TD3, a precision other than OPRL_PREC_F32, policy_freq != 1, expectile outside (0, 1), beta < 0, adv_clip <= 0, lr_value
+ * <= 0, any of them non-finite, a value net whose dims[0] is not state_dim or whose output is not 1, whose layer count or
+ * width the generic path does not take, or without moments or pack; OPRL_ERR_STATE for a learner whose fused form is on
+ * (create it with no_fuse), for export_grads / data-parallel learners, members of a group and a learner with the
+ * behaviour-cloning mode on.  With the mode on, oprl_learner_set_bc, oprl_group_create, oprl_learner_update_weighted and
+ * oprl_learner_step_n_prio return OPRL_ERR_STATE.  A refused call changes nothing. */
+int oprl_learner_set_iql(oprl_learner* h, const oprl_net* value, double expectile, double beta, double adv_clip,
+                         double lr_value);
+/* Of the last update with the mode on, the per-slice sums added in slice order: out_host[0] = the V loss, [1] = mean
+ * V(s), [2] = mean u, [3] = mean w, [4] = the share of rows at the clip, [5] = the weighted cloning loss (what
+ * oprl_learner_read_scalars reports as the actor loss in this mode), [6] = [7] = 0 (spares).  Synchronises `stream`.
+ * OPRL_ERR_STATE for a learner on which the mode was never on. */
+int oprl_learner_read_iql(oprl_learner* h, float out_host[8], void* stream);
+/* V's Adam step count (oprl_learner_get_counters / set_counters carry their four numbers unchanged). */
+int oprl_learner_get_iql_step(oprl_learner* h, int64_t* out_host);
+int oprl_learner_set_iql_step(oprl_learner* h, int64_t step);
+/* k_iql_value_seed and k_iql_actor_seed on caller-supplied device rows, as the learner's update runs them: q1[B], q2[B]
+ * (the target critics), v[B], pi[B][A], a[B][A].  Out: u_out[B] = min(q1, q2) - v; seed_out[B] = ((2 (v - qt)) (1/B))
+ * omega; w_out[B] = min(exp(beta u), adv_clip); da_out[B][A] = (2/B) w (pi - a); per slice of 16 rows, n = (B + 15) / 16:
+ * part_v_out[n][4] = (sum omega u^2, sum v, sum u, untouched), part_w_out[n][4] = (0, sum w, rows at the clip,
+ * untouched), part_a_out[n][4] = (0, sum_b w_b sum_k (pi - a)^2, 0, untouched).  Nothing is written past those extents.
+ * OPRL_ERR_INVALID: a null pointer, B < 1, A < 1, B A > 2^30, expectile outside (0, 1), beta < 0, adv_clip <= 0 or any of
+ * them non-finite.  Tests reach the kernels' corners through it. */
+int oprl_iql_seed(const float* q1, const float* q2, const float* v, const float* pi, const float* a, double expectile,
+                  double beta, double adv_clip, int32_t B, int32_t A, float* u_out, float* seed_out, float* w_out,
+                  float* da_out, float* part_v_out, float* part_w_out, float* part_a_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,4 @@
-"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG`` and ``TD3BC`` are also served from here,
+"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG``, ``TD3BC`` and ``IQL`` are also served from here,
 resolved on first use so that importing the package stays free of torch."""
 
 
@@ -9,4 +9,7 @@ def __getattr__(name: str):
     if name == "TD3BC":
         from oprl_amd.algos.td3_bc import TD3BC
         return TD3BC
+    if name == "IQL":
+        from oprl_amd.algos.iql import IQL
+        return IQL
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -161,6 +161,9 @@ def check_nstep_gamma(algo, replay_buffer) -> None:
                          "algorithm's gamma")
 
 
+IQL_STATE_KEYS = ("value", "value_m", "value_v", "value_step")
+
+
 def _rows_f32(obs) -> np.ndarray:
     """Observation rows as one contiguous float32 [N, S] host array."""
     x = np.ascontiguousarray(obs, dtype=np.float32)
@@ -264,6 +267,8 @@ class HipLearner:
         self.algo_name = algo
         self.policy_freq = int(hp.get("policy_freq", 1))
         self._mlps = (actor_mlp, actor_target_mlp, list(critic_mlps), list(critic_target_mlps))
+        self._value_mlp = None         # the value net of the implicit-Q-learning mode (set_iql) ...
+        self._iql_on = False           # ... and whether the mode is on (the net and its moments are kept while it is off)
         self._ptrs = self._snapshot_ptrs()
         h = C.c_void_p()
         with _capi.on_device(device):
@@ -289,9 +294,9 @@ class HipLearner:
         c = getattr(self, "_pcache", None)
         if c is None:
             a, at, cs, cts = self._mlps
-            mlps = [a, *([at] if at is not None else []), *cs, *cts]
+            mlps = [a, *([at] if at is not None else []), *cs, *cts, *([self._value_mlp] if self._value_mlp is not None else [])]
             first = [next(m.parameters()) for m in mlps]
-            every = [p for m in [a, at, *cs, *cts] if m is not None for p in m.parameters()]
+            every = [p for m in mlps for p in m.parameters()]
             c = self._pcache = (first, every)
         return c
 
@@ -331,6 +336,11 @@ class HipLearner:
         }
         if self.log_alpha is not None:
             sd["log_alpha"] = [x.detach().cpu().clone() for x in (self.log_alpha, self.log_alpha_m, self.log_alpha_v)]
+        if self._iql_on:      # the implicit-Q-learning mode: V, its moments and its Adam step count
+            n = C.c_int64()
+            _capi.check(self.lib.oprl_learner_get_iql_step(self.handle, C.byref(n)), "oprl_learner_get_iql_step")
+            sd.update(value=self.value_arena.detach().cpu().clone(), value_m=self.value_m.cpu().clone(),
+                      value_v=self.value_v.cpu().clone(), value_step=int(n.value))
         return sd
 
     def load_state_dict(self, sd: dict[str, Any]) -> None:
@@ -341,6 +351,12 @@ class HipLearner:
                  *zip(self.target_arenas(), sd["targets"])]
         if self.log_alpha is not None:
             pairs += list(zip((self.log_alpha, self.log_alpha_m, self.log_alpha_v), sd["log_alpha"]))
+        if self._iql_on:
+            missing = [k for k in IQL_STATE_KEYS if k not in sd]
+            if missing:
+                raise ValueError(f"checkpoint has no {', '.join(missing)}: this learner's implicit-Q-learning mode is on "
+                                 "and resumes its value net, both Adam moments and its step count with the rest")
+            pairs += [(self.value_arena, sd["value"]), (self.value_m, sd["value_m"]), (self.value_v, sd["value_v"])]
         for dst, src in pairs:
             if dst.shape != src.shape:
                 raise ValueError(f"checkpoint tensor shape {tuple(src.shape)} != {tuple(dst.shape)}")
@@ -349,6 +365,8 @@ class HipLearner:
                 dst.copy_(src.to(dst.device))
         cnt = (C.c_int64 * 4)(*[int(x) for x in sd["counters"]])
         _capi.check(self.lib.oprl_learner_set_counters(self.handle, cnt), "oprl_learner_set_counters")
+        if self._iql_on:
+            _capi.check(self.lib.oprl_learner_set_iql_step(self.handle, int(sd["value_step"])), "oprl_learner_set_iql_step")
         self.sync_params()      # the fragment-order packs are derived state
 
     def check_bound(self) -> None:
@@ -534,6 +552,56 @@ class HipLearner:
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_read_bc(self.handle, buf, _capi.current_stream()), "oprl_learner_read_bc")
         return {"bc_lambda": float(buf[0]), "q_abs_mean": float(buf[1]), "bc_mse": float(buf[2])}
+
+    def set_iql(self, value_mlp: MLP | None, expectile: float = 0.7, beta: float = 3.0, adv_clip: float = 100.0,
+                lr_value: float = 3e-4) -> None:
+        """The implicit-Q-learning mode of a TD3 learner (oprl_learner_set_iql): ``value_mlp`` is
+        the flat value net V(s), dims [S, ..., 1], for which this learner keeps the Adam moments; ``None`` turns the mode
+        off (the net, its moments and its step count are kept: the same net turns it on again where it stopped).  A refused
+        call leaves the learner as it was."""
+        if value_mlp is None:
+            with _capi.on_device(self.device):
+                _capi.check(self.lib.oprl_learner_set_iql(self.handle, None, 0.0, 0.0, 0.0, 0.0), "oprl_learner_set_iql")
+            self._iql_on = False
+            return
+        if not is_flat(value_mlp):
+            flatten_module_(value_mlp)
+        arena = value_mlp._oprl_arena
+        same = value_mlp is self._value_mlp
+        m = self.value_m if same else t.zeros_like(arena)
+        v = self.value_v if same else t.zeros_like(arena)
+        desc = _capi.OprlNet()
+        desc.n_layers = len(value_mlp.dims) - 1
+        for i, x in enumerate(value_mlp.dims):
+            desc.dims[i] = x
+        desc.theta = value_mlp.theta_ptr()
+        desc.pack = value_mlp.pack_tensor().data_ptr()
+        desc.adam_m, desc.adam_v = m.data_ptr(), v.data_ptr()
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_set_iql(self.handle, C.byref(desc), float(expectile), float(beta),
+                                                      float(adv_clip), float(lr_value)), "oprl_learner_set_iql")
+        if not same:
+            self._all_mlps = [x for x in self._all_mlps if x is not self._value_mlp] + [value_mlp]
+        self._value_mlp, self.value_arena, self.value_m, self.value_v = value_mlp, arena, m, v
+        self._iql_on = True
+        self._pcache = None            # V's parameters join the ones check_bound() watches
+        self._ptrs = self._snapshot_ptrs()
+        self.sync_params()      # V's pack is derived state like the others
+
+    def read_iql(self) -> dict[str, float]:
+        """Of the last update with the mode on: the V loss, mean V(s), mean advantage u, mean weight w, the share of rows
+        at the clip and the weighted cloning loss (oprl_learner_read_iql)."""
+        buf = (C.c_float * 8)()
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_read_iql(self.handle, buf, _capi.current_stream()), "oprl_learner_read_iql")
+        keys = ("v_loss", "v_mean", "adv_mean", "w_mean", "clip_frac", "actor_loss")
+        return dict(zip(keys, (float(x) for x in buf)))
+
+    @property
+    def value_step(self) -> int:
+        n = C.c_int64()
+        _capi.check(self.lib.oprl_learner_get_iql_step(self.handle, C.byref(n)), "oprl_learner_get_iql_step")
+        return int(n.value)
 
     @property
     def update_count(self) -> int:

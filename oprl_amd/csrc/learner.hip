@@ -10,6 +10,7 @@
 #include "per_seed.h"
 #include "c51_seed.h"
 #include "bc_seed.h"
+#include "iql_seed.h"
 #include "philox.h"
 
 namespace oprl {
@@ -1003,6 +1004,92 @@ int c51_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st
   return for_each_net(h, 1, h->w_critic, st, [&](int) { return c51_backward_args(h, B, true); });
 }
 
+// The critic phase of a TD3 learner with the implicit-Q-learning mode on (oprl_learner_set_iql).  No action
+// outside the batch is evaluated: V on s' where TD3 runs the target actor and the target critics on (s', a'), the target
+// critics on the batch's own (s, a), V's expectile step as forward | k_iql_value_seed | backward from SEED_PTR with a dW +
+// Adam launch of its own (its item table, its learning rate, its step count; no target, no Polyak), then TD3's critic
+// launch with the one target row V(s') — taken BEFORE V's step — and the critics' unchanged dW + Adam + Polyak: 8 launches.
+int iql_critic_phase(oprl_learner* h, const StepRows& rows, int B, hipStream_t st) {
+  const oprl_learner_config& c = h->cfg;
+  const float *s = rows.cur.s, *a = rows.cur.a, *r = rows.cur.r, *d = rows.cur.d, *s2 = rows.cur.s2;
+  const int S = h->S, A = h->A, nc = h->nc;
+  const int n_slices = (B + kR - 1) / kR;
+  const oprl_net& V = h->iql_value;
+  if (c.algo != OPRL_TD3 || nc != 2 || h->iql_base == nullptr) { set_err("internal: implicit-Q-learning critic step without its buffers"); return OPRL_ERR_STATE; }
+  const int wv = V.dims[1];
+  // 1. V(s'), from V as it is before this update's step
+  {
+    MlpArgs f = base_args(h, V, false, B);
+    f.do_fwd = 1;
+    f.x0 = s2; f.k0 = S;
+    f.out = h->iql_vn; f.ldo = 1;
+    RC(launch(f, wv, st));
+  }
+  // 2. the target critics on (s, a)
+  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
+    MlpArgs f = base_args(h, c.critics[j], true, B);
+    f.do_fwd = 1;
+    f.x0 = s; f.k0 = S; f.x1 = a; f.k1 = A;
+    f.out = h->qn + (size_t)j * h->Bmax * h->ldq; f.ldo = h->ldq;
+    return f;
+  }));
+  // 3. V's step: forward on s with the activations stored | the seed rows, u and w | backward from the seed rows
+  {
+    MlpArgs f = base_args(h, V, false, B);
+    f.do_fwd = 1;
+    f.x0 = s; f.k0 = S;
+    with_store(f, h->ws_value, true, true);
+    f.out = h->iql_vs; f.ldo = 1;
+    RC(launch(f, wv, st));
+  }
+  IqlValueArgs t;
+  memset((void*)&t, 0, sizeof t);
+  t.q1 = h->qn; t.q2 = h->qn + (size_t)h->Bmax * h->ldq; t.v = h->iql_vs;
+  t.tau = (float)h->iql_tau; t.omtau = (float)(1.0 - h->iql_tau);
+  t.beta = (float)h->iql_beta; t.clip = (float)h->iql_clip;
+  t.inv_B = 1.0f / (float)B;
+  t.B = B; t.n_slices = n_slices;
+  t.u = h->iql_u; t.seed = h->iql_seed; t.w = h->iql_w;
+  t.part_v = h->iql_part_v; t.part_w = h->iql_part_w;
+  prof_begin(3, st);
+  hipError_t e = launch_iql_value_seed(t, st);
+  prof_end(st);
+  HIPC(e);
+  h->iql_B = B;
+  {
+    MlpArgs f = base_args(h, V, false, B);
+    f.do_bwd = 1;
+    with_store(f, h->ws_value, true, true);
+    f.seed_mode = SEED_PTR;
+    f.seed.p0 = h->iql_seed; f.seed.ld0 = 1;
+    RC(launch(f, wv, st));
+  }
+  // 4. V's dW + Adam, committed to V's counter only
+  {
+    DwArgs dw;
+    dw.items = h->iql_items.data();
+    dw.n_items = (int)h->iql_items.size();
+    dw.total_tiles = h->iql_tiles;
+    dw.ad = adam_scalars(h, h->iql_lr, h->opt_step_value + 1, false, 1.0f);
+    dw.B = B;
+    dw.n_part = tp_generic(h, V, B) ? 4 : 1;
+    dw.dy_tiled = dw.n_part > 1 ? 1 : 0;
+    HIPC(launch_dw_prof(h, dw, st));
+    h->opt_step_value += 1;
+  }
+  // 5. the online critics: TD3's launch, y = r + ((1 - d) gamma) V(s'); 6. their dW + Adam + Polyak
+  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
+    MlpArgs f = critic_sa_args(h, j, s, a, B, true);
+    f.partials = h->part_c + (size_t)j * n_slices * 4;
+    f.seed_mode = SEED_MSE_TD;
+    f.seed = mse_td_seed(h, r, d, B, 0);
+    f.seed.p0 = h->iql_vn; f.seed.p1 = nullptr; f.seed.p2 = nullptr;
+    if (j == 0) { f.seed.y_out = h->ydbg; f.seed.q_out = h->qdbg; }
+    return f;
+  }));
+  return dw_step(h, true, B, st);
+}
+
 int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
   const float *s = rows.cur.s, *a = rows.cur.a, *r = rows.cur.r, *d = rows.cur.d, *s2 = rows.cur.s2;
@@ -1064,6 +1151,10 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
   const int S = h->S, A = h->A, nc = h->nc;
   const int algo = c.algo;
   const int n_slices = (B + kR - 1) / kR;
+  if (h->iql_on) {                 // the implicit-Q-learning mode: its own sequence (the entry points refuse weights)
+    if (rows.w != nullptr) { set_err("internal: importance weights reached the implicit-Q-learning critic step"); return OPRL_ERR_STATE; }
+    return iql_critic_phase(h, rows, B, st);
+  }
   // 1. next action
   {
     const bool use_target_actor = (algo == OPRL_DDPG || algo == OPRL_TD3 || algo == OPRL_D4PG);
@@ -1325,6 +1416,20 @@ int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hip
       f.dact_col0 = S; f.dact_cols = A; f.dact = h->da; f.lddact = A;
       return f;
     }));
+  } else if (h->iql_on) {
+    // implicit Q-learning (oprl_learner_set_iql): no critic runs on (s, pi).  The action gradients are
+    // (2/B) w_b (pi - a) with the weights the critic phase's k_iql_value_seed left, written in full by k_iql_actor_seed
+    if (algo != OPRL_TD3 || h->iql_base == nullptr) { set_err("internal: implicit-Q-learning actor step without its buffers"); return OPRL_ERR_STATE; }
+    IqlActorArgs m;
+    memset((void*)&m, 0, sizeof m);
+    m.pi = h->pi; m.a = rows.cur.a; m.w = h->iql_w;
+    m.two_inv_B = 2.0f / (float)B;
+    m.B = B; m.A = A; m.n_slices = (B + kR - 1) / kR;
+    m.da = h->da; m.part = h->part_a;
+    prof_begin(3, st);
+    hipError_t e = launch_iql_actor_seed(m, st);
+    prof_end(st);
+    HIPC(e);
   } else if (h->bc_alpha > 0.0) {
     // TD3 + BC (oprl_learner_set_bc): where TD3 runs one forward + backward launch of critic 0 from
     // SEED_CONST -1/B, the seed is -lambda/B with lambda = alpha / mean |Q1(s, pi)|, which needs every row's q first — so

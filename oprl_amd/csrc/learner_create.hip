@@ -386,7 +386,12 @@ extern "C" int oprl_learner_sync_params(oprl_learner* h, void* stream) {
     const oprl_net* fn[2] = {&h->fnet[0], &h->fnet[1]};
     RC(repack_nets(fn, 2, 3, (hipStream_t)stream));
   }
-  return repack_nets(nets, h->nc + 1, 3, (hipStream_t)stream, (h->bf16 || h->x2) ? p16 : nullptr, (h->bf16 || h->x2) ? p16t : nullptr, h->planes);
+  RC(repack_nets(nets, h->nc + 1, 3, (hipStream_t)stream, (h->bf16 || h->x2) ? p16 : nullptr, (h->bf16 || h->x2) ? p16t : nullptr, h->planes));
+  if (h->iql_on) {                           // the value net of the implicit-Q-learning mode (f32 learners only; no target)
+    const oprl_net* v[1] = {&h->iql_value};
+    RC(repack_nets(v, 1, 1, (hipStream_t)stream));
+  }
+  return OPRL_OK;
 }
 
 extern "C" int64_t oprl_net_pack_floats(const oprl_net* net) {
@@ -417,6 +422,7 @@ extern "C" int oprl_learner_destroy(oprl_learner* h) {
   dev_free(h->batch_alt);
   if (h->per_seed) (void)hipFree(h->per_seed);
   if (h->bc_seed) (void)hipFree(h->bc_seed);
+  if (h->iql_base) (void)hipFree(h->iql_base);
   dev_free(h->uc_base);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->act_pin) (void)hipHostFree(h->act_pin);

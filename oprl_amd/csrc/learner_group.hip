@@ -44,6 +44,10 @@ extern "C" int oprl_group_create(oprl_learner** learners, int32_t n, oprl_group*
       set_err("oprl_group_create: member %d has the behaviour-cloning mode on (oprl_learner_set_bc); packed learners run the fused launches, which have no BC step", i);
       return OPRL_ERR_STATE;
     }
+    if (h && h->iql_on) {
+      set_err("oprl_group_create: member %d has the implicit-Q-learning mode on (oprl_learner_set_iql); packed learners run the fused launches, which have no value net", i);
+      return OPRL_ERR_STATE;
+    }
     if (!h || (algo0 != OPRL_DDPG && algo0 != OPRL_TD3 && algo0 != OPRL_SAC) || h->cfg.algo != algo0 || !h->fused || h->cfg.export_grads ||
         h->bf16 != learners[0]->bf16 || h->x2 != learners[0]->x2 || h->S != learners[0]->S || h->A != learners[0]->A ||
         h->Bmax != learners[0]->Bmax || h->cfg.hp.policy_freq != learners[0]->cfg.hp.policy_freq ||

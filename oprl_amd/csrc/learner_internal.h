@@ -374,6 +374,20 @@ struct oprl_learner {
   double bc_alpha = 0.0;
   float *bc_seed = nullptr, *bc_scal = nullptr, *bc_part = nullptr;
   int bc_parts = 0, bc_B = 0;
+  // the implicit-Q-learning mode of a TD3 learner (oprl_learner_set_iql, iql_seed.hip): the caller's value
+  // net V(s) (iql_on: the mode), its hyper-parameters and its own Adam step count, and one allocation of its own, made when
+  // the mode is first turned on — V's workspace rows | V(s') | V(s) | u | w | the V seed [Bmax] each | the two tables of
+  // k_iql_value_seed's per-slice sums [slices at Bmax][4] each (the actor's go to part_a); V's dW items with their tiles
+  bool iql_on = false;
+  oprl_net iql_value = {};
+  double iql_tau = 0.0, iql_beta = 0.0, iql_clip = 0.0, iql_lr = 0.0;
+  int opt_step_value = 0;
+  float* iql_base = nullptr;
+  NetWs ws_value;
+  float *iql_vn = nullptr, *iql_vs = nullptr, *iql_u = nullptr, *iql_w = nullptr, *iql_seed = nullptr;
+  float *iql_part_v = nullptr, *iql_part_w = nullptr;
+  std::vector<DwItem> iql_items;
+  int iql_tiles = 0, iql_B = 0;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)

@@ -3,6 +3,7 @@
 #include "learner_internal.h"
 #include "c51_seed.h"
 #include "bc_seed.h"
+#include "iql_seed.h"
 
 #include <cmath>
 #include <vector>
@@ -23,7 +24,8 @@ extern "C" int oprl_learner_read_scalars(oprl_learner* h, float* out_host, int32
                               1.0f / ((float)B * (float)h->nc), st));
   // (REDQ: the actor-step sums of every critic, -mean over the ensemble)
   const int n_qa = c.algo == OPRL_REDQ ? h->nc : 1;
-  HIPC(launch_reduce_partials(h->part_a, n_slices * n_qa, h->scalars, 4, 0.f, -1.0f / ((float)B * (float)n_qa), st));
+  // (the implicit-Q-learning mode: k_iql_actor_seed's sums of w (pi - a)^2, the loss itself and not -q)
+  HIPC(launch_reduce_partials(h->part_a, n_slices * n_qa, h->scalars, 4, 0.f, (h->iql_on ? 1.0f : -1.0f) / ((float)B * (float)n_qa), st));
   // critic 0 alone (the reference logs q1, not the twin mean) and the mean log-density of the actor step
   HIPC(launch_reduce_partials(h->part_c, n_slices, h->scalars, 8, loss_scale, 1.0f / (float)B, st));
   const bool gauss = gauss_actor(h);
@@ -217,6 +219,7 @@ extern "C" int oprl_learner_set_bc(oprl_learner* h, double alpha) {
     set_err("oprl_learner_set_bc: gradient-exporting (export_grads) / data-parallel learners have no BC step");
     return OPRL_ERR_STATE;
   }
+  if (h->iql_on) { set_err("oprl_learner_set_bc: the learner's implicit-Q-learning mode is on (oprl_learner_set_iql), whose actor step runs no critic"); return OPRL_ERR_STATE; }
   if (alpha > 0.0 && h->bc_seed == nullptr) {      // the mode's rows, once: no update allocates
     const size_t n = (size_t)h->Bmax + 4 + (size_t)bc_mix_slices(h->Bmax, h->A);
     float* p = nullptr;
@@ -265,6 +268,175 @@ extern "C" int oprl_bc_seed(const float* q, const float* pi, const float* a, flo
   memset((void*)&m, 0, sizeof m);
   m.pi = pi; m.a = a; m.da = da; m.part = part_sq_out; m.B = B; m.A = A;
   HIPC(launch_bc_mix(m, (hipStream_t)stream));
+  return OPRL_OK;
+}
+
+// ---------------------------------------------------------------- implicit Q-learning
+// The IQL mode of a TD3 learner (learner.hip iql_critic_phase / actor_phase).  Every refusal comes before any GPU work and
+// changes nothing.
+namespace {
+// (as the kernels see them, floats: neither overflowing nor flushed to zero)
+bool iql_hparams_ok(const char* who, double expectile, double beta, double adv_clip) {
+  if (!std::isfinite(expectile) || !(expectile > 0.0 && expectile < 1.0) || !((float)expectile > 0.f) || !((float)(1.0 - expectile) > 0.f)) {
+    set_err("%s: expectile=%g is not a number inside (0, 1)", who, expectile);
+    return false;
+  }
+  if (!std::isfinite(beta) || beta < 0.0 || !std::isfinite((float)beta)) { set_err("%s: beta=%g is not a finite number >= 0", who, beta); return false; }
+  if (!std::isfinite(adv_clip) || !((float)adv_clip > 0.f) || !std::isfinite((float)adv_clip)) {
+    set_err("%s: adv_clip=%g is not a finite number > 0", who, adv_clip);
+    return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int oprl_learner_set_iql(oprl_learner* h, const oprl_net* value, double expectile, double beta, double adv_clip,
+                                    double lr_value) {
+  if (!h) { set_err("oprl_learner_set_iql: null learner handle"); return OPRL_ERR_INVALID; }
+  if (value == nullptr) {          // off: plain TD3 again (the rows stay for the next turn-on; V's step count is kept)
+    h->iql_on = false;
+    return OPRL_OK;
+  }
+  if (h->cfg.algo != OPRL_TD3) {
+    set_err("oprl_learner_set_iql: implicit Q-learning is a mode of TD3 learners (algo %d): twin critics and a tanh actor", h->cfg.algo);
+    return OPRL_ERR_INVALID;
+  }
+  if (h->bf16 || h->x2) { set_err("oprl_learner_set_iql: the mode runs the exact-fp32 generic launch sequence only (precision f32)"); return OPRL_ERR_INVALID; }
+  if (h->cfg.hp.policy_freq != 1) {
+    set_err("oprl_learner_set_iql: policy_freq=%d; implicit Q-learning takes its actor step and the critics' Polyak step on every update (policy_freq 1)", h->cfg.hp.policy_freq);
+    return OPRL_ERR_INVALID;
+  }
+  if (!iql_hparams_ok("oprl_learner_set_iql", expectile, beta, adv_clip)) return OPRL_ERR_INVALID;
+  if (!std::isfinite(lr_value) || !(lr_value > 0.0) || !((float)lr_value > 0.f) || !std::isfinite((float)lr_value)) {
+    set_err("oprl_learner_set_iql: lr_value=%g is not a finite number > 0", lr_value);
+    return OPRL_ERR_INVALID;
+  }
+  int wv = 0;
+  RC(check_net(*value, "oprl_learner_set_iql: value net", &wv));      // (layer count, widths, theta, pack: what the generic path takes)
+  if (value->dims[0] != h->S || value->dims[value->n_layers] != 1) {
+    set_err("oprl_learner_set_iql: the value net maps %d inputs to %d outputs; V(s) takes the learner's state_dim=%d and has one output",
+            value->dims[0], value->dims[value->n_layers], h->S);
+    return OPRL_ERR_INVALID;
+  }
+  if (!value->adam_m || !value->adam_v) { set_err("oprl_learner_set_iql: the value net has no Adam moments (adam_m / adam_v)"); return OPRL_ERR_INVALID; }
+  if (value->theta_target != nullptr || value->grad != nullptr) {
+    set_err("oprl_learner_set_iql: the value net has a target or a gradient arena; V has no target net and the mode exports no gradients");
+    return OPRL_ERR_INVALID;
+  }
+  // (a member of a group is a fused learner: said first, so that the message names the reason that cannot be lifted)
+  if (h->group_member) { set_err("oprl_learner_set_iql: the learner is a member of a group (packed learners run the fused launches, which have no value net)"); return OPRL_ERR_STATE; }
+  if (h->fused) {
+    set_err("oprl_learner_set_iql: the learner's fused launch form is on, which has no value net; create it with no_fuse");
+    return OPRL_ERR_STATE;
+  }
+  if (h->cfg.export_grads || h->rccl.comm != nullptr || h->p2p_ok) {
+    set_err("oprl_learner_set_iql: gradient-exporting (export_grads) / data-parallel learners have no implicit-Q-learning step");
+    return OPRL_ERR_STATE;
+  }
+  if (h->bc_alpha > 0.0) { set_err("oprl_learner_set_iql: the learner's behaviour-cloning mode is on (oprl_learner_set_bc); turn it off first"); return OPRL_ERR_STATE; }
+  // the mode's rows, once per shape of V: no update allocates
+  bool same = h->iql_base != nullptr && h->iql_value.n_layers == value->n_layers;
+  for (int l = 0; same && l <= value->n_layers; ++l) same = h->iql_value.dims[l] == value->dims[l];
+  if (!same) {
+    const size_t Bm = (size_t)h->Bmax, slices = (Bm + kR - 1) / kR;
+    // (Pool::take rounds every block up to 256 bytes: 64 floats of slack for each of the 7 blocks behind the workspace)
+    const size_t n = net_ws_floats(*value, h->Bmax) + 5 * Bm + 2 * slices * 4 + 8 * 64;
+    float* p = nullptr;
+    if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) { set_err("hipMalloc(%zu) failed (implicit-Q-learning rows)", n * sizeof(float)); return OPRL_ERR_NOMEM; }
+    hipError_t e = hipMemset(p, 0, n * sizeof(float));
+    if (e != hipSuccess) { (void)hipFree(p); HIPC(e); }
+    if (h->iql_base != nullptr) (void)hipFree(h->iql_base);
+    h->iql_base = p;
+    Pool pool;
+    pool.base = reinterpret_cast<char*>(p); pool.cap = n * sizeof(float);
+    h->ws_value = NetWs{};
+    alloc_net_ws(pool, *value, h->Bmax, &h->ws_value);
+    h->iql_vn = pool.take<float>(Bm);
+    h->iql_vs = pool.take<float>(Bm);
+    h->iql_u = pool.take<float>(Bm);
+    h->iql_w = pool.take<float>(Bm);
+    h->iql_seed = pool.take<float>(Bm);
+    h->iql_part_v = pool.take<float>(slices * 4);
+    h->iql_part_w = pool.take<float>(slices * 4);
+    if (pool.used > pool.cap) { set_err("internal: the implicit-Q-learning rows overran their allocation"); h->iql_on = false; return OPRL_ERR_STATE; }
+    h->iql_B = 0;
+  }
+  h->iql_value = *value;
+  h->iql_items.clear();
+  h->iql_tiles = 0;
+  fill_items(h->iql_value, h->ws_value, h->iql_items, &h->iql_tiles);
+  h->iql_tau = expectile; h->iql_beta = beta; h->iql_clip = adv_clip; h->iql_lr = lr_value;
+  h->iql_on = true;
+  return OPRL_OK;
+}
+
+extern "C" int oprl_learner_read_iql(oprl_learner* h, float out_host[8], void* stream) {
+  if (!h || !out_host) { set_err("oprl_learner_read_iql: null argument"); return OPRL_ERR_INVALID; }
+  if (h->iql_base == nullptr) { set_err("oprl_learner_read_iql: the implicit-Q-learning mode was never on (oprl_learner_set_iql)"); return OPRL_ERR_STATE; }
+  hipStream_t st = (hipStream_t)stream;
+  const int B = h->iql_B, n = B > 0 ? (B + kR - 1) / kR : 0;
+  std::vector<float> pv((size_t)n * 4, 0.f), pw((size_t)n * 4, 0.f), pa((size_t)n * 4, 0.f);
+  if (n > 0) {
+    HIPC(hipMemcpyAsync(pv.data(), h->iql_part_v, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(pw.data(), h->iql_part_w, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, st));
+    HIPC(hipMemcpyAsync(pa.data(), h->part_a, sizeof(float) * 4 * n, hipMemcpyDeviceToHost, st));
+  }
+  HIPC(hipStreamSynchronize(st));
+  RC(check_device_error(h));
+  double s[6] = {0, 0, 0, 0, 0, 0};                 // the per-slice sums, in slice order
+  for (int i = 0; i < n; ++i) {
+    s[0] += (double)pv[4 * i]; s[1] += (double)pv[4 * i + 1]; s[2] += (double)pv[4 * i + 2];
+    s[3] += (double)pw[4 * i + 1]; s[4] += (double)pw[4 * i + 2];
+    s[5] += (double)pa[4 * i + 1];
+  }
+  // V loss | mean V(s) | mean u | mean w | share of rows at the clip | the weighted cloning loss | two spares
+  for (int k = 0; k < 6; ++k) out_host[k] = n > 0 ? (float)(s[k] / (double)B) : 0.f;
+  out_host[6] = out_host[7] = 0.f;
+  return OPRL_OK;
+}
+
+// V's Adam step count (get_counters / set_counters carry four numbers and stay as they are)
+extern "C" int oprl_learner_get_iql_step(oprl_learner* h, int64_t* out_host) {
+  if (!h || !out_host) { set_err("oprl_learner_get_iql_step: null argument"); return OPRL_ERR_INVALID; }
+  *out_host = h->opt_step_value;
+  return OPRL_OK;
+}
+
+extern "C" int oprl_learner_set_iql_step(oprl_learner* h, int64_t step) {
+  if (!h) { set_err("oprl_learner_set_iql_step: null learner handle"); return OPRL_ERR_INVALID; }
+  if (step < 0 || step > 0x7fffffffLL) { set_err("oprl_learner_set_iql_step: step %lld out of range", (long long)step); return OPRL_ERR_INVALID; }
+  h->opt_step_value = (int)step;
+  return OPRL_OK;
+}
+
+extern "C" int oprl_iql_seed(const float* q1, const float* q2, const float* v, const float* pi, const float* a, double expectile,
+                             double beta, double adv_clip, int32_t B, int32_t A, float* u_out, float* seed_out, float* w_out,
+                             float* da_out, float* part_v_out, float* part_w_out, float* part_a_out, void* stream) {
+  if (!q1 || !q2 || !v || !pi || !a || !u_out || !seed_out || !w_out || !da_out || !part_v_out || !part_w_out || !part_a_out) {
+    set_err("oprl_iql_seed: null argument");
+    return OPRL_ERR_INVALID;
+  }
+  if (B < 1 || A < 1 || (int64_t)B * A > (1 << 30)) {
+    set_err("oprl_iql_seed: need B >= 1 (B=%d), A >= 1 (A=%d) and B A <= 2^30", B, A);
+    return OPRL_ERR_INVALID;
+  }
+  if (!iql_hparams_ok("oprl_iql_seed", expectile, beta, adv_clip)) return OPRL_ERR_INVALID;
+  IqlValueArgs t;
+  memset((void*)&t, 0, sizeof t);
+  t.q1 = q1; t.q2 = q2; t.v = v;
+  t.tau = (float)expectile; t.omtau = (float)(1.0 - expectile);
+  t.beta = (float)beta; t.clip = (float)adv_clip;
+  t.inv_B = 1.0f / (float)B;
+  t.B = B; t.n_slices = (B + kR - 1) / kR;
+  t.u = u_out; t.seed = seed_out; t.w = w_out; t.part_v = part_v_out; t.part_w = part_w_out;
+  HIPC(launch_iql_value_seed(t, (hipStream_t)stream));
+  IqlActorArgs m;
+  memset((void*)&m, 0, sizeof m);
+  m.pi = pi; m.a = a; m.w = w_out;
+  m.two_inv_B = 2.0f / (float)B;
+  m.B = B; m.A = A; m.n_slices = t.n_slices;
+  m.da = da_out; m.part = part_a_out;
+  HIPC(launch_iql_actor_seed(m, (hipStream_t)stream));
   return OPRL_OK;
 }
 

@@ -26,6 +26,10 @@ int per_check(const oprl_learner* h, const char* who) {
     return OPRL_ERR_STATE;
   }
   if (h->group_member) { set_err("%s: the learner is a member of a group (packed learners gather their own rows)", who); return OPRL_ERR_STATE; }
+  if (h->iql_on) {
+    set_err("%s: the learner's implicit-Q-learning mode is on (oprl_learner_set_iql), whose value and actor steps take no importance weights", who);
+    return OPRL_ERR_STATE;
+  }
   if (h->fused) {
     set_err("%s: the learner's fused launch form is on, which applies no importance weights; create it with no_fuse", who);
     return OPRL_ERR_STATE;
