@@ -12,11 +12,12 @@ from typing import Callable
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 from oprl.buffers.episodic_buffer import EpisodicReplayBuffer  # noqa: E402
+from oprl.buffers.hindsight_buffer import HindsightEpisodicReplayBuffer  # noqa: E402
 from oprl.buffers.nstep_buffer import NStepEpisodicReplayBuffer  # noqa: E402
 from oprl.buffers.prioritized_buffer import PrioritizedEpisodicReplayBuffer  # noqa: E402
 from oprl.environment import make_env as build_env  # noqa: E402
 from oprl.logging import make_text_logger_func  # noqa: E402
-from oprl.parse_args import check_per, parse_args  # noqa: E402
+from oprl.parse_args import check_her, check_per, parse_args  # noqa: E402
 from oprl.runners.config import CommonParameters  # noqa: E402
 from oprl.runners.train import run_training  # noqa: E402
 
@@ -42,7 +43,14 @@ class TrainingScript:
         if self.per and not self.takes_per:
             raise ValueError(f"--per: {self.algo_name} does not train from prioritized replay (its loss takes no "
                              "importance weights yet)")
+        self.her = check_her(self.args)      # --her: hindsight replay, refused with --per and with --n-step > 1
         probe = self.make_env(seed=0)
+        self.goal_layout = getattr(probe, "goal_layout", None)
+        if self.her and self.goal_layout is None:
+            raise ValueError(f"--her: the environment {self.args.env!r} has no goal layout (achieved and desired goal "
+                             "inside its state rows); hindsight replay needs a goal-conditioned one, e.g. "
+                             "synthetic:goal-reach-2d")
+        self.episode_length = int(getattr(probe, "episode_length", 1000))
         self.state_dim = int(probe.observation_space.shape[0])
         self.action_dim = int(probe.action_space.shape[0])
         self.config = CommonParameters(state_dim=self.state_dim, action_dim=self.action_dim, num_steps=TRAIN_STEPS,
@@ -65,6 +73,9 @@ class TrainingScript:
         if self.args.n_step > 1:        # n-step returns: the sampler discounts with the ALGORITHM's gamma
             gamma = next(f.default for f in fields(self.algo_cls) if f.name == "gamma")
             return NStepEpisodicReplayBuffer(n_step=self.args.n_step, gamma=gamma, **kw).create()
+        if self.her:                    # hindsight goals: the layout and the reward's threshold are the environment's
+            return HindsightEpisodicReplayBuffer(her_ratio=self.args.her_ratio, strategy=self.args.her_strategy,
+                                                 max_episode_lenth=self.episode_length, **self.goal_layout, **kw).create()
         if self.per:
             return PrioritizedEpisodicReplayBuffer(**kw).create()
         return EpisodicReplayBuffer(**kw).create()

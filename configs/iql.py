@@ -38,6 +38,8 @@ script = TrainingScript(IQL, "IQL", estimate_q_every=0, log_every=5000, extra_fl
 if script.args.num_envs > 1 or script.args.open_episodes:
     raise ValueError("--num-envs > 1 / --open-episodes: IQL trains from a fixed dataset, no environment is stepped "
                      "during training (evaluation runs its own)")
+if script.her:
+    raise ValueError("--her: IQL trains from a fixed dataset here; hindsight replay is wired into the online scripts")
 if script.args.seeds != 1:
     raise ValueError("--seeds > 1: one offline run per invocation (--start_seed picks its seed)")
 # the names a reference-style script defines at module level

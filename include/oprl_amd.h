@@ -475,6 +475,30 @@ int oprl_replay_sample_nstep(oprl_replay* h, int32_t B, const int64_t* idx, uint
                              float* out_s, float* out_a, float* out_r, float* out_d, float* out_s2, int32_t* out_ep,
                              int32_t* out_step, int32_t* out_m, void* stream);
 
+/* ---- hindsight experience replay (Andrychowicz et al., NeurIPS 2017) ---------------------------------
+ * A flat state row carries the achieved goal at [ag_off, ag_off + G) and the desired goal at [g_off, g_off + G).  A
+ * replay in hindsight mode draws the slot (e, t) as oprl_replay_sample does and, with c = len_e - 1 - t later rows of
+ * the episode that are always written, relabels the row iff c >= 1 and U < (float)ratio, U = (r.y >> 8) 2^-24 of the
+ * draw's own Philox output r:  t' = t + bounded(r.z, c) (strategy 0, future) or len_e - 2 (strategy 1, final),
+ * g' = achieved goal of states[e, t' + 1];  s and s2 get g' as their desired goal, a and d are verbatim, and
+ *   r = dist2 <= (float)(threshold^2) ? 0 : -1  (reward 0, sparse)   or   r = -sqrtf(dist2)  (reward 1, dense),
+ * dist2 = the float32 sum over k = 0 .. G-1, in order, of (achieved(s2)_k - g'_k)^2, every operation rounded once.
+ * Rows that are not relabelled are oprl_replay_sample's bit for bit.
+ * set_her: 1 <= G <= 16, both ranges inside [0, state_dim) and disjoint, 0 <= ratio <= 1, threshold finite and >= 0,
+ * strategy and reward 0 or 1 (else OPRL_ERR_INVALID); G = 0 switches the mode off (the other arguments are not read).
+ * With the mode on oprl_replay_sample and the learners' step_n / step_act / dp_step_n gather relabelled rows;
+ * oprl_group_step_n refuses such a replay.  Not combined with n-step returns or prioritized replay: set_her on such a
+ * handle, and oprl_replay_set_nstep(n > 1) / oprl_replay_prio_enable on a hindsight handle, return OPRL_ERR_STATE.
+ * Host state only; replays that never call it are unchanged. */
+int oprl_replay_set_her(oprl_replay* h, int32_t ag_off, int32_t g_off, int32_t G, double ratio, int32_t strategy,
+                        int32_t reward, double threshold);
+/* oprl_replay_sample through the hindsight gather kernel (OPRL_ERR_STATE when the mode is off) and, when out_future is
+ * non-NULL, t' per relabelled row and -1 per other row (int32[B]).  With idx given the slots are the caller's; the
+ * relabelling still follows (seed, counter). */
+int oprl_replay_sample_her(oprl_replay* h, int32_t B, const int64_t* idx, uint64_t seed, uint64_t counter,
+                           float* out_s, float* out_a, float* out_r, float* out_d, float* out_s2, int32_t* out_ep,
+                           int32_t* out_step, int32_t* out_future, void* stream);
+
 /* ---- prioritized replay (Schaul et al., ICLR 2016, proportional variant) ------------------------------------------
  * A sum tree over the E·L slots of a replay, in HBM next to it: leaf e·L + t is the priority of slot
  * (e, t).  A slot is live when e < episodes_counter and t < ep_lens[e] (the set oprl_replay_sample draws from); every

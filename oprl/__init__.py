@@ -10,8 +10,8 @@ _SUBMODULES = [
     "algos", "algos.protocols", "algos.base_algorithm", "algos.nn_models", "algos.nn_functions",
     "algos.ddpg", "algos.td3", "algos.sac", "algos.tqc", "algos.redq", "algos.d4pg", "algos.td3_bc", "algos.iql",
     "buffers", "buffers.protocols", "buffers.episodic_buffer", "buffers.prioritized_buffer", "buffers.nstep_buffer",
-    "buffers.offline_dataset",
-    "environment", "environment.protocols", "environment.make_env",
+    "buffers.offline_dataset", "buffers.hindsight_buffer",
+    "environment", "environment.protocols", "environment.make_env", "environment.synthetic_goal",
     "runners", "runners.config", "runners.train", "runners.train_distrib",
     "trainers", "trainers.protocols", "trainers.base_trainer", "trainers.vec_trainer", "trainers.offline_trainer",
     "distrib", "distrib.queue", "distrib.env_worker", "distrib.policy_update_worker",

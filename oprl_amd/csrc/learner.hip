@@ -1783,6 +1783,11 @@ int RowStager::check(const char* who, const oprl_learner* h, const oprl_replay* 
             who, *nstep, gamma, h->cfg.hp.gamma);
     return OPRL_ERR_INVALID;
   }
+  // A hindsight replay (oprl_replay_set_her) is read through its own gather in the same way.
+  if (replay_her(replay) > 0 && packed) {
+    set_err("%s: the replay relabels goals in hindsight (oprl_replay_set_her); packed learners take plain replays only", who);
+    return OPRL_ERR_STATE;
+  }
   return OPRL_OK;
 }
 
@@ -1860,7 +1865,8 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
   int nstep = 1;
   RC(RowStager::check("step_n", h, replay, false, K, B, &nstep));
   RowStager stg;
-  if (nstep == 1 && use_fused(h, B)) {
+  const bool plain = nstep == 1 && replay_her(replay) == 0;      // else: the sample + update loop at the end
+  if (plain && use_fused(h, B)) {
     RC(stg.open("step_n", h, replay, seed, stream));
     // k_ddpg_chain: up to chain_max updates per launch, the rows of update u + 1 staged by update u inside the launch
     if (chain_ok(h, B)) return chain_loop(h, stg, K, B, stream);
@@ -1879,7 +1885,7 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
     }
     return OPRL_OK;
   }
-  if (nstep == 1 && h->cfg.algo == OPRL_TQC && h->batch_alt != nullptr && !h->sw.no_gather_ride && K > 1) {
+  if (plain && h->cfg.algo == OPRL_TQC && h->batch_alt != nullptr && !h->sw.no_gather_ride && K > 1) {
     // the rows of update k + 1 are gathered by riders of update k's k_lw_dact launch (same draw as k_replay_gather)
     // into the other of two sets of batch rows; only the first update's rows are a launch
     RC(stg.open("step_n", h, replay, seed, stream));

@@ -389,6 +389,8 @@ extern "C" int oprl_replay_sample(oprl_replay* h, int32_t B, const int64_t* idx,
   }
   if (h->nstep > 1)      // n-step mode (oprl_replay_set_nstep): the same draw, n-step rows (replay_nstep.hip)
     return oprl_replay_sample_nstep(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
+  if (h->her.G > 0)      // hindsight mode (oprl_replay_set_her): the same draw, relabelled rows (replay_her.hip)
+    return oprl_replay_sample_her(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
   if (h->n_transitions <= 0 || h->n_eps <= 0) {
     set_err("oprl_replay_sample: buffer is empty (np.random.randint(0, 0) raises in the reference)");
     return OPRL_ERR_STATE;

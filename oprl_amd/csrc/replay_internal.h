@@ -36,6 +36,14 @@ struct PrioTree {
 // Called by oprl_replay_flush and oprl_replay_write_rows after their copies, on their stream.
 constexpr int kNstepMax = 16;       // largest n of the n-step sampler (replay_nstep.hip: one lane per (sample, step))
 
+// Hindsight mode of a replay (oprl_replay_set_her, replay_her.hip).  G = 0: off.
+constexpr int kHerMaxGoal = 16;     // largest goal dimension (replay_her.hip: one lane per (sample, goal element))
+struct HerMode {
+  int ag_off = 0, g_off = 0, G = 0;     // achieved goal [ag_off, ag_off + G), desired goal [g_off, g_off + G) of a state row
+  int strategy = 0, reward = 0;         // 0 future | 1 final;  0 sparse | 1 dense
+  double ratio = 0.8, threshold = 0.0;  // relabelled share of the eligible rows; the sparse reward's distance bound
+};
+
 int prio_flush(oprl_replay* h, const float* rows, int n_rows, int rowlen, int ends_first, int ends_n, hipStream_t st);
 void prio_free(PrioTree* p);
 
@@ -78,6 +86,8 @@ struct oprl_replay {
   // n-step mode (oprl_replay_set_nstep): with nstep > 1 oprl_replay_sample gathers n-step rows
   int nstep = 1;
   double nstep_gamma = 1.0;
+  // hindsight mode (oprl_replay_set_her): with her.G > 0 oprl_replay_sample gathers relabelled rows
+  oprl::HerMode her;
   // oprl_replay_write_rows (replay_rows.hip): double-buffered pinned staging of its own for up to kRowsMax
   // records of reclen floats, allocated by the first call
   bool rows_ready = false;

@@ -203,6 +203,10 @@ extern "C" int oprl_replay_set_nstep(oprl_replay* h, int32_t n, double gamma) {
     set_err("oprl_replay_set_nstep: this replay is prioritized; n-step returns over the sum tree are not supported");
     return OPRL_ERR_STATE;
   }
+  if (h->her.G > 0 && n > 1) {
+    set_err("oprl_replay_set_nstep: this replay relabels goals in hindsight (oprl_replay_set_her); n-step returns over relabelled rows are not supported");
+    return OPRL_ERR_STATE;
+  }
   h->nstep = n;
   h->nstep_gamma = gamma;
   return OPRL_OK;

@@ -352,6 +352,10 @@ extern "C" int oprl_replay_prio_enable(oprl_replay* h, double alpha, double eps,
     set_err("oprl_replay_prio_enable: this replay samples %d-step returns (oprl_replay_set_nstep); the sum tree over n-step rows is not supported", h->nstep);
     return OPRL_ERR_STATE;
   }
+  if (h->her.G > 0) {
+    set_err("oprl_replay_prio_enable: this replay relabels goals in hindsight (oprl_replay_set_her); the sum tree over relabelled rows is not supported");
+    return OPRL_ERR_STATE;
+  }
   hipStream_t st = (hipStream_t)stream;
   int rc = oprl_replay_flush(h, stream);          // the episode table the leaves start from
   if (rc != OPRL_OK) return rc;

@@ -8,17 +8,22 @@ build.  What this factory serves is the synthetic stand-in of synthetic.py, and 
 * a bare dm_control task name is accepted so that the reference's config scripts and command lines keep
   running, but a warning names the substitution and the environment reports ``env_family == "synthetic"``
   (never "dm_control"), which runners log;
+* ``synthetic:goal-reach-2d`` / ``synthetic:goal-reach-3d`` are the goal-conditioned point mass of synthetic_goal.py
+  (sparse reward, a ``goal_layout`` for hindsight replay); they have no bare spelling;
 * any other name (gymnasium ``Ant-v4``, ``Safety*``) raises: there is no stand-in with made-up dims."""
 import logging
 
 from oprl_amd.environment.protocols import EnvProtocol
 from oprl_amd.environment.synthetic import DM_CONTROL_DIMS, SyntheticEnv
+from oprl_amd.environment.synthetic_goal import GOAL_TASKS, SyntheticGoalEnv
 
 PREFIX = "synthetic:"
 _warned: set[str] = set()
 
 
 def make_env(name: str, seed: int = 0) -> EnvProtocol:
+    if name.startswith(PREFIX) and name[len(PREFIX):] in GOAL_TASKS:
+        return SyntheticGoalEnv(name[len(PREFIX):], seed=seed)
     if name.startswith(PREFIX):
         return SyntheticEnv(name[len(PREFIX):], seed=seed)
     if name in DM_CONTROL_DIMS:

@@ -67,7 +67,29 @@ def parse_args(extra=()) -> argparse.Namespace:
     parser.add_argument("--open-episodes", action="store_true",
                         help="with --num-envs N > 1: N open episodes in the replay, every iteration's N transitions "
                              "written at once (next states included) instead of whole episodes when they end")
+    # extension: hindsight experience replay (buffers/hindsight_buffer.py)
+    parser.add_argument("--her", action="store_true",
+                        help="hindsight experience replay: the sampler relabels goals from later steps of the same episode "
+                             "and recomputes the sparse reward (goal-conditioned environments, e.g. synthetic:goal-reach-2d; "
+                             "not with --per or --n-step > 1)")
+    parser.add_argument("--her-ratio", type=float, default=0.8,
+                        help="with --her: the relabelled share of the sampled rows that can be relabelled (0.8 = 4 hindsight goals per stored one)")
+    parser.add_argument("--her-strategy", type=str, default="future", choices=("future", "final"),
+                        help="with --her: goals from a uniformly drawn later step of the episode (future) or from its last one (final)")
     return parser.parse_args()
+
+
+def check_her(args: argparse.Namespace) -> bool:
+    """Is ``--her`` given?  Raises ValueError when it comes with ``--per`` or ``--n-step > 1``: the replay refuses both
+    combinations, and the scripts say so before anything is built."""
+    if not getattr(args, "her", False):
+        return False
+    if getattr(args, "per", False):
+        raise ValueError("--her with --per: hindsight goals over the sum tree are not supported; give one of the two")
+    if getattr(args, "n_step", 1) > 1:
+        raise ValueError(f"--her with --n-step {args.n_step}: hindsight goals over n-step rows are not supported; give "
+                         "one of the two")
+    return True
 
 
 def parse_args_distrib() -> argparse.Namespace:
