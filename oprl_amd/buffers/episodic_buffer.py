@@ -363,12 +363,17 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         self._sync_lens()
         return self._handle
 
-    def sample(self, batch_size: int, inds: t.Tensor | npt.NDArray | None = None,
-               return_indices: bool = False):
-        """Uniform (with replacement) minibatch of live transitions, including the
-        in-progress episode's tail — reference semantics (:123-133).  ``inds``:
-        optional injected flat indices (what ``np.random.randint(0, len, B)``
-        would return) for parity tests; None draws them on device."""
+    def _empty_rows(self, B: int):
+        """The five outputs of a sampler call: (state, action, reward, done, next_state) for B rows, uninitialised."""
+        S, A, dev = self.state_dim, self.action_dim, self._dev
+        return (t.empty((B, S), dtype=t.float32, device=dev), t.empty((B, A), dtype=t.float32, device=dev),
+                t.empty((B, 1), dtype=t.float32, device=dev), t.empty((B, 1), dtype=t.float32, device=dev),
+                t.empty((B, S), dtype=t.float32, device=dev))
+
+    def _sample(self, fn: str, batch_size: int, inds, return_indices: bool, extra: bool | None = None):
+        """One call of the gather entry point ``fn`` — oprl_replay_sample, or with ``extra`` not None one of its
+        n-step / hindsight forms, which take one more optional int32[B] output — at this buffer's (seed, counter),
+        which then moves on.  Returns ``(rows, (ep, step) | None, extra | None)``."""
         self.check_created()
         if self._handle is None:
             raise RuntimeError("sample() runs on the MI355X gather kernel; create the buffer with "
@@ -376,30 +381,37 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         if self._number_transitions <= 0:
             raise ValueError("cannot sample from an empty replay buffer")
         self._sync_lens()
-        B, S, A, dev = int(batch_size), self.state_dim, self.action_dim, self._dev
-        out_s = t.empty((B, S), dtype=t.float32, device=dev)
-        out_a = t.empty((B, A), dtype=t.float32, device=dev)
-        out_r = t.empty((B, 1), dtype=t.float32, device=dev)
-        out_d = t.empty((B, 1), dtype=t.float32, device=dev)
-        out_s2 = t.empty((B, S), dtype=t.float32, device=dev)
+        B, dev = int(batch_size), self._dev
+        rows = self._empty_rows(B)
         idx = None
         if inds is not None:
             idx = t.as_tensor(inds).to(device=dev, dtype=t.int64).contiguous()
             if idx.numel() != B:
                 raise ValueError("inds must hold batch_size indices")
-        ep = st = None
+        ep = st = x = None
         if return_indices:
             ep = t.empty(B, dtype=t.int32, device=dev)
             st = t.empty(B, dtype=t.int32, device=dev)
+        if extra:
+            x = t.empty(B, dtype=t.int32, device=dev)
+        ints = [_capi.ptr(ep), _capi.ptr(st)]
+        if extra is not None:       # (oprl_replay_sample itself has no such argument)
+            ints.append(_capi.ptr(x))
         with _capi.on_device(dev):
-            _capi.check(self._lib.oprl_replay_sample(
-                self._handle, B, _capi.ptr(idx), self.seed, self._sample_counter, _capi.ptr(out_s),
-                _capi.ptr(out_a), _capi.ptr(out_r), _capi.ptr(out_d), _capi.ptr(out_s2),
-                _capi.ptr(ep), _capi.ptr(st), _capi.current_stream()), "oprl_replay_sample")
+            _capi.check(getattr(self._lib, fn)(
+                self._handle, B, _capi.ptr(idx), self.seed, self._sample_counter, *[_capi.ptr(v) for v in rows],
+                *ints, _capi.current_stream()), fn)
         self._sample_counter += 1
-        if return_indices:
-            return (out_s, out_a, out_r, out_d, out_s2), (ep, st)
-        return out_s, out_a, out_r, out_d, out_s2
+        return rows, ((ep, st) if return_indices else None), x
+
+    def sample(self, batch_size: int, inds: t.Tensor | npt.NDArray | None = None,
+               return_indices: bool = False):
+        """Uniform (with replacement) minibatch of live transitions, including the
+        in-progress episode's tail — reference semantics (:123-133).  ``inds``:
+        optional injected flat indices (what ``np.random.randint(0, len, B)``
+        would return) for parity tests; None draws them on device."""
+        rows, pair, _ = self._sample("oprl_replay_sample", batch_size, inds, return_indices)
+        return (rows, pair) if return_indices else rows
 
     # ---- checkpoint (SURVEY.md 8f N4) ------------------------------------------------------
     def state_dict(self) -> dict:

@@ -54,41 +54,8 @@ class NStepEpisodicReplayBuffer(EpisodicReplayBuffer):
                return_steps: bool = False):
         """``(state, action, R, done', state_{t+m})`` for uniformly drawn slots; ``inds`` and ``return_indices`` as in
         the base class (the (episode, step) pairs are those of the FIRST step); ``return_steps`` appends m (int32[B])."""
-        self.check_created()
-        if self._handle is None:
-            raise RuntimeError("sample() runs on the MI355X gather kernel; create the buffer with "
-                               "device='cuda' (there is no CPU sampler)")
-        if self._number_transitions <= 0:
-            raise ValueError("cannot sample from an empty replay buffer")
-        self._sync_lens()
-        B, S, A, dev = int(batch_size), self.state_dim, self.action_dim, self._dev
-        out_s = t.empty((B, S), dtype=t.float32, device=dev)
-        out_a = t.empty((B, A), dtype=t.float32, device=dev)
-        out_r = t.empty((B, 1), dtype=t.float32, device=dev)
-        out_d = t.empty((B, 1), dtype=t.float32, device=dev)
-        out_s2 = t.empty((B, S), dtype=t.float32, device=dev)
-        idx = None
-        if inds is not None:
-            idx = t.as_tensor(inds).to(device=dev, dtype=t.int64).contiguous()
-            if idx.numel() != B:
-                raise ValueError("inds must hold batch_size indices")
-        ep = st = m = None
-        if return_indices:
-            ep = t.empty(B, dtype=t.int32, device=dev)
-            st = t.empty(B, dtype=t.int32, device=dev)
-        if return_steps:
-            m = t.empty(B, dtype=t.int32, device=dev)
-        with _capi.on_device(dev):
-            _capi.check(self._lib.oprl_replay_sample_nstep(
-                self._handle, B, _capi.ptr(idx), self.seed, self._sample_counter, _capi.ptr(out_s),
-                _capi.ptr(out_a), _capi.ptr(out_r), _capi.ptr(out_d), _capi.ptr(out_s2),
-                _capi.ptr(ep), _capi.ptr(st), _capi.ptr(m), _capi.current_stream()), "oprl_replay_sample_nstep")
-        self._sample_counter += 1
-        out = [(out_s, out_a, out_r, out_d, out_s2)]
-        if return_indices:
-            out.append((ep, st))
-        if return_steps:
-            out.append(m)
+        out = [x for x in self._sample("oprl_replay_sample_nstep", batch_size, inds, return_indices, bool(return_steps))
+               if x is not None]
         return out[0] if len(out) == 1 else tuple(out)
 
     def state_dict(self) -> dict:

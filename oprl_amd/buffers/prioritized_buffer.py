@@ -84,12 +84,8 @@ class PrioritizedEpisodicReplayBuffer(EpisodicReplayBuffer):
         if self._number_transitions <= 0:
             raise ValueError("cannot sample from an empty replay buffer")
         self._sync_lens()
-        B, S, A, dev = int(batch_size), self.state_dim, self.action_dim, self._dev
-        out_s = t.empty((B, S), dtype=t.float32, device=dev)
-        out_a = t.empty((B, A), dtype=t.float32, device=dev)
-        out_r = t.empty((B, 1), dtype=t.float32, device=dev)
-        out_d = t.empty((B, 1), dtype=t.float32, device=dev)
-        out_s2 = t.empty((B, S), dtype=t.float32, device=dev)
+        B, dev = int(batch_size), self._dev
+        out_s, out_a, out_r, out_d, out_s2 = self._empty_rows(B)
         slots = t.empty(B, dtype=t.int32, device=dev)
         w = t.empty(B, dtype=t.float32, device=dev)
         b = self.beta(self._sample_counter) if beta is None else float(beta)

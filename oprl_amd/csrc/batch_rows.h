@@ -24,8 +24,9 @@ __device__ __forceinline__ void load_batch(const BatchSrc& P, int row0, int B, i
       const int i = row0 + tid;
       int e = 0, t = 0;
       if (i < B) {
+        // replay_index.h draw_slot, written out: the call changes this launch's instruction selection (r.x's product)
         const u32x4 rnd = philox4x32_10(
-            u32x4{(uint32_t)P.counter, (uint32_t)(P.counter >> 32), (uint32_t)i, 0x5a17u},
+            u32x4{(uint32_t)P.counter, (uint32_t)(P.counter >> 32), (uint32_t)i, kUniformWord},
             (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
         const long ind = (long)bounded_u32(rnd.x, (uint32_t)P.n_transitions);
         long start = 0;
@@ -137,8 +138,8 @@ __device__ __forceinline__ void prefetch_rows_direct(const PrefetchJob& J, int s
   if (tid < kR) {
     const int i = row0 + tid;
     int e = 0, t = 0;
-    if (i < B) {
-      const u32x4 rnd = philox4x32_10(u32x4{(uint32_t)P.counter, (uint32_t)(P.counter >> 32), (uint32_t)i, 0x5a17u},
+    if (i < B) {        // (draw_slot written out, as in load_batch)
+      const u32x4 rnd = philox4x32_10(u32x4{(uint32_t)P.counter, (uint32_t)(P.counter >> 32), (uint32_t)i, kUniformWord},
                                       (uint32_t)P.seed, (uint32_t)(P.seed >> 32));
       const long ind = (long)bounded_u32(rnd.x, (uint32_t)P.n_transitions);
       long start = 0;

@@ -18,16 +18,13 @@
 #include <vector>
 
 #include "../../include/oprl_amd.h"
+#include "host_err.h"
 #include "kernels.h"
 #include "p2p.h"
 
 namespace oprl {
 
-void set_err(const char* fmt, ...);
-// HIP-event profiler (off by default; zero cost when off): learner.hip
-void prof_fold();
-void prof_begin(int kind, hipStream_t st);
-void prof_end(hipStream_t st);
+void prof_fold();      // (the profiler of host_err.h's prof_begin / prof_end: learner.hip)
 
 // (Learners that share a GPU: the fused phase kernels contain bounded cross-workgroup waits that rely on a launch's
 // workgroups becoming resident together.  An event chain that serialised the phase launches of all learners of a process
@@ -140,24 +137,6 @@ inline int rccl_bind(Rccl& r, const char* path) {
   }
   return OPRL_OK;
 }
-}  // namespace oprl_host
-
-#define HIPC(x)                                                                        \
-  do {                                                                                 \
-    hipError_t _e = (x);                                                               \
-    if (_e != hipSuccess) {                                                            \
-      set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return OPRL_ERR_HIP;                                                             \
-    }                                                                                  \
-  } while (0)
-#define RC(x)                      \
-  do {                             \
-    int _rc = (x);                 \
-    if (_rc != OPRL_OK) return _rc; \
-  } while (0)
-
-namespace oprl_host {
-
 inline long net_param_count(const oprl_net& n) {
   long c = 0;
   for (int l = 0; l < n.n_layers; ++l) c += (long)n.dims[l + 1] * n.dims[l] + n.dims[l + 1];

@@ -9,8 +9,8 @@
 //
 // Because states is [E, L+1, S], state (e,t) and next_state (e,t+1) are ADJACENT
 // rows: one sample reads a single contiguous 2·S-float run, plus A + 1 + 1 floats.
-// A workgroup stages 32 samples' rows in LDS and writes the five output arrays
-// fully coalesced.
+// A workgroup stages 16 samples' rows in LDS and writes the five output arrays
+// fully coalesced (the shape and its pieces: replay_gather.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -18,42 +18,17 @@
 #include <vector>
 
 #include "../../include/oprl_amd.h"
-#include "philox.h"
-#include "replay_index.h"
-#include "replay_internal.h"
+#include "replay_gather.h"
 
-namespace oprl {
-void set_err(const char* fmt, ...);
-void prof_begin(int kind, hipStream_t st);
-void prof_end(hipStream_t st);
-}
-using oprl::set_err;
-
-#define HIPC(x)                                                              \
-  do {                                                                       \
-    hipError_t _e = (x);                                                     \
-    if (_e != hipSuccess) {                                                  \
-      set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return OPRL_ERR_HIP;                                                   \
-    }                                                                        \
-  } while (0)
+using namespace oprl;
 
 namespace {
 
-constexpr int kGatherThreads = 256;
-constexpr int kSamplesPerWg = 16;   // more workgroups, one copy round per thread at walker dims
-constexpr int kStageRows = 4096;
-constexpr int kMaxEndsLds = 2048; // episode-end table entries staged in LDS by the gather  // transitions staged on the host between flushes
+constexpr int kStageRows = 4096;      // transitions staged on the host between flushes
 
 struct GatherArgs {
-  const float *states, *actions, *rewards, *dones;
-  const int* ends;  // cumulative episode ends, [n_eps]
-  int n_eps, L, S, A, B;
-  long n_transitions;
-  const long long* idx;  // or null
-  unsigned long long seed, counter;
-  float *out_s, *out_a, *out_r, *out_d, *out_s2;
-  int *out_ep, *out_step;
+  GatherSrc src;
+  GatherOut out;
 };
 
 __global__ __launch_bounds__(kGatherThreads) void k_replay_gather(const GatherArgs G) {
@@ -63,78 +38,22 @@ __global__ __launch_bounds__(kGatherThreads) void k_replay_gather(const GatherAr
   const int tid = threadIdx.x;
   // the episode table goes to LDS in one coalesced pass (whole, or every stride-th end: replay_index.h); a
   // binary search over global memory is 10+ dependent round trips to L2/HBM (measured 7.4 us for this kernel)
-  const oprl::EndsLds ET = oprl::stage_ends(G.ends, G.n_eps, s_ends, kMaxEndsLds, tid, kGatherThreads);
+  const EndsLds ET = stage_ends(G.src.ends, G.src.n_eps, s_ends, kMaxEndsLds, tid, kGatherThreads);
   __syncthreads();
   const int base = blockIdx.x * kSamplesPerWg;
-  const int S = G.S, A = G.A, W = 2 * S + A + 2;
-  if (tid < kSamplesPerWg) {
-    const int i = base + tid;
-    int e = 0, t = 0;
-    if (i < G.B) {
-      long ind;
-      if (G.idx != nullptr) {
-        ind = (long)G.idx[i];
-      } else {
-        const oprl::u32x4 r = oprl::philox4x32_10(
-            oprl::u32x4{(uint32_t)G.counter, (uint32_t)(G.counter >> 32), (uint32_t)i, 0x5a17u},
-            (uint32_t)G.seed, (uint32_t)(G.seed >> 32));
-        ind = (long)oprl::bounded_u32(r.x, (uint32_t)G.n_transitions);
-      }
-      // first episode with ends[e] > ind  (np.argmin over the >= mask; all-True -> 0)
-      long start = 0;
-      e = oprl::find_episode(G.ends, G.n_eps, ET, ind, &start);
-      t = (int)(ind - start);
-      if (G.out_ep != nullptr) G.out_ep[i] = e;
-      if (G.out_step != nullptr) G.out_step[i] = t;
-    }
-    s_ep[tid] = e;
-    s_t[tid] = t;
-  }
+  const int S = G.src.S, A = G.src.A, W = 2 * S + A + 2;
+  gather_slots(G.src, G.out, ET, base, s_ep, s_t, [](int, bool, const Slot&) {});
   __syncthreads();
-  const int n_here = min(kSamplesPerWg, G.B - base);
-  // Rows -> LDS.  Branch-free source selection and all of a thread's loads issued before its LDS
-  // stores: an if/else per kind (s|s', a, r, d) diverges inside a wave and turns the copy into several
-  // serialised load -> wait -> store round trips (the kernel is pure latency: 8.5 us at B = 256 before).
-  constexpr int kU = 4;
-  for (int i0 = 0; i0 < n_here * W; i0 += kU * kGatherThreads) {
-    float v[kU];
-#pragma unroll
-    for (int j = 0; j < kU; ++j) {
-      const int idx = min(i0 + j * kGatherThreads + tid, n_here * W - 1);
-      const int smp = idx / W, c = idx - smp * W;
-      const long e = s_ep[smp], t = s_t[smp];
-      const float* src = G.states + (e * (G.L + 1) + t) * S + c;                       // s | s' contiguous
-      if (c >= 2 * S) src = G.actions + (e * G.L + t) * A + (c - 2 * S);
-      if (c == 2 * S + A) src = G.rewards + e * G.L + t;
-      if (c == 2 * S + A + 1) src = G.dones + e * G.L + t;
-      v[j] = *src;
-    }
-#pragma unroll
-    for (int j = 0; j < kU; ++j) {
-      const int idx = i0 + j * kGatherThreads + tid;
-      if (idx < n_here * W) stage[idx] = v[j];
-    }
-  }
+  const int n_here = min(kSamplesPerWg, G.src.B - base);
+  gather_stage_rows(G.src, n_here, s_ep, s_t, stage);
   __syncthreads();
-  for (int idx = tid; idx < n_here * S; idx += kGatherThreads) {
-    const int smp = idx / S, c = idx - smp * S;
-    G.out_s[(size_t)(base + smp) * S + c] = stage[smp * W + c];
-    G.out_s2[(size_t)(base + smp) * S + c] = stage[smp * W + S + c];
-  }
-  for (int idx = tid; idx < n_here * A; idx += kGatherThreads) {
-    const int smp = idx / A, c = idx - smp * A;
-    G.out_a[(size_t)(base + smp) * A + c] = stage[smp * W + 2 * S + c];
-  }
-  if (tid < n_here) {
-    G.out_r[base + tid] = stage[tid * W + 2 * S + A];
-    G.out_d[base + tid] = stage[tid * W + 2 * S + A + 1];
-  }
+  gather_write_rows(G.out, S, A, base, n_here, stage, W, S, 2 * S);
+  gather_write_rd(G.out, base, n_here, stage + 2 * S + A, stage + 2 * S + A + 1, W);
 }
 
 // staged row: [ep, t] as two ints bit-cast into floats, then s[S], a[A], r, d
-__global__ void k_replay_scatter(const float* rows, int n, int rowlen, float* states,
-                                 float* actions, float* rewards, float* dones, int L, int S,
-                                 int A) {
+__device__ __forceinline__ void scatter_rows(const float* rows, int n, int rowlen, float* states, float* actions,
+                                             float* rewards, float* dones, int L, int S, int A) {
   for (int rix = blockIdx.x; rix < n; rix += gridDim.x) {
     const float* row = rows + (size_t)rix * rowlen;
     const long e = __float_as_int(row[0]), t = __float_as_int(row[1]);
@@ -146,6 +65,12 @@ __global__ void k_replay_scatter(const float* rows, int n, int rowlen, float* st
       else dones[e * L + t] = v;
     }
   }
+}
+
+__global__ void k_replay_scatter(const float* rows, int n, int rowlen, float* states,
+                                 float* actions, float* rewards, float* dones, int L, int S,
+                                 int A) {
+  scatter_rows(rows, n, rowlen, states, actions, rewards, dones, L, S, A);
 }
 
 // The per-env-step form of the same (the trainer loop adds ONE transition between two updates): rows AND the changed
@@ -154,22 +79,10 @@ __global__ void k_replay_scatter(const float* rows, int n, int rowlen, float* st
 __global__ void k_replay_ingest(const float* rows, int n, int rowlen, float* states, float* actions, float* rewards,
                                 float* dones, int L, int S, int A, const int* ends_src, int* ends_dst, int ends_first,
                                 int ends_n) {
-  for (int rix = blockIdx.x; rix < n; rix += gridDim.x) {
-    const float* row = rows + (size_t)rix * rowlen;
-    const long e = __float_as_int(row[0]), t = __float_as_int(row[1]);
-    for (int c = threadIdx.x; c < S + A + 2; c += blockDim.x) {
-      const float v = row[2 + c];
-      if (c < S) states[(e * (L + 1) + t) * S + c] = v;
-      else if (c < S + A) actions[(e * L + t) * A + (c - S)] = v;
-      else if (c == S + A) rewards[e * L + t] = v;
-      else dones[e * L + t] = v;
-    }
-  }
+  scatter_rows(rows, n, rowlen, states, actions, rewards, dones, L, S, A);
   for (int i = ends_first + (int)(blockIdx.x * blockDim.x + threadIdx.x); i < ends_n; i += (int)(gridDim.x * blockDim.x))
     ends_dst[i] = ends_src[i];
 }
-using oprl::kDirectRows;              // staged rows / changed table entries up to which the ingest kernel reads the pinned buffers itself
-using oprl::kDirectEnds;
 
 }  // namespace
 
@@ -224,8 +137,9 @@ extern "C" int oprl_replay_flush(oprl_replay* h, void* stream) {
   if (h->n_staged == 0 && !h->ends_pending && !(h->prio && h->prio->n_eps != h->n_eps)) return OPRL_OK;
   hipStream_t st = (hipStream_t)stream;
   const int c = h->cur, n = h->n_staged, ec = h->ends_cur;
-  const int e_first = h->ends_pending ? h->ends_first : 0, e_n = h->ends_pending ? h->ends_n : 0;
-  const bool direct = n <= kDirectRows && e_n - e_first <= kDirectEnds && h->stage_map[c] != nullptr && h->ends_map[ec] != nullptr;
+  const PendingEnds pe = pending_ends(h, n, h->stage_map[c], h->ends_map[ec]);
+  const int e_first = pe.first, e_n = pe.n;
+  const bool direct = pe.direct;
   if (direct) {
     const int wgs = n > 0 ? n : 1;
     hipLaunchKernelGGL(k_replay_ingest, dim3(wgs), dim3(64), 0, st, h->stage_map[c], n, h->rowlen, h->states, h->actions,
@@ -262,6 +176,14 @@ extern "C" int oprl_replay_flush(oprl_replay* h, void* stream) {
 }
 
 namespace oprl {
+PendingEnds pending_ends(const oprl_replay* h, int n_rows, const float* rows_map, const int* ends_map) {
+  PendingEnds p;
+  p.first = h->ends_pending ? h->ends_first : 0;
+  p.n = h->ends_pending ? h->ends_n : 0;
+  p.direct = n_rows <= kDirectRows && p.n - p.first <= kDirectEnds && rows_map != nullptr && ends_map != nullptr;
+  return p;
+}
+
 int ends_sent(oprl_replay* h, hipStream_t st) {
   if (h->ends_pending) {
     const int ec = h->ends_cur;
@@ -383,34 +305,15 @@ extern "C" int oprl_replay_sample(oprl_replay* h, int32_t B, const int64_t* idx,
                                   uint64_t counter, float* out_s, float* out_a, float* out_r,
                                   float* out_d, float* out_s2, int32_t* out_ep, int32_t* out_step,
                                   void* stream) {
-  if (!h || B < 1 || !out_s || !out_a || !out_r || !out_d || !out_s2) {
-    set_err("oprl_replay_sample: invalid argument");
-    return OPRL_ERR_INVALID;
-  }
+  RC(gather_check("oprl_replay_sample", h, B, out_s, out_a, out_r, out_d, out_s2));
   if (h->nstep > 1)      // n-step mode (oprl_replay_set_nstep): the same draw, n-step rows (replay_nstep.hip)
     return oprl_replay_sample_nstep(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
   if (h->her.G > 0)      // hindsight mode (oprl_replay_set_her): the same draw, relabelled rows (replay_her.hip)
     return oprl_replay_sample_her(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
-  if (h->n_transitions <= 0 || h->n_eps <= 0) {
-    set_err("oprl_replay_sample: buffer is empty (np.random.randint(0, 0) raises in the reference)");
-    return OPRL_ERR_STATE;
-  }
-  int rc = oprl_replay_flush(h, stream);
-  if (rc != OPRL_OK) return rc;
   GatherArgs G;
-  G.states = h->states; G.actions = h->actions; G.rewards = h->rewards; G.dones = h->dones;
-  G.ends = h->ends_dev; G.n_eps = h->n_eps; G.L = h->L; G.S = h->S; G.A = h->A; G.B = B;
-  G.n_transitions = h->n_transitions;
-  G.idx = (const long long*)idx; G.seed = seed; G.counter = counter;
-  G.out_s = out_s; G.out_a = out_a; G.out_r = out_r; G.out_d = out_d; G.out_s2 = out_s2;
-  G.out_ep = out_ep; G.out_step = out_step;
-  const int grid = (B + kSamplesPerWg - 1) / kSamplesPerWg;
-  const size_t lds = sizeof(float) * kSamplesPerWg * (2 * h->S + h->A + 2);
-  oprl::prof_begin(2, (hipStream_t)stream);
-  hipLaunchKernelGGL(k_replay_gather, dim3(grid), dim3(kGatherThreads), lds, (hipStream_t)stream, G);
-  oprl::prof_end((hipStream_t)stream);
-  HIPC(hipGetLastError());
-  return OPRL_OK;
+  gather_fill(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, &G.src, &G.out);
+  return gather_launch("oprl_replay_sample: buffer is empty (np.random.randint(0, 0) raises in the reference)",
+                       k_replay_gather, G, 2 * h->S + h->A + 2, h, stream);
 }
 
 // used by the learner's fused step_n

@@ -1,5 +1,10 @@
-// replay_index.h — flat transition index -> (episode, step) for the device-side samplers
-// (k_replay_gather in replay.hip, load_batch in fused_ddpg.hip).
+// replay_index.h — the uniform sampler's draw, and flat transition index -> (episode, step), for every device-side
+// sampler: the gather kernels (replay_gather.h: k_replay_gather in replay.hip, k_replay_gather_nstep in
+// replay_nstep.hip, k_replay_gather_her in replay_her.hip) and the in-kernel gathers of the fused and layer-by-layer
+// launches (batch_rows.h: load_batch, prefetch_rows_direct).  All of them pick the same slot for the same
+// (seed, counter, row): the gather kernels call draw_slot; batch_rows.h's two sites carry its no-index path written
+// out (kUniformWord, bounded_u32 of r.x, find_episode), because the call moves an instruction selection inside the
+// benchmarked launches.  A change to the draw is a change here and at those two sites.
 //
 // Reference: EpisodicReplayBuffer._inds_to_episodic (buffers/episodic_buffer.py:114-121): the episode of flat
 // index `ind` is the first slot whose cumulative end exceeds it (np.argmin over the >= mask; if none does,
@@ -9,6 +14,9 @@
 // (a replay of 200-step episodes has 5000 of them: 5.4 us -> 1.x us for the sampling chain).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "philox.h"
 
 namespace oprl {
 
@@ -53,6 +61,36 @@ __device__ __forceinline__ int find_episode(const int* __restrict__ ends, int n_
   if (e == 0) *start = 0;
   else *start = T.stride == 1 ? (long)T.lds[e - 1] : (long)ends[e - 1];
   return e;
+}
+
+// fourth Philox counter word of the uniform draw (the prioritized sampler has its own: replay_prio.hip kSampleWord)
+constexpr uint32_t kUniformWord = 0x5a17u;
+
+struct Slot {
+  int e, t;          // episode and step of the drawn transition
+  long start, end;   // ends[e - 1] (0 for e = 0) and ends[e]: the episode holds end - start steps
+  u32x4 r;           // the draw's Philox words (r.x picked the slot); zeros where the draw was skipped
+};
+
+// Row i of the sample (seed, counter): flat index bounded_u32(r.x, n_transitions), or idx[i] when indices are
+// injected, as (episode, step).  An injected index skips the Philox call unless kAlwaysDraw (hindsight reads r.y and
+// r.z of injected rows too).  After stage_ends' barrier.
+template <bool kAlwaysDraw = false>
+__device__ __forceinline__ Slot draw_slot(const int* ends, const EndsLds& ET, int n_eps, long n_transitions,
+                                          unsigned long long seed, unsigned long long counter, int i,
+                                          const long long* idx) {
+  Slot s;
+  s.r = u32x4{0u, 0u, 0u, 0u};
+  if (kAlwaysDraw || idx == nullptr)
+    s.r = philox4x32_10(u32x4{(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)i, kUniformWord}, (uint32_t)seed,
+                        (uint32_t)(seed >> 32));
+  const long ind = idx != nullptr ? (long)idx[i] : (long)bounded_u32(s.r.x, (uint32_t)n_transitions);
+  // first episode with ends[e] > ind  (np.argmin over the >= mask; all-True -> 0)
+  s.e = find_episode(ends, n_eps, ET, ind, &s.start);
+  s.t = (int)(ind - s.start);
+  // (a global load when the table is coarse; k_replay_gather never reads `end` or `r`, and both are dead code there)
+  s.end = ET.stride == 1 ? (long)ET.lds[s.e] : (long)ends[s.e];
+  return s;
 }
 
 }  // namespace oprl

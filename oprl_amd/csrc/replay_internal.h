@@ -1,5 +1,7 @@
-// replay_internal.h — the replay handle, shared by the uniform replay (replay.hip) and the sum tree of
-// prioritized replay (replay_prio.hip).
+// replay_internal.h — the replay handle (struct oprl_replay) and what the replay's translation units share: the writes,
+// the flush and the uniform sampler (replay.hip), the sum tree of prioritized replay (replay_prio.hip), the n-step and
+// hindsight samplers (replay_nstep.hip, replay_her.hip; their kernels' common shape is replay_gather.h) and the
+// many-episodes write (replay_rows.hip).  learner_per.hip reads the handle's sum tree too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +9,7 @@
 #include <vector>
 
 #include "../../include/oprl_amd.h"
+#include "host_err.h"
 
 namespace oprl {
 
@@ -31,9 +34,6 @@ struct PrioTree {
   int idx_cap = 0;
 };
 
-// Keep the leaves in step with a flush: the staged rows `rows` (n_rows records of `rowlen` floats, [ep, t] as int
-// bits first; device-readable) and the episode-table entries [ends_first, ends_n) it uploaded (ends_n = 0: none).
-// Called by oprl_replay_flush and oprl_replay_write_rows after their copies, on their stream.
 constexpr int kNstepMax = 16;       // largest n of the n-step sampler (replay_nstep.hip: one lane per (sample, step))
 
 // Hindsight mode of a replay (oprl_replay_set_her, replay_her.hip).  G = 0: off.
@@ -44,6 +44,9 @@ struct HerMode {
   double ratio = 0.8, threshold = 0.0;  // relabelled share of the eligible rows; the sparse reward's distance bound
 };
 
+// Keep the leaves in step with a flush: the staged rows `rows` (n_rows records of `rowlen` floats, [ep, t] as int
+// bits first; device-readable) and the episode-table entries [ends_first, ends_n) it uploaded (ends_n = 0: none).
+// Called by oprl_replay_flush and oprl_replay_write_rows after their copies, on their stream.
 int prio_flush(oprl_replay* h, const float* rows, int n_rows, int rowlen, int ends_first, int ends_n, hipStream_t st);
 void prio_free(PrioTree* p);
 
@@ -52,6 +55,11 @@ void prio_free(PrioTree* p);
 constexpr int kDirectRows = 16;
 constexpr int kDirectEnds = 2048;
 constexpr int kRowsMax = 256;       // records of one oprl_replay_write_rows call (replay_rows.hip)
+// What an ingest launch of n_rows staged rows has to take along: the pending range [first, n) of the episode-ends
+// table (n = 0: none), and `direct`: its kernel may read the pinned row buffer and ends_host[ends_cur] through their
+// device mappings rows_map / ends_map (null: not mapped) instead of waiting for copies to device staging.
+struct PendingEnds { int first, n; bool direct; };
+PendingEnds pending_ends(const oprl_replay* h, int n_rows, const float* rows_map, const int* ends_map);
 
 // what oprl_replay_set_lens refuses, without touching the handle (`who` names the caller in the message)
 int check_lens(const oprl_replay* h, const int32_t* ep_lens_host, int32_t episodes_counter, const char* who);

@@ -15,26 +15,12 @@
 #include "philox.h"
 #include "replay_internal.h"
 
-namespace oprl {
-void set_err(const char* fmt, ...);
-}
-using oprl::set_err;
-
-#define HIPC(x)                                                              \
-  do {                                                                       \
-    hipError_t _e = (x);                                                     \
-    if (_e != hipSuccess) {                                                  \
-      set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return OPRL_ERR_HIP;                                                   \
-    }                                                                        \
-  } while (0)
-
 namespace {
 
 constexpr int F = oprl::kPrioFan;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr uint32_t kSampleWord = 0x7e55u;  // the sampler's fourth Philox counter word (the uniform sampler's is 0x5a17)
+constexpr uint32_t kSampleWord = 0x7e55u;  // the sampler's fourth Philox counter word (the uniform sampler's: replay_index.h kUniformWord)
 
 __device__ __forceinline__ int ep_len(const int* ends, int e) { return ends[e] - (e > 0 ? ends[e - 1] : 0); }
 

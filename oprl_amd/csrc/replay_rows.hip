@@ -13,20 +13,6 @@
 #include "../../include/oprl_amd.h"
 #include "replay_internal.h"
 
-namespace oprl {
-void set_err(const char* fmt, ...);
-}
-using oprl::set_err;
-
-#define HIPC(x)                                                              \
-  do {                                                                       \
-    hipError_t _e = (x);                                                     \
-    if (_e != hipSuccess) {                                                  \
-      set_err("%s failed: %s (%s:%d)", #x, hipGetErrorString(_e), __FILE__, __LINE__); \
-      return OPRL_ERR_HIP;                                                   \
-    }                                                                        \
-  } while (0)
-
 namespace {
 
 constexpr int kWave = 64;
@@ -158,11 +144,11 @@ extern "C" int oprl_replay_write_rows(oprl_replay* h, int32_t n, const int32_t* 
   // 4. the episode table
   rc = oprl_replay_set_lens(h, ep_lens_host, episodes_counter, stream);
   if (rc != OPRL_OK) return rc;
-  // 5. one launch: the records and the table's changed range.  Who reads the pinned memory follows oprl_replay_flush
+  // 5. one launch: the records and the table's changed range
   const int ec = h->ends_cur;
-  const int e_first = h->ends_pending ? h->ends_first : 0, e_n = h->ends_pending ? h->ends_n : 0;
-  const bool direct = n <= oprl::kDirectRows && e_n - e_first <= oprl::kDirectEnds && h->rows_map[c] != nullptr &&
-                      h->ends_map[ec] != nullptr;
+  const oprl::PendingEnds pe = oprl::pending_ends(h, n, h->rows_map[c], h->ends_map[ec]);
+  const int e_first = pe.first, e_n = pe.n;
+  const bool direct = pe.direct;
   const float* recs = direct ? h->rows_map[c] : h->rows_dev[c];
   if (!direct) HIPC(hipMemcpyAsync(h->rows_dev[c], h->rows_host[c], sizeof(float) * reclen * n, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_replay_ingest_rows, dim3(n), dim3(kWave), 0, st, recs, (int)n, reclen, h->states, h->actions,

@@ -147,6 +147,23 @@ def test_bitexact_at_the_smallest_and_the_largest_goal(G, ag, g):
     assert not changed[~rel].any() and not np.delete(changed, np.s_[g:g + G], axis=1).any()
 
 
+def test_coarse_episode_table():
+    """2500 episodes: more than the 2048 table entries the kernel holds in LDS, so the table is staged coarsely and an
+    episode's end comes from global memory.  Lengths 0 .. 4: relabelled rows, eligible rows left stored and rows without
+    a candidate all occur, from episodes on both sides of entry 2048 (the oracle alone gives 255 / 58 / 199 such rows,
+    443 distinct episodes and 101 rows from episodes >= 2048)."""
+    buf = make_buffer(2500, 4, 8, 2, goal_dim=2, achieved_offset=4, desired_offset=6, threshold=1.5, her_ratio=0.8)
+    lens = np.random.RandomState(2).randint(0, 5, size=2500)
+    set_table(buf, lens)
+    for strategy in ("future", "final"):
+        set_mode(buf, strategy=strategy, reward="sparse")
+        got, want = sample(buf, 512, 3), oracle(buf, 512, 3)
+        assert_same(got, want, ("coarse", strategy))
+        fut, c = want["future"], lens[want["ep"]] - 1 - want["step"]
+        assert np.any(fut >= 0) and np.any((fut < 0) & (c >= 1)) and np.any(c == 0)
+        assert len(np.unique(want["ep"])) > 300 and np.any(want["ep"] >= 2048)
+
+
 # ---- the reward ---------------------------------------------------------------------------------------------------------
 def test_sparse_reward_at_its_threshold(replay):
     """One relabelled row's dist2 against thresholds whose float32 square is that dist2, one float below it and one
