@@ -10,6 +10,8 @@
  *                    (Fujimoto & Gu 2021), for training from a fixed dataset
  *   oprl_learner_set_iql / read_iql / get_iql_step / set_iql_step, oprl_iql_seed   no counterpart: implicit Q-learning
  *                    (Kostrikov et al. 2021) as a mode of a TD3 learner with a caller-owned value net
+ *   oprl_learner_set_cql / read_cql / set_cql_noise, oprl_cql_rows, oprl_cql_seed   no counterpart: conservative Q-learning
+ *                    (Kumar et al. 2020, CQL(H)) as a mode of a SAC learner
  *   oprl_replay_*    ReplayBufferProtocol                 buffers/protocols.py:6-26
  *                    EpisodicReplayBuffer.{add_transition,sample}  buffers/episodic_buffer.py:81-133
  *   oprl_mlp_*       MLP / Critic / policies forward      algos/nn_models.py:27-194
@@ -622,6 +624,53 @@ int oprl_learner_set_iql_step(oprl_learner* h, int64_t step);
 int oprl_iql_seed(const float* q1, const float* q2, const float* v, const float* pi, const float* a, double expectile,
                   double beta, double adv_clip, int32_t B, int32_t A, float* u_out, float* seed_out, float* w_out,
                   float* da_out, float* part_v_out, float* part_w_out, float* part_a_out, void* stream);
+
+/* ---- Conservative Q-learning: a penalty on the critics' values of actions outside the dataset (Kumar et al. 2020, CQL(H)
+ * with a fixed penalty weight).  A MODE of a SAC learner, like the two above: n_actions = N in 1 .. 16 turns
+ * it on, 0 turns it off (SAC again, bit for bit).  With the mode on the critic step of an update on B rows runs on
+ * Bw = B (1 + 3 N) rows: the minibatch's (s, a) and, per state s_b, N actions uniform in [-1, 1]^A (log-density -A log 2),
+ * N drawn from pi(.|s_b) and N from pi(.|s'_b) with their log-probabilities — the tanh-Gaussian head's formula, from ONE
+ * forward of the online actor on s and one on s' — all evaluated at s_b and all constants for every gradient.  Per critic j,
+ * with c_jbe = Q_j(s_b, x_be) - logdensity(x_be) over the row's 3 N entries, the loss is
+ *   (1/B) sum_b (Q_j(s_b, a_b) - y_b)^2 + cql_alpha (1/B) sum_b [ logsumexp_e c_jbe - Q_j(s_b, a_b) ]
+ * with SAC's target y (so an n-step replay gives n-step CQL); the critics are summed as SAC sums them and take one Adam step.
+ * The actor step, the temperature step and Polyak are SAC's.  The call that turns the mode on allocates its rows (once);
+ * no update allocates.  Noise: Philox streams 4 (normal) and 5 (uniform) of the learner's seed, counter = the update count.
+ * OPRL_ERR_INVALID: a learner that is not SAC, a precision other than OPRL_PREC_F32, cql_alpha < 0 or non-finite, n_actions
+ * outside 0 .. 16.  OPRL_ERR_STATE: a learner whose fused form is on (create it with no_fuse), a member of a group, an
+ * export_grads / data-parallel learner.  The workspace holds max_batch rows — oprl_learner_create sets no ceiling on it —
+ * so with the mode on oprl_learner_update / update_phase / step_n return OPRL_ERR_INVALID for B (1 + 3 N) > max_batch, and
+ * oprl_learner_update_weighted and oprl_learner_step_n_prio return OPRL_ERR_STATE.  A refused call changes nothing. */
+int oprl_learner_set_cql(oprl_learner* h, double cql_alpha, int32_t n_actions);
+/* Of the last update with the mode on, the per-slice sums added in slice order, as means: out_host[0], [1] = mean_b
+ * (logsumexp_e c_jbe - Q_j(s_b, a_b)) of critic 0, 1; [2], [3] = their mean Q on the uniform actions; [4], [5] = on the actions
+ * drawn from pi(.|s_b); [6] = cql_alpha ([0] + [1]), the penalty term of the summed loss; [7] = 0.  Synchronises `stream`.
+ * OPRL_ERR_STATE for a learner on which the mode was never on. */
+int oprl_learner_read_cql(oprl_learner* h, float out_host[8], void* stream);
+/* Test hook, like noise0 / noise1 of oprl_learner_update: device arrays standing in for the mode's draws, read by every
+ * later update until replaced — eps[B][2N][A] N(0,1) draws ([b][k] for pi(.|s_b), [b][N + k] for pi(.|s'_b)), uni[B][N][A]
+ * the uniform actions themselves (clamped to [-1, 1]).  NULL: Philox. */
+int oprl_learner_set_cql_noise(oprl_learner* h, const float* eps, const float* uni);
+/* k_cql_rows on caller-supplied device rows, as the learner's update runs it: s[B][S], a[B][A], the actor's raw head rows
+ * raw_s[B][2A], raw_s2[B][2A] (means | log-stds), eps / uni as above (NULL: Philox streams 4 / 5 of `seed`, rank 0, at
+ * `counter`).  Out, Bw = B (1 + 3 N) rows: ws_out[Bw][S], wa_out[Bw][A] — row b < B is (s_b, a_b); row B + b 3N + e,
+ * e = kind N + k, is (s_b, x) with kind 0 uniform, 1 from pi(.|s_b), 2 from pi(.|s'_b) — and logd_out[B][3N].  Nothing is
+ * written past those extents.  OPRL_ERR_INVALID: a null pointer (eps, uni excepted), B, S, A < 1, N outside 1 .. 16,
+ * B (1 + 3 N) max(S, A) > 2^30. */
+int oprl_cql_rows(const float* s, const float* a, const float* raw_s, const float* raw_s2, const float* eps, const float* uni,
+                  uint64_t seed, uint64_t counter, int32_t B, int32_t S, int32_t A, int32_t N, float* ws_out, float* wa_out,
+                  float* logd_out, void* stream);
+/* k_cql_seed on caller-supplied device rows: q[nc][Bw] the critics on the wide rows, the target's operands qn1[B], qn2[B]
+ * (or NULL), logp2[B] (or NULL; then alpha is unused), r[B], d[B] — y = r + ((1 - d) gamma) (min(qn1, qn2) - alpha logp2)
+ * as SEED_MSE_TD forms it — and logd[B][3N].  Out: seed_out[nc][Bw] — data row b: ((2 (q - y)) - cql_alpha) (1/B); sampled
+ * row (b, e): (cql_alpha softmax(c_jb.)_e) (1/B), a max-subtracted softmax in entry order — y_out[B] (or NULL), and per
+ * slice of 16 rows, n = (B + 15) / 16: part_out[nc][n][4] = (sum (q - y)^2, sum q, sum y, untouched),
+ * part_cql_out[nc][n][4] = (sum (logsumexp - q), sum_b sum_k q on the uniform actions, ... on pi(.|s_b)'s, untouched).
+ * Nothing is written past those extents.  OPRL_ERR_INVALID: a null pointer, nc outside 1 .. OPRL_MAX_CRITICS, B < 1, N
+ * outside 1 .. 16, B (1 + 3 N) > 2^30, cql_alpha < 0 or non-finite. */
+int oprl_cql_seed(const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
+                  const float* logd, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
+                  float* seed_out, float* y_out, float* part_out, float* part_cql_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -156,6 +156,11 @@ SIGNATURES = {
     "oprl_learner_get_iql_step": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "oprl_learner_set_iql_step": (C.c_int, [_P, C.c_int64]),
     "oprl_iql_seed": (C.c_int, [_P, _P, _P, _P, _P, _D, _D, _D, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oprl_learner_set_cql": (C.c_int, [_P, _D, _I32]),
+    "oprl_learner_read_cql": (C.c_int, [_P, C.POINTER(C.c_float), _P]),
+    "oprl_learner_set_cql_noise": (C.c_int, [_P, _P, _P]),
+    "oprl_cql_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "oprl_cql_seed": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
-"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG``, ``TD3BC`` and ``IQL`` are also served from here,
-resolved on first use so that importing the package stays free of torch."""
+"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG``, ``TD3BC``, ``IQL`` and ``CQL`` are also served
+from here, resolved on first use so that importing the package stays free of torch."""
 
 
 def __getattr__(name: str):
@@ -12,4 +12,7 @@ def __getattr__(name: str):
     if name == "IQL":
         from oprl_amd.algos.iql import IQL
         return IQL
+    if name == "CQL":
+        from oprl_amd.algos.cql import CQL
+        return CQL
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -553,6 +553,29 @@ class HipLearner:
             _capi.check(self.lib.oprl_learner_read_bc(self.handle, buf, _capi.current_stream()), "oprl_learner_read_bc")
         return {"bc_lambda": float(buf[0]), "q_abs_mean": float(buf[1]), "bc_mse": float(buf[2])}
 
+    def set_cql(self, cql_alpha: float, n_actions: int) -> None:
+        """The conservative-Q-learning mode of a SAC learner's critic step (oprl_learner_set_cql; CQL, DESIGN.md section
+        19): ``n_actions`` in 1 .. 16 turns it on, ``0`` turns it off.  A refused call leaves the learner as it was."""
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_set_cql(self.handle, float(cql_alpha), int(n_actions)), "oprl_learner_set_cql")
+
+    def read_cql(self) -> dict[str, float]:
+        """Of the last update with the mode on, per critic: the mean of logsumexp - Q(s, a), the mean Q on the uniform
+        actions and on the actions drawn from pi(.|s); and the penalty term of the loss (oprl_learner_read_cql)."""
+        buf = (C.c_float * 8)()
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_read_cql(self.handle, buf, _capi.current_stream()), "oprl_learner_read_cql")
+        keys = ("gap1", "gap2", "q_rand1", "q_rand2", "q_pi1", "q_pi2", "penalty")
+        return dict(zip(keys, (float(x) for x in buf)))
+
+    def set_cql_noise(self, eps: t.Tensor | None, uni: t.Tensor | None) -> None:
+        """Test hook (oprl_learner_set_cql_noise): device arrays standing in for the mode's normal draws [B, 2N, A] and
+        uniform actions [B, N, A], read by every later update until replaced; ``None``: Philox.  The learner keeps them alive."""
+        prep = lambda x: None if x is None else x.to(device=self.device, dtype=t.float32).contiguous()     # noqa: E731
+        self._cql_noise = (prep(eps), prep(uni))
+        _capi.check(self.lib.oprl_learner_set_cql_noise(self.handle, _capi.ptr(self._cql_noise[0]), _capi.ptr(self._cql_noise[1])),
+                    "oprl_learner_set_cql_noise")
+
     def set_iql(self, value_mlp: MLP | None, expectile: float = 0.7, beta: float = 3.0, adv_clip: float = 100.0,
                 lr_value: float = 3e-4) -> None:
         """The implicit-Q-learning mode of a TD3 learner (oprl_learner_set_iql): ``value_mlp`` is

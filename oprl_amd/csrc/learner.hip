@@ -11,6 +11,7 @@
 #include "c51_seed.h"
 #include "bc_seed.h"
 #include "iql_seed.h"
+#include "cql_seed.h"
 #include "philox.h"
 
 namespace oprl {
@@ -1004,6 +1005,68 @@ int c51_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st
   return for_each_net(h, 1, h->w_critic, st, [&](int) { return c51_backward_args(h, B, true); });
 }
 
+// Step 3 of the generic critic phase of a SAC learner with the conservative-Q-learning mode on (oprl_learner_set_cql;
+// DESIGN.md §19), in weighted_critic_step's form at a wider row count: Bw = B (1 + 3 N) rows, the minibatch's (s, a) first and
+// then N uniform actions, N from pi(.|s_b) and N from pi(.|s'_b) per state, all at s_b (cql_seed.h has the layout).  The
+// actor's raw head row on s' is step 1's (raw_out); the one on s is a forward-only launch here: the actor does not run N times.
+// Then k_cql_rows | the critics' forward on the wide rows with the activations stored, q into qpi | k_cql_seed | the critics'
+// backward from SEED_PTR: 5 launches where SAC has 1, and step 4's dW + Adam + Polyak reads what it always reads, Bw rows of it.
+int cql_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st) {
+  const oprl_learner_config& c = h->cfg;
+  const int S = h->S, A = h->A, nc = h->nc, N = h->cql_n;
+  const int Bw = B * (1 + 3 * N);
+  if (c.algo != OPRL_SAC || h->cql_base == nullptr || Bw > h->Bmax) { set_err("internal: conservative-Q-learning critic step without its buffers"); return OPRL_ERR_STATE; }
+  {
+    MlpArgs f = base_args(h, c.actor, false, B);
+    f.do_fwd = 1;
+    f.x0 = rows.cur.s; f.k0 = S;
+    f.out = h->cql_raw_s; f.ldo = 2 * A;
+    f.out_act = ACT_NONE;
+    RC(launch(f, h->w_actor, st));
+  }
+  CqlRowsArgs g;
+  memset((void*)&g, 0, sizeof g);
+  g.s = rows.cur.s; g.a = rows.cur.a;
+  g.raw_s = h->cql_raw_s; g.raw_s2 = h->cql_raw_s2;
+  g.eps = h->cql_eps; g.uni = h->cql_uni;
+  g.key_eps = noise_key(h, 4); g.key_uni = noise_key(h, 5);       // (streams 1 .. 3: seed_rng's two and REDQ's subset)
+  g.ctr = (unsigned long long)h->update_count;
+  g.B = B; g.S = S; g.A = A; g.N = N;
+  g.ws = h->cql_ws; g.wa = h->cql_wa; g.logd = h->cql_logd;
+  prof_begin(3, st);
+  hipError_t e = launch_cql_rows(g, st);
+  prof_end(st);
+  HIPC(e);
+  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
+    MlpArgs f = critic_sa_args(h, j, h->cql_ws, h->cql_wa, Bw, false);
+    f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
+    return f;
+  }));
+  CqlSeedArgs t;
+  memset((void*)&t, 0, sizeof t);
+  t.s = mse_td_seed(h, rows.cur.r, rows.cur.d, B, 0);
+  t.s.y_out = h->ydbg; t.s.q_out = h->qdbg;
+  t.q = h->qpi; t.q_stride = h->Bmax;
+  t.logd = h->cql_logd;
+  t.ca = (float)h->cql_alpha;
+  t.seed = h->cql_seed; t.seed_stride = h->Bmax;
+  t.partials = h->part_c; t.part_cql = h->cql_part;
+  t.nc = nc; t.B = B; t.N = N; t.n_slices = (B + kR - 1) / kR;
+  prof_begin(3, st);
+  e = launch_cql_seed(t, st);
+  prof_end(st);
+  HIPC(e);
+  h->cql_B = B; h->cql_last_n = N;
+  return for_each_net(h, nc, h->w_critic, st, [&](int j) {
+    MlpArgs f = base_args(h, c.critics[j], false, Bw);
+    f.do_bwd = 1;
+    with_store(f, h->ws_critic[j], true, true);
+    f.seed_mode = SEED_PTR;
+    f.seed.p0 = h->cql_seed + (size_t)j * h->Bmax; f.seed.ld0 = 1;
+    return f;
+  });
+}
+
 // The critic phase of a TD3 learner with the implicit-Q-learning mode on (oprl_learner_set_iql).  No action
 // outside the batch is evaluated: V on s' where TD3 runs the target actor and the target critics on (s', a'), the target
 // critics on the batch's own (s, a), V's expectile step as forward | k_iql_value_seed | backward from SEED_PTR with a dW +
@@ -1165,6 +1228,7 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
     if (algo == OPRL_DDPG || algo == OPRL_D4PG) f.out_act = ACT_TANH;
     else if (algo == OPRL_TD3) { f.out_act = ACT_TANH_SMOOTH; seed_rng(f, h, noise0, 1); }
     else { f.out_act = ACT_GAUSS; f.logp = h->logp2; seed_rng(f, h, noise0, 1); }
+    if (h->cql_n > 0) { f.raw_out = h->cql_raw_s2; f.ldraw = 2 * A; }      // (the CQL mode samples from this head row too: cql_critic_step)
     // TQC: this launch is 64 workgroups on 256 CUs, and the online critics' first two layers on (s, a) — the
     // first launch of step 3 — depend on nothing of it: they ride behind it (k_slice_tp_fin, layerwise.hip)
     bool fin_ride = false, fin16 = false;
@@ -1243,6 +1307,11 @@ int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hi
   // heads (k_lw_head: 80 workgroups on 256 CUs), with the noise and the counter actor_phase would give it
   h->rider_pending = false;
   h->rider_done = false;
+  if (h->cql_n > 0) {              // the conservative-Q-learning mode: the critic step on the wide rows, then step 4 on as many
+    if (rows.w != nullptr) { set_err("internal: importance weights reached the conservative-Q-learning critic step"); return OPRL_ERR_STATE; }
+    RC(cql_critic_step(h, rows, B, st));
+    return dw_step(h, true, B * (1 + 3 * h->cql_n), st);
+  }
   if (rows.w != nullptr) {         // importance weights: the same step as three launches per grouping, then step 4
     RC(weighted_critic_step(h, rows, B, n_min, st));
     return dw_step(h, true, B, st);
@@ -1597,6 +1666,15 @@ int check_batch(const oprl_learner* h, const void* s, const void* a, const void*
 }
 
 // Has a kernel of this learner reported an expired wait?  (Sticky until oprl_learner_clear_error.)
+// the conservative-Q-learning mode's critic step runs on B (1 + 3 N) rows of the workspace
+int cql_rows_fit(const oprl_learner* h, const char* who, int B) {
+  if (h->cql_n == 0 || (long)B * (1 + 3 * h->cql_n) <= (long)h->Bmax) return OPRL_OK;
+  set_err("%s: the conservative-Q-learning mode's critic step needs batch x (1 + 3 n_actions) = %d x %d = %ld rows of a workspace "
+          "of max_batch=%d; create the learner with a larger max_batch or lower n_actions", who, B, 1 + 3 * h->cql_n,
+          (long)B * (1 + 3 * h->cql_n), h->Bmax);
+  return OPRL_ERR_INVALID;
+}
+
 int check_device_error(const oprl_learner* h) {
   if (h == nullptr || h->err_host == nullptr) return OPRL_OK;
   const unsigned code = *(volatile const unsigned*)h->err_host;
@@ -1709,6 +1787,7 @@ extern "C" int oprl_abi_version(void) { return OPRL_ABI_VERSION; }
 namespace oprl_host {
 int learner_update_phase(oprl_learner* h, int phase, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream) {
   RC(check_batch(h, rows.cur.s, rows.cur.a, rows.cur.r, rows.cur.d, rows.cur.s2, B));
+  RC(cql_rows_fit(h, "update", B));
   RC(check_device_error(h));      // an expired wait of an earlier launch (asynchronous: whatever has run by now)
   hipStream_t st = (hipStream_t)stream;
   h->last_B = B;
@@ -1864,6 +1943,7 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
   if (h->cfg.export_grads) { set_err("step_n is the single-GPU fused path; export_grads learners use update_phase/apply"); return OPRL_ERR_STATE; }
   int nstep = 1;
   RC(RowStager::check("step_n", h, replay, false, K, B, &nstep));
+  RC(cql_rows_fit(h, "step_n", B));
   RowStager stg;
   const bool plain = nstep == 1 && replay_her(replay) == 0;      // else: the sample + update loop at the end
   if (plain && use_fused(h, B)) {

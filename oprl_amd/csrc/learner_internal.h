@@ -368,6 +368,17 @@ struct oprl_learner {
   float *iql_part_v = nullptr, *iql_part_w = nullptr;
   std::vector<DwItem> iql_items;
   int iql_tiles = 0, iql_B = 0;
+  // the conservative-Q-learning mode of a SAC learner (oprl_learner_set_cql, cql_seed.hip): the penalty
+  // weight and the sampled actions per kind (cql_n = 0: off), and one allocation of its own, made when the mode is first
+  // turned on — the actor's raw head rows on s and on s' [Bmax][2A] each | the wide states [Bmax][S] and actions [Bmax][A] |
+  // the log-densities and the seed rows [nc][Bmax] | k_cql_seed's own per-slice sums [nc][slices at Bmax][4]; the test
+  // hook's noise arrays (null: Philox) and the row count of the last update with the mode on
+  double cql_alpha = 0.0;
+  int cql_n = 0, cql_B = 0, cql_last_n = 0;
+  float* cql_base = nullptr;
+  float *cql_raw_s = nullptr, *cql_raw_s2 = nullptr, *cql_ws = nullptr, *cql_wa = nullptr, *cql_logd = nullptr, *cql_seed = nullptr;
+  float* cql_part = nullptr;
+  const float *cql_eps = nullptr, *cql_uni = nullptr;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)
@@ -504,6 +515,8 @@ void set_adam(AdamScalars& ad, double lr, double beta1, double beta2, double eps
 int next_tp_tag(unsigned* counter, unsigned long long* xbuf, size_t xbuf_bytes, hipStream_t st, unsigned* out);
 const oprl_net& eff(const oprl_learner* h, const oprl_net& n);
 int check_device_error(const oprl_learner* h);
+int cql_rows_fit(const oprl_learner* h, const char* who, int B);
+unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id);      // Philox key of a noise stream (1 .. 3: learner.hip; 4, 5: the CQL mode's)
 void with_store(MlpArgs& a, const NetWs& ws, bool x, bool dy);
 hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st);
 void fill_items(const oprl_net& n, const NetWs& ws, std::vector<DwItem>& v, int* tiles, bool small_partial_tiles = false,

@@ -4,6 +4,7 @@
 #include "c51_seed.h"
 #include "bc_seed.h"
 #include "iql_seed.h"
+#include "cql_seed.h"
 
 #include <cmath>
 #include <vector>
@@ -437,6 +438,147 @@ extern "C" int oprl_iql_seed(const float* q1, const float* q2, const float* v, c
   m.B = B; m.A = A; m.n_slices = t.n_slices;
   m.da = da_out; m.part = part_a_out;
   HIPC(launch_iql_actor_seed(m, (hipStream_t)stream));
+  return OPRL_OK;
+}
+
+// ---------------------------------------------------------------- conservative Q-learning
+// The CQL mode of a SAC learner (learner.hip cql_critic_step).  Every refusal comes before any GPU work and changes nothing.
+namespace {
+bool cql_alpha_ok(const char* who, double cql_alpha) {
+  if (!std::isfinite(cql_alpha) || cql_alpha < 0.0 || !std::isfinite((float)cql_alpha)) {
+    set_err("%s: cql_alpha=%g is not a finite number >= 0", who, cql_alpha);
+    return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int oprl_learner_set_cql(oprl_learner* h, double cql_alpha, int32_t n_actions) {
+  if (!h) { set_err("oprl_learner_set_cql: null learner handle"); return OPRL_ERR_INVALID; }
+  if (n_actions < 0 || n_actions > kCqlMaxActions) {
+    set_err("oprl_learner_set_cql: n_actions=%d outside 0..%d (0 turns the mode off; 3 n_actions entries per row)", n_actions, kCqlMaxActions);
+    return OPRL_ERR_INVALID;
+  }
+  if (n_actions == 0) {            // off: plain SAC again (the rows stay for the next turn-on)
+    h->cql_n = 0;
+    return OPRL_OK;
+  }
+  if (h->cfg.algo != OPRL_SAC) {
+    set_err("oprl_learner_set_cql: conservative Q-learning is a mode of SAC learners (algo %d): twin critics, a tanh-Gaussian actor and a temperature", h->cfg.algo);
+    return OPRL_ERR_INVALID;
+  }
+  if (h->bf16 || h->x2) { set_err("oprl_learner_set_cql: the mode runs the exact-fp32 generic launch sequence only (precision f32)"); return OPRL_ERR_INVALID; }
+  if (!cql_alpha_ok("oprl_learner_set_cql", cql_alpha)) return OPRL_ERR_INVALID;
+  // (a member of a group is a fused learner: said first, so that the message names the reason that cannot be lifted)
+  if (h->group_member) { set_err("oprl_learner_set_cql: the learner is a member of a group (packed learners run the fused launches, which have no wide critic step)"); return OPRL_ERR_STATE; }
+  if (h->fused) {
+    set_err("oprl_learner_set_cql: the learner's fused launch form is on, which has no wide critic step; create it with no_fuse");
+    return OPRL_ERR_STATE;
+  }
+  if (h->cfg.export_grads || h->rccl.comm != nullptr || h->p2p_ok) {
+    set_err("oprl_learner_set_cql: gradient-exporting (export_grads) / data-parallel learners have no conservative-Q-learning step");
+    return OPRL_ERR_STATE;
+  }
+  if (h->cql_base == nullptr) {      // the mode's rows, once: no update allocates
+    const size_t Bm = (size_t)h->Bmax, slices = (Bm + kR - 1) / kR, A = (size_t)h->A, S = (size_t)h->S, nc = (size_t)h->nc;
+    // (Pool::take rounds every block up to 256 bytes: 64 floats of slack for each of the 7 blocks)
+    const size_t n = 2 * Bm * 2 * A + Bm * S + Bm * A + Bm + nc * Bm + nc * slices * 4 + 8 * 64;
+    float* p = nullptr;
+    if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) { set_err("hipMalloc(%zu) failed (conservative-Q-learning rows)", n * sizeof(float)); return OPRL_ERR_NOMEM; }
+    hipError_t e = hipMemset(p, 0, n * sizeof(float));
+    if (e != hipSuccess) { (void)hipFree(p); HIPC(e); }
+    Pool pool;
+    pool.base = reinterpret_cast<char*>(p); pool.cap = n * sizeof(float);
+    h->cql_raw_s = pool.take<float>(Bm * 2 * A);
+    h->cql_raw_s2 = pool.take<float>(Bm * 2 * A);
+    h->cql_ws = pool.take<float>(Bm * S);
+    h->cql_wa = pool.take<float>(Bm * A);
+    h->cql_logd = pool.take<float>(Bm);
+    h->cql_seed = pool.take<float>(nc * Bm);
+    h->cql_part = pool.take<float>(nc * slices * 4);
+    if (pool.used > pool.cap) { (void)hipFree(p); set_err("internal: the conservative-Q-learning rows overran their allocation"); return OPRL_ERR_STATE; }
+    h->cql_base = p;
+    h->cql_B = 0;
+  }
+  h->cql_alpha = cql_alpha;
+  h->cql_n = n_actions;
+  return OPRL_OK;
+}
+
+extern "C" int oprl_learner_set_cql_noise(oprl_learner* h, const float* eps, const float* uni) {
+  if (!h) { set_err("oprl_learner_set_cql_noise: null learner handle"); return OPRL_ERR_INVALID; }
+  h->cql_eps = eps;
+  h->cql_uni = uni;
+  return OPRL_OK;
+}
+
+extern "C" int oprl_learner_read_cql(oprl_learner* h, float out_host[8], void* stream) {
+  if (!h || !out_host) { set_err("oprl_learner_read_cql: null argument"); return OPRL_ERR_INVALID; }
+  if (h->cql_base == nullptr) { set_err("oprl_learner_read_cql: the conservative-Q-learning mode was never on (oprl_learner_set_cql)"); return OPRL_ERR_STATE; }
+  hipStream_t st = (hipStream_t)stream;
+  const int B = h->cql_B, n = B > 0 ? (B + kR - 1) / kR : 0, nc = h->nc < 2 ? h->nc : 2;
+  std::vector<float> pc((size_t)nc * n * 4, 0.f);
+  if (n > 0) HIPC(hipMemcpyAsync(pc.data(), h->cql_part, sizeof(float) * 4 * n * nc, hipMemcpyDeviceToHost, st));
+  HIPC(hipStreamSynchronize(st));
+  RC(check_device_error(h));
+  for (int k = 0; k < 8; ++k) out_host[k] = 0.f;
+  if (n == 0) return OPRL_OK;
+  const double N = (double)h->cql_last_n;
+  for (int j = 0; j < nc; ++j) {
+    double s[3] = {0, 0, 0};                          // the per-slice sums, in slice order
+    for (int i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) s[k] += (double)pc[((size_t)j * n + i) * 4 + k];
+    // per critic: mean (lse - q) | mean q on the uniform actions | mean q on the actions drawn from pi(.|s)
+    out_host[j] = (float)(s[0] / (double)B);
+    out_host[2 + j] = (float)(s[1] / ((double)B * N));
+    out_host[4 + j] = (float)(s[2] / ((double)B * N));
+  }
+  out_host[6] = (float)(h->cql_alpha * ((double)out_host[0] + (double)out_host[1]));     // the penalty term of the summed critic loss
+  return OPRL_OK;
+}
+
+extern "C" int oprl_cql_rows(const float* s, const float* a, const float* raw_s, const float* raw_s2, const float* eps, const float* uni,
+                             uint64_t seed, uint64_t counter, int32_t B, int32_t S, int32_t A, int32_t N, float* ws_out, float* wa_out,
+                             float* logd_out, void* stream) {
+  if (!s || !a || !raw_s || !raw_s2 || !ws_out || !wa_out || !logd_out) { set_err("oprl_cql_rows: null argument"); return OPRL_ERR_INVALID; }
+  if (B < 1 || S < 1 || A < 1 || N < 1 || N > kCqlMaxActions || (int64_t)B * (1 + 3 * N) * (S > A ? S : A) > (1 << 30)) {
+    set_err("oprl_cql_rows: need B >= 1 (B=%d), S >= 1 (S=%d), A >= 1 (A=%d), n_actions in 1..%d (%d) and B (1 + 3 n_actions) max(S, A) <= 2^30",
+            B, S, A, kCqlMaxActions, N);
+    return OPRL_ERR_INVALID;
+  }
+  CqlRowsArgs g;
+  memset((void*)&g, 0, sizeof g);
+  g.s = s; g.a = a; g.raw_s = raw_s; g.raw_s2 = raw_s2; g.eps = eps; g.uni = uni;
+  g.key_eps = noise_key(seed, 0, 4); g.key_uni = noise_key(seed, 0, 5); g.ctr = counter;
+  g.B = B; g.S = S; g.A = A; g.N = N;
+  g.ws = ws_out; g.wa = wa_out; g.logd = logd_out;
+  HIPC(launch_cql_rows(g, (hipStream_t)stream));
+  return OPRL_OK;
+}
+
+extern "C" int oprl_cql_seed(const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
+                             const float* logd, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
+                             float* seed_out, float* y_out, float* part_out, float* part_cql_out, void* stream) {
+  if (!q || !qn1 || !r || !d || !logd || !seed_out || !part_out || !part_cql_out) { set_err("oprl_cql_seed: null argument"); return OPRL_ERR_INVALID; }
+  if (nc < 1 || nc > OPRL_MAX_CRITICS || B < 1 || N < 1 || N > kCqlMaxActions || (int64_t)B * (1 + 3 * N) > (1 << 30)) {
+    set_err("oprl_cql_seed: need critics in 1..%d (%d), B >= 1 (B=%d), n_actions in 1..%d (%d) and B (1 + 3 n_actions) <= 2^30",
+            OPRL_MAX_CRITICS, nc, B, kCqlMaxActions, N);
+    return OPRL_ERR_INVALID;
+  }
+  if (!cql_alpha_ok("oprl_cql_seed", cql_alpha)) return OPRL_ERR_INVALID;
+  const long Bw = (long)B * (1 + 3 * N);
+  CqlSeedArgs t;
+  memset((void*)&t, 0, sizeof t);
+  t.s.p0 = qn1; t.s.p1 = qn2; t.s.p2 = logp2;
+  t.s.alpha_const = (float)alpha; t.s.r = r; t.s.d = d; t.s.gamma = (float)gamma;
+  t.s.cval = 1.0f / (float)B;
+  t.s.y_out = y_out;
+  t.q = q; t.q_stride = Bw; t.logd = logd;
+  t.ca = (float)cql_alpha;
+  t.seed = seed_out; t.seed_stride = Bw;
+  t.partials = part_out; t.part_cql = part_cql_out;
+  t.nc = nc; t.B = B; t.N = N; t.n_slices = (B + kR - 1) / kR;
+  HIPC(launch_cql_seed(t, (hipStream_t)stream));
   return OPRL_OK;
 }
 
