@@ -14,10 +14,12 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from oprl.buffers.episodic_buffer import EpisodicReplayBuffer  # noqa: E402
 from oprl.buffers.hindsight_buffer import HindsightEpisodicReplayBuffer  # noqa: E402
 from oprl.buffers.nstep_buffer import NStepEpisodicReplayBuffer  # noqa: E402
+from oprl.buffers.offline_dataset import cut_pieces, fill_replay, load_dataset  # noqa: E402
+from oprl.buffers.prior_buffer import PriorDataReplayBuffer  # noqa: E402
 from oprl.buffers.prioritized_buffer import PrioritizedEpisodicReplayBuffer  # noqa: E402
 from oprl.environment import make_env as build_env  # noqa: E402
 from oprl.logging import make_text_logger_func  # noqa: E402
-from oprl.parse_args import check_her, check_per, parse_args  # noqa: E402
+from oprl.parse_args import check_her, check_per, check_prior, parse_args  # noqa: E402
 from oprl.runners.config import CommonParameters  # noqa: E402
 from oprl.runners.train import run_training  # noqa: E402
 
@@ -39,6 +41,7 @@ class TrainingScript:
 
     def __post_init__(self) -> None:
         self.args = parse_args(self.extra_flags)
+        self.prior = check_prior(self.args)  # --prior-data: a dataset in every batch, refused with --per, --n-step > 1, --her, --num-envs > 1
         self.per = check_per(self.args)      # --per: prioritized replay and an algorithm that applies its weights
         if self.per and not self.takes_per:
             raise ValueError(f"--per: {self.algo_name} does not train from prioritized replay (its loss takes no "
@@ -78,7 +81,20 @@ class TrainingScript:
                                                  max_episode_lenth=self.episode_length, **self.goal_layout, **kw).create()
         if self.per:
             return PrioritizedEpisodicReplayBuffer(**kw).create()
+        if self.prior:                  # prior data: the dataset as it is (the environment's observations are not normalised)
+            return PriorDataReplayBuffer(prior=self.make_prior_buffer(), prior_share=self.args.prior_share, **kw).create()
         return EpisodicReplayBuffer(**kw).create()
+
+    def make_prior_buffer(self):
+        """The ``--prior-data`` dataset in a replay with exactly the episode slots its pieces need (as configs/iql.py
+        sizes its own; fill_replay never wraps)."""
+        data = load_dataset(self.args.prior_data)
+        L = next(f.default for f in fields(EpisodicReplayBuffer) if f.name == "max_episode_lenth")
+        pieces, _ = cut_pieces(data, L)
+        buf = EpisodicReplayBuffer(buffer_size_transitions=(len(pieces) + 1) * L, state_dim=self.state_dim,
+                                   action_dim=self.action_dim, device=self.config.device).create()
+        fill_replay(buf, data, normalize=False)
+        return buf
 
     def run(self) -> None:
         run_training(make_algo=self.make_algo, make_env=self.make_env, make_replay_buffer=self.make_replay_buffer,

@@ -6,6 +6,10 @@ tools/make_offline_dataset.py writes one from a ``synthetic:`` environment — D
 
     python configs/cql.py --dataset data.npz --env synthetic:walker-walk [--cql-alpha 5.0] [--cql-actions 10] [--tune-alpha]
                           [--updates N] [--batch 256] [--updates-per-call K] [--no-normalize] [--n-step N]
+                          [--finetune-steps N [--prior-share 0.5]]
+
+``--finetune-steps N``: after the offline updates the same learner goes on for N environment steps online, every batch
+drawn partly from the dataset and partly from the fresh experience (trainers/finetune.py; not with ``--n-step > 1``).
 """
 import sys
 from dataclasses import fields
@@ -15,6 +19,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 from _common import TrainingScript  # noqa: E402
+from oprl.parse_args import check_finetune  # noqa: E402
 from oprl.algos.cql import CQL  # noqa: E402
 
 FLAGS = (
@@ -26,6 +31,7 @@ FLAGS = (
     ("--batch", int, 256, "minibatch rows"),
     ("--updates-per-call", int, 1000, "updates per step_n call; evaluation, saving and logging happen between calls"),
     ("--no-normalize", bool, False, "store the observations as they are instead of (x - mean) / (std + 1e-3)"),
+    ("--finetune-steps", int, 0, "after the offline updates: that many environment steps of online training, --prior-share of every batch from the dataset (0: none)"),
 )
 
 
@@ -42,6 +48,7 @@ if script.her:
     raise ValueError("--her: CQL trains from a fixed dataset here; hindsight replay is wired into the online scripts")
 if script.args.seeds != 1:
     raise ValueError("--seeds > 1: one offline run per invocation (--start_seed picks its seed)")
+finetune_steps = check_finetune(script.args)      # --finetune-steps: refused with --n-step > 1
 # the names a reference-style script defines at module level
 make_env, make_algo, make_logger, config = script.make_env, script.make_algo, script.make_logger, script.config
 
@@ -80,6 +87,11 @@ def run() -> None:
     OfflineTrainer(logger=logger, make_env_test=make_env, replay_buffer=buffer, algo=algo, obs_norm=norm,
                    num_updates=args.updates, updates_per_call=args.updates_per_call, batch_size=args.batch,
                    eval_interval=config.eval_every * 2, stdout_log_every=config.log_every, seed=seed).train()
+    if finetune_steps > 0:      # the same algorithm object goes on online, the dataset in every batch
+        from oprl_amd.trainers.finetune import finetune
+        finetune(algo=algo, prior_buffer=buffer, obs_norm=norm, make_env=make_env, logger=logger, num_steps=finetune_steps,
+                 batch_size=args.batch, prior_share=args.prior_share, seed=seed, eval_interval=config.eval_every,
+                 stdout_log_every=config.log_every)
 
 
 if __name__ == "__main__":

@@ -501,6 +501,29 @@ int oprl_replay_sample_her(oprl_replay* h, int32_t B, const int64_t* idx, uint64
                            float* out_s, float* out_a, float* out_r, float* out_d, float* out_s2, int32_t* out_ep,
                            int32_t* out_step, int32_t* out_future, void* stream);
 
+/* ---- prior data in the batch ------------------------------------------------------------------------
+ * Reference: none.  A replay may name a second replay, `prior` (a fixed dataset), and a share in [0, 1].  Of a batch of B
+ * rows the first B_p = min(B, max(0, (int)floor(share * B + 0.5))) (double arithmetic) come from `prior` and the rest
+ * from the replay itself; row i is oprl_replay_sample's row i — the same Philox call for (seed, counter, i), or idx[i] —
+ * over the episode table and storage of ITS source.  So rows [0, B_p) equal those rows of oprl_replay_sample(prior, B, ...)
+ * and rows [B_p, B) those of oprl_replay_sample on a plain handle with this replay's contents, bit for bit.
+ * set_prior: prior non-NULL switches the mode on (share 0 is allowed), prior NULL switches it off (the share is not
+ * read).  Host state only; the caller keeps `prior` alive while it is set.  OPRL_ERR_INVALID: a null h, a share that is
+ * not finite or outside [0, 1], prior == h, state or action dims that differ (episode slots and steps per episode may);
+ * OPRL_ERR_STATE: either handle samples n-step returns, relabels in hindsight or is prioritized, or prior has a prior of
+ * its own.  A refused call changes nothing.  With the mode on oprl_replay_sample and the learners' step_n / step_act /
+ * dp_step_n gather mixed batches; oprl_group_step_n refuses such a replay, and oprl_replay_set_nstep(n > 1),
+ * oprl_replay_set_her(G > 0) and oprl_replay_prio_enable on it return OPRL_ERR_STATE.  Replays that never call it are
+ * unchanged. */
+int oprl_replay_set_prior(oprl_replay* h, oprl_replay* prior, double share);
+/* The mixed batch (OPRL_ERR_STATE when the mode is off) and, when out_src is non-NULL, 1 per prior row and 0 per own row
+ * (int32[B]); out_ep / out_step are the slot inside the row's source, idx[i] a flat index into it.  Both handles are
+ * flushed on `stream` first.  OPRL_ERR_STATE, with nothing launched, when prior is no longer plain, or when a source
+ * that has to supply at least one row holds no transitions. */
+int oprl_replay_sample_mix(oprl_replay* h, int32_t B, const int64_t* idx, uint64_t seed, uint64_t counter,
+                           float* out_s, float* out_a, float* out_r, float* out_d, float* out_s2, int32_t* out_ep,
+                           int32_t* out_step, int32_t* out_src, void* stream);
+
 /* ---- prioritized replay (Schaul et al., ICLR 2016, proportional variant) ------------------------------------------
  * A sum tree over the E·L slots of a replay, in HBM next to it: leaf e·L + t is the priority of slot
  * (e, t).  A slot is live when e < episodes_counter and t < ep_lens[e] (the set oprl_replay_sample draws from); every

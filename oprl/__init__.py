@@ -10,10 +10,10 @@ _SUBMODULES = [
     "algos", "algos.protocols", "algos.base_algorithm", "algos.nn_models", "algos.nn_functions",
     "algos.ddpg", "algos.td3", "algos.sac", "algos.tqc", "algos.redq", "algos.d4pg", "algos.td3_bc", "algos.iql", "algos.cql",
     "buffers", "buffers.protocols", "buffers.episodic_buffer", "buffers.prioritized_buffer", "buffers.nstep_buffer",
-    "buffers.offline_dataset", "buffers.hindsight_buffer",
-    "environment", "environment.protocols", "environment.make_env", "environment.synthetic_goal",
+    "buffers.offline_dataset", "buffers.hindsight_buffer", "buffers.prior_buffer",
+    "environment", "environment.protocols", "environment.make_env", "environment.synthetic_goal", "environment.normalized",
     "runners", "runners.config", "runners.train", "runners.train_distrib",
-    "trainers", "trainers.protocols", "trainers.base_trainer", "trainers.vec_trainer", "trainers.offline_trainer",
+    "trainers", "trainers.protocols", "trainers.base_trainer", "trainers.vec_trainer", "trainers.offline_trainer", "trainers.finetune",
     "distrib", "distrib.queue", "distrib.env_worker", "distrib.policy_update_worker",
 ]
 for _name in _SUBMODULES:

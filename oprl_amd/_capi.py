@@ -140,6 +140,8 @@ SIGNATURES = {
     "oprl_replay_sample_nstep": (C.c_int, [_P, _I32, _P, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "oprl_replay_set_her": (C.c_int, [_P, _I32, _I32, _I32, _D, _I32, _I32, _D]),
     "oprl_replay_sample_her": (C.c_int, [_P, _I32, _P, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oprl_replay_set_prior": (C.c_int, [_P, _P, _D]),
+    "oprl_replay_sample_mix": (C.c_int, [_P, _I32, _P, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "oprl_replay_prio_enable": (C.c_int, [_P, _D, _D, _P]),
     "oprl_replay_prio_sample": (C.c_int, [_P, _I32, _U64, _U64, _D, _P, _P, _P, _P, _P, _P, _P, _P]),
     "oprl_replay_prio_update": (C.c_int, [_P, _I32, _P, _P, _P]),

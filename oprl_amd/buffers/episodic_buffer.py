@@ -370,16 +370,20 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
                 t.empty((B, 1), dtype=t.float32, device=dev), t.empty((B, 1), dtype=t.float32, device=dev),
                 t.empty((B, S), dtype=t.float32, device=dev))
 
+    def _refuse_empty(self, batch_size: int) -> None:
+        """A batch of ``batch_size`` rows needs transitions to draw from (buffers/prior_buffer.py: in both sources)."""
+        if self._number_transitions <= 0:
+            raise ValueError("cannot sample from an empty replay buffer")
+
     def _sample(self, fn: str, batch_size: int, inds, return_indices: bool, extra: bool | None = None):
         """One call of the gather entry point ``fn`` — oprl_replay_sample, or with ``extra`` not None one of its
-        n-step / hindsight forms, which take one more optional int32[B] output — at this buffer's (seed, counter),
+        n-step / hindsight / prior-data forms, which take one more optional int32[B] output — at this buffer's (seed, counter),
         which then moves on.  Returns ``(rows, (ep, step) | None, extra | None)``."""
         self.check_created()
         if self._handle is None:
             raise RuntimeError("sample() runs on the MI355X gather kernel; create the buffer with "
                                "device='cuda' (there is no CPU sampler)")
-        if self._number_transitions <= 0:
-            raise ValueError("cannot sample from an empty replay buffer")
+        self._refuse_empty(int(batch_size))
         self._sync_lens()
         B, dev = int(batch_size), self._dev
         rows = self._empty_rows(B)

@@ -1867,6 +1867,11 @@ int RowStager::check(const char* who, const oprl_learner* h, const oprl_replay* 
     set_err("%s: the replay relabels goals in hindsight (oprl_replay_set_her); packed learners take plain replays only", who);
     return OPRL_ERR_STATE;
   }
+  // A replay with prior data (oprl_replay_set_prior) likewise: its rows come from two storages.
+  if (replay_prior(replay) != 0 && packed) {
+    set_err("%s: the replay mixes prior data into its batches (oprl_replay_set_prior); packed learners take plain replays only", who);
+    return OPRL_ERR_STATE;
+  }
   return OPRL_OK;
 }
 
@@ -1945,7 +1950,8 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
   RC(RowStager::check("step_n", h, replay, false, K, B, &nstep));
   RC(cql_rows_fit(h, "step_n", B));
   RowStager stg;
-  const bool plain = nstep == 1 && replay_her(replay) == 0;      // else: the sample + update loop at the end
+  // else (n-step, hindsight or prior-data rows): the sample + update loop at the end
+  const bool plain = nstep == 1 && replay_her(replay) == 0 && replay_prior(replay) == 0;
   if (plain && use_fused(h, B)) {
     RC(stg.open("step_n", h, replay, seed, stream));
     // k_ddpg_chain: up to chain_max updates per launch, the rows of update u + 1 staged by update u inside the launch

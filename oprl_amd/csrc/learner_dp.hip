@@ -201,12 +201,12 @@ extern "C" int oprl_learner_dp_step_n(oprl_learner* h, oprl_replay* replay, int3
                                       uint64_t seed, void* stream) {
   if (!h || !replay) { set_err("oprl_learner_dp_step_n: null handle"); return OPRL_ERR_INVALID; }
   if (!h->rccl.comm && !h->p2p_ok) { set_err("oprl_learner_dp_step_n: call oprl_comm_init (or connect the peer windows) first"); return OPRL_ERR_STATE; }
-  // an n-step replay or a hindsight replay (§18) takes the sample + dp_update loop at the end, as in oprl_learner_step_n
+  // an n-step replay, a hindsight replay (§18) or one with prior data (§20) takes the sample + dp_update loop at the end, as in oprl_learner_step_n
   int nstep = 1;
   RC(RowStager::check("dp_step_n", h, replay, false, K, B, &nstep));
   // every rank samples its own shard: the Philox key mixes the rank in
   const uint64_t rseed = seed * 0x9E3779B97F4A7C15ull + (uint64_t)dp_rank(h);
-  if (nstep == 1 && replay_her(replay) == 0 && use_fused(h, B)) {
+  if (nstep == 1 && replay_her(replay) == 0 && replay_prior(replay) == 0 && use_fused(h, B)) {
     RowStager stg;
     RC(stg.open("dp_step_n", h, replay, rseed, stream));
     // The gradient exchange inside the tiles of the whole-update launch (peer windows, PrecX2 learners): the data-parallel

@@ -71,6 +71,7 @@ hipError_t launch_redq_min(const float* q, long net_stride, int ldq, int M, int 
 int replay_dims(const oprl_replay* h, int* S, int* A);
 int replay_nstep(const oprl_replay* h, int* n, double* gamma);
 int replay_her(const oprl_replay* h);     // the goal dimension of a replay in hindsight mode (replay_her.hip), else 0
+int replay_prior(const oprl_replay* h);   // 1 for a replay that mixes prior data into its batches (replay_mix.hip), else 0
 int replay_view(const oprl_replay* h, const float** states, const float** actions,
                 const float** rewards, const float** dones, const int** ends, int* n_eps, int* L,
                 long* n_transitions);
@@ -550,7 +551,7 @@ struct RowStager {
   int cur = 0;                 // the set the coming update reads
   bool staged = false;         // ... which a launch of the previous update has already filled
   int flip = 0;                // sets done() moves on by: 1 after phase-1 staging, U after a chain launch, else 0
-  // do the replay and K / B fit (dims; K / B; an n-step replay's gamma; packed learners: one-step, no hindsight)?  *nstep > 1 or replay_her(replay) > 0: no in-kernel gather
+  // do the replay and K / B fit (dims; K / B; an n-step replay's gamma; packed learners: one-step, no hindsight, no prior data)?  *nstep > 1, replay_her(replay) > 0 or replay_prior(replay): no in-kernel gather
   static int check(const char* who, const oprl_learner* h, const oprl_replay* replay, bool packed, int K, int B, int* nstep);
   int open(const char* who, const oprl_learner* h, oprl_replay* replay, uint64_t seed, void* stream);
   void bind(const oprl_learner* h, uint64_t seed);     // the seed and staging sets of (another) learner over the opened view

@@ -310,6 +310,8 @@ extern "C" int oprl_replay_sample(oprl_replay* h, int32_t B, const int64_t* idx,
     return oprl_replay_sample_nstep(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
   if (h->her.G > 0)      // hindsight mode (oprl_replay_set_her): the same draw, relabelled rows (replay_her.hip)
     return oprl_replay_sample_her(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
+  if (h->prior)          // prior-data mode (oprl_replay_set_prior): the same draw, over two replays (replay_mix.hip)
+    return oprl_replay_sample_mix(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, nullptr, stream);
   GatherArgs G;
   gather_fill(h, B, idx, seed, counter, out_s, out_a, out_r, out_d, out_s2, out_ep, out_step, &G.src, &G.out);
   return gather_launch("oprl_replay_sample: buffer is empty (np.random.randint(0, 0) raises in the reference)",

@@ -1,7 +1,7 @@
 // replay_gather.h — what the gather kernels of the replay sampler share: k_replay_gather (replay.hip),
-// k_replay_gather_nstep (replay_nstep.hip) and k_replay_gather_her (replay_her.hip).
+// k_replay_gather_nstep (replay_nstep.hip), k_replay_gather_her (replay_her.hip) and k_replay_gather_mix (replay_mix.hip).
 //
-// One shape for all three: 256 threads and 16 samples per workgroup; the episode table staged in LDS
+// One shape for all of them: 256 threads and 16 samples per workgroup; the episode table staged in LDS
 // (replay_index.h); lanes < 16 draw their sample's slot (e, t) into s_ep / s_t; the rows go to an LDS stage and from
 // there, coalesced, to the five outputs.  The pieces below are that shape — every one __forceinline__, so a kernel is
 // the code it would be with the pieces written out — and the host side of it: the kernels' common arguments, the
@@ -98,6 +98,35 @@ __device__ __forceinline__ void gather_stage_rows(const GatherSrc& G, int n_here
       if (c >= 2 * S) src = G.actions + (e * G.L + t) * A + (c - 2 * S);
       if (c == 2 * S + A) src = G.rewards + e * G.L + t;
       if (c == 2 * S + A + 1) src = G.dones + e * G.L + t;
+      v[j] = *src;
+    }
+#pragma unroll
+    for (int j = 0; j < kU; ++j) {
+      const int idx = i0 + j * kGatherThreads + tid;
+      if (idx < n_here * W) stage[idx] = v[j];
+    }
+  }
+}
+
+// The same copy for a workgroup whose samples [0, split) lie in P and [split, n_here) in O (k_replay_gather_mix,
+// replay_mix.hip): the sample's source selects the base pointers and L — selects, no branch — and S and A are common
+// to the two.  Beside gather_stage_rows, not in it: the three kernels above keep their code.
+__device__ __forceinline__ void gather_stage_rows_mix(const GatherSrc& P, const GatherSrc& O, int split, int n_here,
+                                                      const int* s_ep, const int* s_t, float* stage) {
+  const int tid = threadIdx.x, S = O.S, A = O.A, W = 2 * S + A + 2;
+  constexpr int kU = 4;
+  for (int i0 = 0; i0 < n_here * W; i0 += kU * kGatherThreads) {
+    float v[kU];
+#pragma unroll
+    for (int j = 0; j < kU; ++j) {
+      const int idx = min(i0 + j * kGatherThreads + tid, n_here * W - 1);
+      const int smp = idx / W, c = idx - smp * W;
+      const bool p = smp < split;
+      const long e = s_ep[smp], t = s_t[smp], L = p ? P.L : O.L;
+      const float* src = (p ? P.states : O.states) + (e * (L + 1) + t) * S + c;         // s | s' contiguous
+      if (c >= 2 * S) src = (p ? P.actions : O.actions) + (e * L + t) * A + (c - 2 * S);
+      if (c == 2 * S + A) src = (p ? P.rewards : O.rewards) + e * L + t;
+      if (c == 2 * S + A + 1) src = (p ? P.dones : O.dones) + e * L + t;
       v[j] = *src;
     }
 #pragma unroll

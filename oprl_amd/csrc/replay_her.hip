@@ -137,6 +137,10 @@ extern "C" int oprl_replay_set_her(oprl_replay* h, int32_t ag_off, int32_t g_off
     set_err("oprl_replay_set_her: this replay is prioritized; hindsight goals over the sum tree are not supported");
     return OPRL_ERR_STATE;
   }
+  if (h->prior) {
+    set_err("oprl_replay_set_her: this replay mixes prior data into its batches (oprl_replay_set_prior); hindsight goals over mixed batches are not supported");
+    return OPRL_ERR_STATE;
+  }
   h->her = oprl::HerMode{(int)ag_off, (int)g_off, (int)G, (int)strategy, (int)reward, ratio, threshold};
   return OPRL_OK;
 }

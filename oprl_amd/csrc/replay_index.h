@@ -1,6 +1,7 @@
 // replay_index.h — the uniform sampler's draw, and flat transition index -> (episode, step), for every device-side
 // sampler: the gather kernels (replay_gather.h: k_replay_gather in replay.hip, k_replay_gather_nstep in
-// replay_nstep.hip, k_replay_gather_her in replay_her.hip) and the in-kernel gathers of the fused and layer-by-layer
+// replay_nstep.hip, k_replay_gather_her in replay_her.hip, k_replay_gather_mix in replay_mix.hip, which draws each
+// row over the table of the row's own replay) and the in-kernel gathers of the fused and layer-by-layer
 // launches (batch_rows.h: load_batch, prefetch_rows_direct).  All of them pick the same slot for the same
 // (seed, counter, row): the gather kernels call draw_slot; batch_rows.h's two sites carry its no-index path written
 // out (kUniformWord, bounded_u32 of r.x, find_episode), because the call moves an instruction selection inside the

@@ -1,7 +1,7 @@
 // replay_internal.h — the replay handle (struct oprl_replay) and what the replay's translation units share: the writes,
 // the flush and the uniform sampler (replay.hip), the sum tree of prioritized replay (replay_prio.hip), the n-step and
-// hindsight samplers (replay_nstep.hip, replay_her.hip; their kernels' common shape is replay_gather.h) and the
-// many-episodes write (replay_rows.hip).  learner_per.hip reads the handle's sum tree too.
+// hindsight samplers (replay_nstep.hip, replay_her.hip; their kernels' common shape is replay_gather.h), the sampler
+// over two replays (replay_mix.hip) and the many-episodes write (replay_rows.hip).  learner_per.hip reads the handle's sum tree too.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -96,6 +96,10 @@ struct oprl_replay {
   double nstep_gamma = 1.0;
   // hindsight mode (oprl_replay_set_her): with her.G > 0 oprl_replay_sample gathers relabelled rows
   oprl::HerMode her;
+  // prior-data mode (oprl_replay_set_prior): with prior non-null oprl_replay_sample gathers the first
+  // floor(prior_share · B + 0.5) rows of a batch from `prior` (the caller keeps it alive) and the rest from this replay
+  oprl_replay* prior = nullptr;
+  double prior_share = 0.0;
   // oprl_replay_write_rows (replay_rows.hip): double-buffered pinned staging of its own for up to kRowsMax
   // records of reclen floats, allocated by the first call
   bool rows_ready = false;

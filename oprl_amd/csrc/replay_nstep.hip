@@ -138,6 +138,10 @@ extern "C" int oprl_replay_set_nstep(oprl_replay* h, int32_t n, double gamma) {
     set_err("oprl_replay_set_nstep: this replay relabels goals in hindsight (oprl_replay_set_her); n-step returns over relabelled rows are not supported");
     return OPRL_ERR_STATE;
   }
+  if (h->prior && n > 1) {
+    set_err("oprl_replay_set_nstep: this replay mixes prior data into its batches (oprl_replay_set_prior); n-step returns over mixed batches are not supported");
+    return OPRL_ERR_STATE;
+  }
   h->nstep = n;
   h->nstep_gamma = gamma;
   return OPRL_OK;

@@ -342,6 +342,10 @@ extern "C" int oprl_replay_prio_enable(oprl_replay* h, double alpha, double eps,
     set_err("oprl_replay_prio_enable: this replay relabels goals in hindsight (oprl_replay_set_her); the sum tree over relabelled rows is not supported");
     return OPRL_ERR_STATE;
   }
+  if (h->prior) {
+    set_err("oprl_replay_prio_enable: this replay mixes prior data into its batches (oprl_replay_set_prior); the sum tree over mixed batches is not supported");
+    return OPRL_ERR_STATE;
+  }
   hipStream_t st = (hipStream_t)stream;
   int rc = oprl_replay_flush(h, stream);          // the episode table the leaves start from
   if (rc != OPRL_OK) return rc;

@@ -76,7 +76,55 @@ def parse_args(extra=()) -> argparse.Namespace:
                         help="with --her: the relabelled share of the sampled rows that can be relabelled (0.8 = 4 hindsight goals per stored one)")
     parser.add_argument("--her-strategy", type=str, default="future", choices=("future", "final"),
                         help="with --her: goals from a uniformly drawn later step of the episode (future) or from its last one (final)")
+    # extension: a fixed dataset in every batch (buffers/prior_buffer.py)
+    parser.add_argument("--prior-data", type=str, default=None,
+                        help="online training with prior data: an .npz dataset (buffers/offline_dataset.py) that supplies "
+                             "--prior-share of every batch (not with --per, --n-step > 1, --her, --num-envs > 1)")
+    parser.add_argument("--prior-share", type=float, default=0.5,
+                        help="with --prior-data, or --finetune-steps of the offline scripts: the share of every batch that "
+                             "comes from the dataset (0.5 = symmetric sampling)")
     return parser.parse_args()
+
+
+def check_share(args: argparse.Namespace) -> float:
+    share = getattr(args, "prior_share", 0.5)
+    if not 0 <= share <= 1:      # (nan fails)
+        raise ValueError(f"--prior-share {share}: the dataset's share of a batch must lie in [0, 1]")
+    return share
+
+
+def check_prior(args: argparse.Namespace) -> bool:
+    """Is ``--prior-data`` given?  Raises ValueError when it comes with ``--per``, ``--n-step > 1`` or ``--her`` (the
+    replay refuses those rows on either side of a mixed batch) or with ``--num-envs > 1`` / ``--open-episodes`` (not
+    built): the scripts say so before anything is built."""
+    if not getattr(args, "prior_data", None):
+        return False
+    check_share(args)
+    for on, flag in ((getattr(args, "per", False), "--per"), (getattr(args, "n_step", 1) > 1, f"--n-step {getattr(args, 'n_step', 1)}"),
+                     (getattr(args, "her", False), "--her"), (getattr(args, "num_envs", 1) > 1, f"--num-envs {getattr(args, 'num_envs', 1)}"),
+                     (getattr(args, "open_episodes", False), "--open-episodes")):
+        if on:
+            raise ValueError(f"--prior-data with {flag}: batches mixed from a dataset and fresh experience are plain "
+                             "one-step rows collected by one environment; drop one of the two")
+    return True
+
+
+def check_finetune(args: argparse.Namespace) -> int:
+    """``--finetune-steps`` of the offline scripts (0: none).  Raises ValueError for a negative count, with
+    ``--n-step > 1`` (mixed batches are one-step rows) and with ``--prior-data`` (the dataset is ``--dataset``)."""
+    steps = getattr(args, "finetune_steps", 0)
+    if getattr(args, "prior_data", None):
+        raise ValueError("--prior-data: an offline script's dataset is --dataset; --finetune-steps N continues online "
+                         "with that dataset in every batch")
+    if steps < 0:
+        raise ValueError(f"--finetune-steps {steps}: expected >= 0")
+    if steps == 0:
+        return 0
+    check_share(args)
+    if getattr(args, "n_step", 1) > 1:
+        raise ValueError(f"--finetune-steps with --n-step {args.n_step}: batches mixed from the dataset and fresh "
+                         "experience are one-step rows; drop one of the two")
+    return steps
 
 
 def check_her(args: argparse.Namespace) -> bool:
