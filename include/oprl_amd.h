@@ -12,6 +12,8 @@
  *                    (Kostrikov et al. 2021) as a mode of a TD3 learner with a caller-owned value net
  *   oprl_learner_set_cql / read_cql / set_cql_noise, oprl_cql_rows, oprl_cql_seed   no counterpart: conservative Q-learning
  *                    (Kumar et al. 2020, CQL(H)) as a mode of a SAC learner
+ *   oprl_learner_set_calql / update_calql, oprl_replay_returns, oprl_cql_seed_cal   no counterpart: calibrated Q-learning
+ *                    (Nakamoto et al. 2023, Cal-QL), the calibrated form of that mode
  *   oprl_replay_*    ReplayBufferProtocol                 buffers/protocols.py:6-26
  *                    EpisodicReplayBuffer.{add_transition,sample}  buffers/episodic_buffer.py:81-133
  *   oprl_mlp_*       MLP / Critic / policies forward      algos/nn_models.py:27-194
@@ -524,6 +526,24 @@ int oprl_replay_sample_mix(oprl_replay* h, int32_t B, const int64_t* idx, uint64
                            float* out_s, float* out_a, float* out_r, float* out_d, float* out_s2, int32_t* out_ep,
                            int32_t* out_step, int32_t* out_src, void* stream);
 
+/* ---- returns-to-go of sampled slots -------------------------------------------------------------------
+ * Reference: none.  ep[B], step[B] (device, int32) are the slots (e, t) of B rows inside each row's SOURCE, exactly what
+ * the gathers write to out_ep / out_step: the source is h, and with h in prior-data mode rows i < B_p (the formula above,
+ * from the share on the handle: the split is by row index) read h's prior.  With len_e the episode's stored steps from
+ * the source's episode table (the in-progress tail included) and T the first k >= t with dones[e, k] != 0, or len_e - 1
+ * when there is none,
+ *   out_g[i] = sum_{k = t .. T} gamma^(k - t) rewards[e, k]
+ * with NO bootstrap at a truncation (a timeout, a dataset piece cut at L, an episode still running end the sum at the last
+ * stored step): an underestimate of the return for non-negative rewards.  t >= len_e gives the single term rewards[e, t];
+ * a row with e outside [0, E) or t outside [0, L) of its source reads nothing and gives 0 (the arrays are the caller's
+ * and cannot be checked on the host).  float32, a fixed summation order (csrc/replay_returns.hip): the same bits in every
+ * run.  Nothing is written past out_g[B].  h is flushed on `stream` first, and its prior too.  n-step and prioritized
+ * handles are fine: G depends on (e, t) only.  OPRL_ERR_INVALID: a null pointer, B < 1, gamma outside (0, 1];
+ * OPRL_ERR_STATE, with nothing launched: a source in hindsight mode (its rewards are relabelled per sample), a source
+ * that has to supply a row and holds no transitions. */
+int oprl_replay_returns(oprl_replay* h, int32_t B, const int32_t* ep, const int32_t* step, double gamma, float* out_g,
+                        void* stream);
+
 /* ---- prioritized replay (Schaul et al., ICLR 2016, proportional variant) ------------------------------------------
  * A sum tree over the E·L slots of a replay, in HBM next to it: leaf e·L + t is the priority of slot
  * (e, t).  A slot is live when e < episodes_counter and t < ep_lens[e] (the set oprl_replay_sample draws from); every
@@ -667,7 +687,9 @@ int oprl_iql_seed(const float* q1, const float* q2, const float* v, const float*
 int oprl_learner_set_cql(oprl_learner* h, double cql_alpha, int32_t n_actions);
 /* Of the last update with the mode on, the per-slice sums added in slice order, as means: out_host[0], [1] = mean_b
  * (logsumexp_e c_jbe - Q_j(s_b, a_b)) of critic 0, 1; [2], [3] = their mean Q on the uniform actions; [4], [5] = on the actions
- * drawn from pi(.|s_b); [6] = cql_alpha ([0] + [1]), the penalty term of the summed loss; [7] = 0.  Synchronises `stream`.
+ * drawn from pi(.|s_b); [6] = cql_alpha ([0] + [1]), the penalty term of the summed loss; [7] = after a calibrated update
+ * (oprl_learner_set_calql) the share of the policy entries at the bound, sum_j #{(b, e >= N) : q_jbe < g_b} / (nc B 2N), else
+ * 0.  Synchronises `stream`.
  * OPRL_ERR_STATE for a learner on which the mode was never on. */
 int oprl_learner_read_cql(oprl_learner* h, float out_host[8], void* stream);
 /* Test hook, like noise0 / noise1 of oprl_learner_update: device arrays standing in for the mode's draws, read by every
@@ -694,6 +716,31 @@ int oprl_cql_rows(const float* s, const float* a, const float* raw_s, const floa
 int oprl_cql_seed(const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
                   const float* logd, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
                   float* seed_out, float* y_out, float* part_out, float* part_cql_out, void* stream);
+/* The calibrated kernel on the same rows: oprl_cql_seed's arguments and g[B] (before `stream`, which stays last), the rows'
+ * returns-to-go.  At the policy entries e in [N, 3N) of row b — the actions from pi(.|s_b) and pi(.|s'_b); the uniform ones are
+ * not bounded — c_e = max(q_e, g_b) - logd_e, and seed(b, e) = (cql_alpha softmax(c)_e) (1/B) if q_e >= g_b, else 0 (written).
+ * Everything else is formed as oprl_cql_seed forms it, from c; the sums of q are sums of the critics' own q.  Slot 3 of
+ * part_cql_out takes the slice's count of bounded entries, #{e >= N : q_e < g_b}.  g = -inf everywhere gives oprl_cql_seed's
+ * outputs bit for bit (and counts 0).  OPRL_ERR_INVALID as oprl_cql_seed, and for a null g. */
+int oprl_cql_seed_cal(const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
+                      const float* logd, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
+                      float* seed_out, float* y_out, float* part_out, float* part_cql_out, const float* g, void* stream);
+
+/* ---- Calibrated Q-learning (Nakamoto et al. 2023, Cal-QL): the calibrated form of the mode above.  Inside the
+ * conservative penalty the critics' values at the policy actions are bounded below by the rows' returns-to-go g
+ * (oprl_replay_returns); the TD term, the actor step, the temperature step and Polyak do not change.  on != 0 needs the CQL
+ * mode on (OPRL_ERR_STATE otherwise) and, the first time, allocates [max_batch] rows for step_n's slots and returns;
+ * oprl_learner_set_cql(.., 0) turns this form off with the mode.  With it on: oprl_learner_step_n (and step_act /
+ * step_act_rows through it) takes the sampler's slots, calls oprl_replay_returns with the learner's gamma and updates with
+ * them, over a plain, an n-step, a prioritized and a prior-data replay alike — a hindsight replay is refused with
+ * OPRL_ERR_STATE before anything is launched; oprl_learner_update / update_phase return OPRL_ERR_STATE (the rows carry no
+ * returns); oprl_learner_update_weighted and oprl_learner_step_n_prio return OPRL_ERR_STATE as under the CQL mode.  A
+ * refused call changes nothing. */
+int oprl_learner_set_calql(oprl_learner* h, int32_t on);
+/* oprl_learner_update with the rows' returns-to-go g[B]: the two-call path of the calibrated form.  OPRL_ERR_INVALID: a
+ * null g; OPRL_ERR_STATE: the calibrated form is off. */
+int oprl_learner_update_calql(oprl_learner* h, const float* s, const float* a, const float* r, const float* d, const float* s2,
+                              const float* g, int32_t B, const float* noise0, const float* noise1, void* stream);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,7 @@ SIGNATURES = {
     "oprl_replay_sample_her": (C.c_int, [_P, _I32, _P, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "oprl_replay_set_prior": (C.c_int, [_P, _P, _D]),
     "oprl_replay_sample_mix": (C.c_int, [_P, _I32, _P, _U64, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oprl_replay_returns": (C.c_int, [_P, _I32, _P, _P, _D, _P, _P]),
     "oprl_replay_prio_enable": (C.c_int, [_P, _D, _D, _P]),
     "oprl_replay_prio_sample": (C.c_int, [_P, _I32, _U64, _U64, _D, _P, _P, _P, _P, _P, _P, _P, _P]),
     "oprl_replay_prio_update": (C.c_int, [_P, _I32, _P, _P, _P]),
@@ -163,6 +164,9 @@ SIGNATURES = {
     "oprl_learner_set_cql_noise": (C.c_int, [_P, _P, _P]),
     "oprl_cql_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "oprl_cql_seed": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
+    "oprl_cql_seed_cal": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "oprl_learner_set_calql": (C.c_int, [_P, _I32]),
+    "oprl_learner_update_calql": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P]),
 }
 
 _lib = None

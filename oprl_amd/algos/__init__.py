@@ -1,4 +1,4 @@
-"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG``, ``TD3BC``, ``IQL`` and ``CQL`` are also served
+"""The algorithms, one module each (``oprl_amd.algos.ddpg`` ...).  ``D4PG``, ``TD3BC``, ``IQL``, ``CQL`` and ``CalQL`` are also served
 from here, resolved on first use so that importing the package stays free of torch."""
 
 
@@ -15,4 +15,7 @@ def __getattr__(name: str):
     if name == "CQL":
         from oprl_amd.algos.cql import CQL
         return CQL
+    if name == "CalQL":
+        from oprl_amd.algos.calql import CalQL
+        return CalQL
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

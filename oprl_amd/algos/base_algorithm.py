@@ -565,7 +565,7 @@ class HipLearner:
         buf = (C.c_float * 8)()
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_read_cql(self.handle, buf, _capi.current_stream()), "oprl_learner_read_cql")
-        keys = ("gap1", "gap2", "q_rand1", "q_rand2", "q_pi1", "q_pi2", "penalty")
+        keys = ("gap1", "gap2", "q_rand1", "q_rand2", "q_pi1", "q_pi2", "penalty", "bound_rate")
         return dict(zip(keys, (float(x) for x in buf)))
 
     def set_cql_noise(self, eps: t.Tensor | None, uni: t.Tensor | None) -> None:
@@ -575,6 +575,27 @@ class HipLearner:
         self._cql_noise = (prep(eps), prep(uni))
         _capi.check(self.lib.oprl_learner_set_cql_noise(self.handle, _capi.ptr(self._cql_noise[0]), _capi.ptr(self._cql_noise[1])),
                     "oprl_learner_set_cql_noise")
+
+    def set_calql(self, on: bool) -> None:
+        """The calibrated form of the CQL mode (oprl_learner_set_calql; Cal-QL): the penalty's
+        policy entries are bounded below by the rows' returns-to-go, which ``update_calql`` takes and ``step_n``
+        computes.  Needs ``set_cql`` first; a refused call leaves the learner as it was."""
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_set_calql(self.handle, int(bool(on))), "oprl_learner_set_calql")
+
+    def update_calql(self, state, action, reward, done, next_state, returns, noise0=None, noise1=None) -> None:
+        """One update with the rows' returns-to-go ``returns`` ([B] or [B, 1]; oprl_learner_update_calql)."""
+        self.check_bound()
+        B, s, a, r, d, s2 = self._prep(state, action, reward, done, next_state)
+        g = t.as_tensor(returns).to(device=self.device, dtype=t.float32).reshape(-1).contiguous()
+        if g.numel() != B:
+            raise ValueError(f"{g.numel()} returns for a batch of {B}")
+        n0 = None if noise0 is None else noise0.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        n1 = None if noise1 is None else noise1.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_update_calql(
+                self.handle, _capi.ptr(s), _capi.ptr(a), _capi.ptr(r), _capi.ptr(d), _capi.ptr(s2), _capi.ptr(g), B,
+                _capi.ptr(n0), _capi.ptr(n1), _capi.current_stream()), "oprl_learner_update_calql")
 
     def set_iql(self, value_mlp: MLP | None, expectile: float = 0.7, beta: float = 3.0, adv_clip: float = 100.0,
                 lr_value: float = 3e-4) -> None:

@@ -417,6 +417,33 @@ class EpisodicReplayBuffer(ReplayBufferProtocol):
         rows, pair, _ = self._sample("oprl_replay_sample", batch_size, inds, return_indices)
         return (rows, pair) if return_indices else rows
 
+    def _sync_sources(self) -> None:
+        """The episode table of every storage a batch's rows come from, up to date on the device."""
+        self._sync_lens()
+
+    def returns_to_go(self, episodes, steps, gamma: float | None = None) -> t.Tensor:
+        """The discounted return-to-go of the slots ``(episodes[i], steps[i])`` — what ``sample(return_indices=True)``
+        gives — as a float32 device tensor [B] (oprl_replay_returns): the rewards from the slot to
+        the episode's first done at or after it, or to its last stored step (no bootstrap at a truncation), discounted
+        by ``gamma`` (default: the buffer's own).  A slot outside the storage gives 0."""
+        self.check_created()
+        if self._handle is None:
+            raise RuntimeError("returns_to_go() runs on the MI355X returns kernel; create the buffer with "
+                               "device='cuda' (there is no CPU path)")
+        dev = self._dev
+        ep = t.as_tensor(episodes).to(device=dev, dtype=t.int32).reshape(-1).contiguous()
+        st = t.as_tensor(steps).to(device=dev, dtype=t.int32).reshape(-1).contiguous()
+        if ep.numel() != st.numel():
+            raise ValueError(f"{ep.numel()} episodes for {st.numel()} steps")
+        B = ep.numel()
+        self._sync_sources()
+        out = t.empty(B, dtype=t.float32, device=dev)
+        with _capi.on_device(dev):
+            _capi.check(self._lib.oprl_replay_returns(
+                self._handle, B, _capi.ptr(ep), _capi.ptr(st), float(self.gamma if gamma is None else gamma),
+                _capi.ptr(out), _capi.current_stream()), "oprl_replay_returns")
+        return out
+
     # ---- checkpoint (SURVEY.md 8f N4) ------------------------------------------------------
     def state_dict(self) -> dict:
         """Storage tensors (host copies) and the bookkeeping that decides where the next

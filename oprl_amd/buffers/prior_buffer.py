@@ -107,6 +107,12 @@ class PriorDataReplayBuffer(EpisodicReplayBuffer):
             self.prior.handle       # (the property syncs the prior's table)
         return super().handle
 
+    def _sync_sources(self) -> None:
+        """``returns_to_go``: rows ``[0, n_prior(len(episodes)))`` are slots of the prior (the split is by row index)."""
+        if self.prior is not None and self._handle is not None:
+            self.prior._sync_lens()
+        super()._sync_sources()
+
     def sample(self, batch_size: int, inds: t.Tensor | npt.NDArray | None = None, return_indices: bool = False,
                return_source: bool = False):
         """``(state, action, reward, done, next_state)``, rows ``[0, n_prior(batch_size))`` from the prior and the rest

@@ -43,9 +43,11 @@ struct CqlSeedArgs {
   float* partials;               // out [nc][n_slices][4]: per slice of 16 data rows (sum (q - y)^2, sum q, sum y) — launch_reduce_partials' layout
   float* part_cql;               // out [nc][n_slices][4]: per slice (sum (lse - q), sum_b sum_k q on the uniform actions, ... on the kind-1 policy actions)
   int nc, B, N, n_slices;        // critics, minibatch rows, sampled actions per kind, (B + kR - 1) / kR
+  const float* g;                // the calibrated form only (Cal-QL): the rows' returns-to-go [B], the lower bound of
+                                 //   q at the policy entries e in [N, 3N); part_cql[..][3] then takes the count of bounded entries
 };
 
 hipError_t launch_cql_rows(const CqlRowsArgs& a, hipStream_t st);
-hipError_t launch_cql_seed(const CqlSeedArgs& a, hipStream_t st);
+hipError_t launch_cql_seed(const CqlSeedArgs& a, hipStream_t st);      // a.g null: the plain kernel; else the calibrated one
 
 }  // namespace oprl

@@ -89,6 +89,14 @@ __device__ __forceinline__ float cql_td_target(const SeedArgs& S, int gr) {
 // and the slice sums over 16 adjacent lanes in the slice kernels' order (k_td_weighted_seed's butterfly, lanes past B hold
 // zeros).  The entries are re-read in each pass (3 N <= 48 floats per row and critic, from L2) instead of kept in an
 // indexed register array.
+//
+// kCal, the calibrated form (Cal-QL, Nakamoto et al. 2023): at the policy entries e in [N, 3N) the critic's
+// value is bounded below by the row's return-to-go g_b — c_e = max(q_e, g_b) - logd_e in all three passes — and the bound
+// passes no gradient: seed(b, e) = (ca p_e)(1/B) if q_e >= g_b, else 0 (written, as 0).  The uniform entries are not
+// bounded.  Everything else is formed as in the plain form, from c; the sums of q stay sums of the critic's own q.  Slot 3
+// of part_cql takes the count of bounded entries (exact in float: at most 512 per slice).  The plain instantiation reads
+// no g and leaves slot 3 alone.
+template <bool kCal>
 __global__ __launch_bounds__(kCqlThreads) void k_cql_seed(const CqlSeedArgs A) {
 #pragma clang fp contract(off)
   const SeedArgs& S = A.s;
@@ -97,7 +105,8 @@ __global__ __launch_bounds__(kCqlThreads) void k_cql_seed(const CqlSeedArgs A) {
   const int N = A.N, E = 3 * N;
   const float y = ok ? cql_td_target(S, gr) : 0.f;
   for (int j = 0; j < A.nc; ++j) {       // (uniform trip count: the shuffles below need whole slices)
-    float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    constexpr int kV = kCal ? 7 : 6;
+    float v[kV] = {};
     if (ok) {
       const float* qj = A.q + (size_t)j * A.q_stride;
       float* sj = A.seed + (size_t)j * A.seed_stride;
@@ -105,18 +114,25 @@ __global__ __launch_bounds__(kCqlThreads) void k_cql_seed(const CqlSeedArgs A) {
       const float* qe = qj + (size_t)A.B + (size_t)gr * E;
       float* se = sj + (size_t)A.B + (size_t)gr * E;
       const float* ld = A.logd + (size_t)gr * E;
-      float m = qe[0] - ld[0];
-      for (int e = 1; e < E; ++e) m = fmaxf(m, qe[e] - ld[e]);
+      const float gb = kCal ? A.g[gr] : 0.f;
+      // the entry's value as the penalty sees it: the critic's, or in the calibrated form at a policy entry max(q_e, g_b)
+      auto qt = [&](int e) { return kCal && e >= N ? fmaxf(qe[e], gb) : qe[e]; };
+      float m = qt(0) - ld[0];
+      for (int e = 1; e < E; ++e) m = fmaxf(m, qt(e) - ld[e]);
       float z = 0.f, q_uni = 0.f, q_pi = 0.f;
       for (int e = 0; e < E; ++e) {
-        z += expf((qe[e] - ld[e]) - m);
+        z += expf((qt(e) - ld[e]) - m);
         if (e < N) q_uni += qe[e];
         else if (e < 2 * N) q_pi += qe[e];
       }
       const float lse = m + logf(z);
+      float n_bound = 0.f;
       for (int e = 0; e < E; ++e) {
-        const float p = expf((qe[e] - ld[e]) - m) / z;
-        se[e] = (A.ca * p) * S.cval;
+        const float p = expf((qt(e) - ld[e]) - m) / z;
+        float sd = (A.ca * p) * S.cval;
+        if (kCal && e >= N && !(qe[e] >= gb)) sd = 0.f;
+        if (kCal && e >= N && qe[e] < gb) n_bound += 1.f;
+        se[e] = sd;
       }
       sj[gr] = ((2.f * (q - y)) - A.ca) * S.cval;
       if (j == 0 && S.y_out != nullptr) S.y_out[gr] = y;
@@ -127,9 +143,10 @@ __global__ __launch_bounds__(kCqlThreads) void k_cql_seed(const CqlSeedArgs A) {
       v[3] = lse - q;
       v[4] = q_uni;
       v[5] = q_pi;
+      if constexpr (kCal) v[6] = n_bound;
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
+    for (int k = 0; k < kV; ++k) {
 #pragma unroll
       for (int mm = 1; mm < kR; mm <<= 1) v[k] += __shfl_xor(v[k], mm);
     }
@@ -138,6 +155,7 @@ __global__ __launch_bounds__(kCqlThreads) void k_cql_seed(const CqlSeedArgs A) {
       p[0] = v[0]; p[1] = v[1]; p[2] = v[2];
       float* c = A.part_cql + ((size_t)j * A.n_slices + slice) * 4;
       c[0] = v[3]; c[1] = v[4]; c[2] = v[5];
+      if constexpr (kCal) c[3] = v[6];
     }
   }
 }
@@ -157,7 +175,9 @@ hipError_t launch_cql_seed(const CqlSeedArgs& a, hipStream_t st) {
       a.q == nullptr || a.logd == nullptr || a.seed == nullptr || a.partials == nullptr || a.part_cql == nullptr || a.s.p0 == nullptr ||
       a.s.r == nullptr || a.s.d == nullptr || !(a.ca >= 0.f))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_cql_seed, dim3((a.B + kCqlThreads - 1) / kCqlThreads), dim3(kCqlThreads), 0, st, a);
+  const dim3 grid((a.B + kCqlThreads - 1) / kCqlThreads);
+  if (a.g != nullptr) hipLaunchKernelGGL(k_cql_seed<true>, grid, dim3(kCqlThreads), 0, st, a);
+  else hipLaunchKernelGGL(k_cql_seed<false>, grid, dim3(kCqlThreads), 0, st, a);
   return hipGetLastError();
 }
 

@@ -1052,11 +1052,12 @@ int cql_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st
   t.seed = h->cql_seed; t.seed_stride = h->Bmax;
   t.partials = h->part_c; t.part_cql = h->cql_part;
   t.nc = nc; t.B = B; t.N = N; t.n_slices = (B + kR - 1) / kR;
+  t.g = rows.g;                    // the calibrated seed when the rows carry returns-to-go
   prof_begin(3, st);
   e = launch_cql_seed(t, st);
   prof_end(st);
   HIPC(e);
-  h->cql_B = B; h->cql_last_n = N;
+  h->cql_B = B; h->cql_last_n = N; h->cql_last_cal = rows.g != nullptr;
   return for_each_net(h, nc, h->w_critic, st, [&](int j) {
     MlpArgs f = base_args(h, c.critics[j], false, Bw);
     f.do_bwd = 1;
@@ -1787,6 +1788,15 @@ extern "C" int oprl_abi_version(void) { return OPRL_ABI_VERSION; }
 namespace oprl_host {
 int learner_update_phase(oprl_learner* h, int phase, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream) {
   RC(check_batch(h, rows.cur.s, rows.cur.a, rows.cur.r, rows.cur.d, rows.cur.s2, B));
+  if (h->calql_on && rows.g == nullptr) {
+    set_err("update: the learner's calibrated mode is on (oprl_learner_set_calql) and these rows carry no returns-to-go; "
+            "oprl_learner_update_calql takes them, oprl_learner_step_n computes them");
+    return OPRL_ERR_STATE;
+  }
+  if (!h->calql_on && rows.g != nullptr) {
+    set_err("update: returns-to-go for a learner whose calibrated mode is off (oprl_learner_set_calql)");
+    return OPRL_ERR_STATE;
+  }
   RC(cql_rows_fit(h, "update", B));
   RC(check_device_error(h));      // an expired wait of an earlier launch (asynchronous: whatever has run by now)
   hipStream_t st = (hipStream_t)stream;
@@ -1820,6 +1830,18 @@ extern "C" int oprl_learner_update_phase(oprl_learner* h, int32_t phase, const f
 extern "C" int oprl_learner_update(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
                                    const float* s2, int32_t B, const float* noise0, const float* noise1, void* stream) {
   StepRows rows = plain_rows(s, a, r, d, s2);
+  return learner_update(h, rows, B, noise0, noise1, stream);
+}
+
+// The two-call path of the calibrated mode (oprl_learner_set_calql): g[B] are the rows' returns-to-go
+// (oprl_replay_returns), which cql_critic_step hands to the calibrated seed kernel.
+extern "C" int oprl_learner_update_calql(oprl_learner* h, const float* s, const float* a, const float* r, const float* d,
+                                         const float* s2, const float* g, int32_t B, const float* noise0, const float* noise1,
+                                         void* stream) {
+  if (!h) { set_err("oprl_learner_update_calql: null learner handle"); return OPRL_ERR_INVALID; }
+  if (!g) { set_err("oprl_learner_update_calql: null returns-to-go pointer"); return OPRL_ERR_INVALID; }
+  StepRows rows = plain_rows(s, a, r, d, s2);
+  rows.g = g;
   return learner_update(h, rows, B, noise0, noise1, stream);
 }
 
@@ -1949,6 +1971,11 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
   int nstep = 1;
   RC(RowStager::check("step_n", h, replay, false, K, B, &nstep));
   RC(cql_rows_fit(h, "step_n", B));
+  if (h->calql_on && replay_her(replay) > 0) {      // (before anything is launched; oprl_replay_returns would say the same after the sample)
+    set_err("step_n: the learner's calibrated mode is on (oprl_learner_set_calql) and the replay relabels goals in hindsight "
+            "(oprl_replay_set_her): its rewards are relabelled per sample, so its slots have no returns-to-go");
+    return OPRL_ERR_STATE;
+  }
   RowStager stg;
   // else (n-step, hindsight or prior-data rows): the sample + update loop at the end
   const bool plain = nstep == 1 && replay_her(replay) == 0 && replay_prior(replay) == 0;
@@ -2000,6 +2027,13 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
     return rc;
   }
   for (int k = 0; k < K; ++k) {
+    if (h->calql_on) {      // the sampler's slots -> their returns-to-go with the learner's gamma -> the calibrated update
+      RC(oprl_replay_sample(replay, B, nullptr, seed, (uint64_t)h->update_count, h->bs, h->ba, h->br,
+                            h->bd, h->bs2, h->calql_ep, h->calql_step, stream));
+      RC(oprl_replay_returns(replay, B, h->calql_ep, h->calql_step, h->cfg.hp.gamma, h->calql_g, stream));
+      RC(oprl_learner_update_calql(h, h->bs, h->ba, h->br, h->bd, h->bs2, h->calql_g, B, nullptr, nullptr, stream));
+      continue;
+    }
     RC(oprl_replay_sample(replay, B, nullptr, seed, (uint64_t)h->update_count, h->bs, h->ba, h->br,
                           h->bd, h->bs2, nullptr, nullptr, stream));
     RC(oprl_learner_update(h, h->bs, h->ba, h->br, h->bd, h->bs2, B, nullptr, nullptr, stream));

@@ -424,6 +424,7 @@ extern "C" int oprl_learner_destroy(oprl_learner* h) {
   if (h->bc_seed) (void)hipFree(h->bc_seed);
   if (h->iql_base) (void)hipFree(h->iql_base);
   if (h->cql_base) (void)hipFree(h->cql_base);
+  if (h->calql_ep) (void)hipFree(h->calql_ep);
   dev_free(h->uc_base);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->act_pin) (void)hipHostFree(h->act_pin);

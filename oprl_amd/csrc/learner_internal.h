@@ -289,6 +289,9 @@ struct StepRows {
   // |TD| goes [B]; null: the plain update.  Generic launch sequence only (critic_phase).
   const float* w = nullptr;
   float* td_abs = nullptr;
+  // calibrated Q-learning (oprl_learner_update_calql): the rows' returns-to-go [B], the lower bound of the
+  // conservative penalty's policy entries; null: the plain penalty.  Read by cql_critic_step alone.
+  const float* g = nullptr;
 };
 inline StepRows plain_rows(const float* s, const float* a, const float* r, const float* d, const float* s2) {
   StepRows rows{};
@@ -380,6 +383,12 @@ struct oprl_learner {
   float *cql_raw_s = nullptr, *cql_raw_s2 = nullptr, *cql_ws = nullptr, *cql_wa = nullptr, *cql_logd = nullptr, *cql_seed = nullptr;
   float* cql_part = nullptr;
   const float *cql_eps = nullptr, *cql_uni = nullptr;
+  // the calibrated form of that mode (oprl_learner_set_calql, Cal-QL): on only while cql_n > 0; one
+  // allocation of its own, made when it is first turned on — step_n's slots (episode | step, int32) and returns-to-go,
+  // [Bmax] each; whether the last update with the CQL mode on was a calibrated one (read_cql's out[7])
+  bool calql_on = false, cql_last_cal = false;
+  int *calql_ep = nullptr, *calql_step = nullptr;
+  float* calql_g = nullptr;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)

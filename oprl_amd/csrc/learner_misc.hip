@@ -459,8 +459,9 @@ extern "C" int oprl_learner_set_cql(oprl_learner* h, double cql_alpha, int32_t n
     set_err("oprl_learner_set_cql: n_actions=%d outside 0..%d (0 turns the mode off; 3 n_actions entries per row)", n_actions, kCqlMaxActions);
     return OPRL_ERR_INVALID;
   }
-  if (n_actions == 0) {            // off: plain SAC again (the rows stay for the next turn-on)
+  if (n_actions == 0) {            // off: plain SAC again (the rows stay for the next turn-on), the calibrated form with it
     h->cql_n = 0;
+    h->calql_on = false;
     return OPRL_OK;
   }
   if (h->cfg.algo != OPRL_SAC) {
@@ -505,6 +506,28 @@ extern "C" int oprl_learner_set_cql(oprl_learner* h, double cql_alpha, int32_t n
   return OPRL_OK;
 }
 
+// The calibrated form of the mode (Cal-QL): the updates then need the rows' returns-to-go.
+extern "C" int oprl_learner_set_calql(oprl_learner* h, int32_t on) {
+  if (!h) { set_err("oprl_learner_set_calql: null learner handle"); return OPRL_ERR_INVALID; }
+  if (!on) { h->calql_on = false; return OPRL_OK; }
+  if (h->cql_n == 0) {
+    set_err("oprl_learner_set_calql: the conservative-Q-learning mode is off (oprl_learner_set_cql first): the calibrated bound is a form of its penalty");
+    return OPRL_ERR_STATE;
+  }
+  if (h->calql_ep == nullptr) {      // step_n's slots and returns-to-go, once: no update allocates
+    const size_t Bm = (size_t)h->Bmax;
+    int* p = nullptr;
+    if (hipMalloc(&p, 3 * Bm * sizeof(int)) != hipSuccess) { set_err("hipMalloc(%zu) failed (calibrated-Q-learning rows)", 3 * Bm * sizeof(int)); return OPRL_ERR_NOMEM; }
+    hipError_t e = hipMemset(p, 0, 3 * Bm * sizeof(int));
+    if (e != hipSuccess) { (void)hipFree(p); HIPC(e); }
+    h->calql_ep = p;
+    h->calql_step = p + Bm;
+    h->calql_g = reinterpret_cast<float*>(p + 2 * Bm);
+  }
+  h->calql_on = true;
+  return OPRL_OK;
+}
+
 extern "C" int oprl_learner_set_cql_noise(oprl_learner* h, const float* eps, const float* uni) {
   if (!h) { set_err("oprl_learner_set_cql_noise: null learner handle"); return OPRL_ERR_INVALID; }
   h->cql_eps = eps;
@@ -524,16 +547,20 @@ extern "C" int oprl_learner_read_cql(oprl_learner* h, float out_host[8], void* s
   for (int k = 0; k < 8; ++k) out_host[k] = 0.f;
   if (n == 0) return OPRL_OK;
   const double N = (double)h->cql_last_n;
+  double bound = 0;                                   // the calibrated form's count of bounded entries, over the critics
   for (int j = 0; j < nc; ++j) {
     double s[3] = {0, 0, 0};                          // the per-slice sums, in slice order
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < n; ++i) {
       for (int k = 0; k < 3; ++k) s[k] += (double)pc[((size_t)j * n + i) * 4 + k];
+      if (h->cql_last_cal) bound += (double)pc[((size_t)j * n + i) * 4 + 3];
+    }
     // per critic: mean (lse - q) | mean q on the uniform actions | mean q on the actions drawn from pi(.|s)
     out_host[j] = (float)(s[0] / (double)B);
     out_host[2 + j] = (float)(s[1] / ((double)B * N));
     out_host[4 + j] = (float)(s[2] / ((double)B * N));
   }
   out_host[6] = (float)(h->cql_alpha * ((double)out_host[0] + (double)out_host[1]));     // the penalty term of the summed critic loss
+  if (h->cql_last_cal) out_host[7] = (float)(bound / ((double)nc * (double)B * 2.0 * N));   // the share of policy entries at the bound
   return OPRL_OK;
 }
 
@@ -556,16 +583,18 @@ extern "C" int oprl_cql_rows(const float* s, const float* a, const float* raw_s,
   return OPRL_OK;
 }
 
-extern "C" int oprl_cql_seed(const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
-                             const float* logd, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
-                             float* seed_out, float* y_out, float* part_out, float* part_cql_out, void* stream) {
-  if (!q || !qn1 || !r || !d || !logd || !seed_out || !part_out || !part_cql_out) { set_err("oprl_cql_seed: null argument"); return OPRL_ERR_INVALID; }
+namespace {
+// k_cql_seed on caller-supplied rows; g null: the plain kernel, else the calibrated one
+int cql_seed_rows(const char* who, const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
+                  const float* logd, const float* g, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
+                  float* seed_out, float* y_out, float* part_out, float* part_cql_out, void* stream) {
+  if (!q || !qn1 || !r || !d || !logd || !seed_out || !part_out || !part_cql_out) { set_err("%s: null argument", who); return OPRL_ERR_INVALID; }
   if (nc < 1 || nc > OPRL_MAX_CRITICS || B < 1 || N < 1 || N > kCqlMaxActions || (int64_t)B * (1 + 3 * N) > (1 << 30)) {
-    set_err("oprl_cql_seed: need critics in 1..%d (%d), B >= 1 (B=%d), n_actions in 1..%d (%d) and B (1 + 3 n_actions) <= 2^30",
-            OPRL_MAX_CRITICS, nc, B, kCqlMaxActions, N);
+    set_err("%s: need critics in 1..%d (%d), B >= 1 (B=%d), n_actions in 1..%d (%d) and B (1 + 3 n_actions) <= 2^30",
+            who, OPRL_MAX_CRITICS, nc, B, kCqlMaxActions, N);
     return OPRL_ERR_INVALID;
   }
-  if (!cql_alpha_ok("oprl_cql_seed", cql_alpha)) return OPRL_ERR_INVALID;
+  if (!cql_alpha_ok(who, cql_alpha)) return OPRL_ERR_INVALID;
   const long Bw = (long)B * (1 + 3 * N);
   CqlSeedArgs t;
   memset((void*)&t, 0, sizeof t);
@@ -578,8 +607,25 @@ extern "C" int oprl_cql_seed(const float* q, const float* qn1, const float* qn2,
   t.seed = seed_out; t.seed_stride = Bw;
   t.partials = part_out; t.part_cql = part_cql_out;
   t.nc = nc; t.B = B; t.N = N; t.n_slices = (B + kR - 1) / kR;
+  t.g = g;
   HIPC(launch_cql_seed(t, (hipStream_t)stream));
   return OPRL_OK;
+}
+}  // namespace
+
+extern "C" int oprl_cql_seed(const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
+                             const float* logd, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
+                             float* seed_out, float* y_out, float* part_out, float* part_cql_out, void* stream) {
+  return cql_seed_rows("oprl_cql_seed", q, qn1, qn2, logp2, r, d, logd, nullptr, alpha, gamma, cql_alpha, nc, B, N, seed_out, y_out,
+                       part_out, part_cql_out, stream);
+}
+
+extern "C" int oprl_cql_seed_cal(const float* q, const float* qn1, const float* qn2, const float* logp2, const float* r, const float* d,
+                                 const float* logd, double alpha, double gamma, double cql_alpha, int32_t nc, int32_t B, int32_t N,
+                                 float* seed_out, float* y_out, float* part_out, float* part_cql_out, const float* g, void* stream) {
+  if (!g) { set_err("oprl_cql_seed_cal: null returns-to-go pointer"); return OPRL_ERR_INVALID; }
+  return cql_seed_rows("oprl_cql_seed_cal", q, qn1, qn2, logp2, r, d, logd, g, alpha, gamma, cql_alpha, nc, B, N, seed_out, y_out,
+                       part_out, part_cql_out, stream);
 }
 
 // ---------------------------------------------------------------- building blocks

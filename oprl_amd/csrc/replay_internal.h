@@ -1,9 +1,11 @@
 // replay_internal.h — the replay handle (struct oprl_replay) and what the replay's translation units share: the writes,
 // the flush and the uniform sampler (replay.hip), the sum tree of prioritized replay (replay_prio.hip), the n-step and
 // hindsight samplers (replay_nstep.hip, replay_her.hip; their kernels' common shape is replay_gather.h), the sampler
-// over two replays (replay_mix.hip) and the many-episodes write (replay_rows.hip).  learner_per.hip reads the handle's sum tree too.
+// over two replays (replay_mix.hip), the returns-to-go of sampled slots (replay_returns.hip) and the many-episodes write
+// (replay_rows.hip).  learner_per.hip reads the handle's sum tree too.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #include <vector>
@@ -60,6 +62,12 @@ constexpr int kRowsMax = 256;       // records of one oprl_replay_write_rows cal
 // device mappings rows_map / ends_map (null: not mapped) instead of waiting for copies to device staging.
 struct PendingEnds { int first, n; bool direct; };
 PendingEnds pending_ends(const oprl_replay* h, int n_rows, const float* rows_map, const int* ends_map);
+
+// B_p: the prior rows of a batch of B over a replay in prior-data mode, rows [0, B_p) of the batch
+inline int prior_rows(int B, double share) {
+  const double x = floor(share * (double)B + 0.5);
+  return x > 0.0 ? (x < (double)B ? (int)x : B) : 0;
+}
 
 // what oprl_replay_set_lens refuses, without touching the handle (`who` names the caller in the message)
 int check_lens(const oprl_replay* h, const int32_t* ep_lens_host, int32_t episodes_counter, const char* who);

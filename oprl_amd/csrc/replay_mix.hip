@@ -79,12 +79,6 @@ const char* not_plain(const oprl_replay* r) {
   return nullptr;
 }
 
-// B_p: the prior rows of a batch of B
-int prior_rows(int B, double share) {
-  const double x = floor(share * (double)B + 0.5);
-  return x > 0.0 ? (x < (double)B ? (int)x : B) : 0;
-}
-
 }  // namespace
 
 namespace oprl {
