@@ -3,7 +3,7 @@ categorical critic (Bellemare et al., ICML 2017) whose ``n_atoms`` outputs are l
 ``z_i = v_min + i (v_max - v_min) / (n_atoms - 1)``.  Multi-step targets come from an n-step replay buffer
 (buffers/nstep_buffer.py), many actors from ``--num-envs`` or configs/distrib_ddpg.py's layout.
 
-One update on a minibatch (s, a, r, d, s'), csrc/learner.hip + csrc/c51_seed.hip:
+One update on a minibatch (s, a, r, d, s'), csrc/learner_generic.hip + csrc/learner_modes.hip + csrc/c51_seed.hip:
   1. a' = pi_target(s'), p' = softmax(Z_target(s', a'));
   2. Tz_i = clamp(r + ((1 - d) gamma) z_i, v_min, v_max), projected onto the atoms: the target distribution m;
   3. one Adam step of the critic on (1/B) sum_b -sum_j m_j log softmax(Z(s, a))_j, then Polyak on its target;

@@ -2,7 +2,7 @@
 tanh-Gaussian actor, an ensemble of N scalar critics, a TD target that takes the minimum over M target critics drawn
 afresh for every update, and G critic updates per actor step (the update-to-data ratio).
 
-One update u (the learner's update count before it) on a minibatch (s, a, r, d, s'), csrc/learner.hip:
+One update u (the learner's update count before it) on a minibatch (s, a, r, d, s'), csrc/learner_generic.hip:
   1. I_u = M distinct critics, drawn on the host (oprl_redq_subset: Philox stream 3, counter u, partial Fisher-Yates);
   2. a', log pi' = pi(s'); y = r + gamma (1 - d) (min_{i in I_u} Qbar_i(s', a') - alpha log pi');
   3. one Adam step over the whole critic arena on sum_i mean_b (Q_i(s, a) - y)^2, then Polyak on all N targets;

@@ -3,7 +3,7 @@
 row-wise sort + truncation of the 125 target quantiles, fused quantile-Huber
 forward/backward, learned temperature.
 
-One update is 17 launches (csrc/learner.hip critic_phase / actor_phase, csrc/layerwise.hip): the five critics run
+One update is 17 launches (csrc/learner_generic.hip generic_critic_phase / generic_actor_phase, csrc/layerwise.hip): the five critics run
 layer by layer over the whole chip; the launches that leave CUs idle carry independent work as riding workgroups
 (the online critics' first layers behind the actor's forward on s', the TD-target sort on the target pass's heads,
 the actor step's forward on the critic step's heads, the narrow layers' dW tiles behind the wide dW launch, the

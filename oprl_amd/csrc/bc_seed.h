@@ -1,6 +1,6 @@
 // bc_seed.h — the argument blocks of k_bc_seed / k_bc_mix (bc_seed.hip): the behaviour-cloning mode of a TD3 learner's
 // actor step (TD3+BC, Fujimoto & Gu 2021), between critic 0's forward-only launch on (s, pi) and its backward-only launch
-// from SEED_PTR, and between that backward and the actor's (learner.hip actor_phase).
+// from SEED_PTR, and between that backward and the actor's (learner_modes.hip bc_action_grads).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // c51_seed.h — the argument block of k_c51_critic_seed / k_c51_actor_seed (c51_seed.hip): the loss-gradient seeds of
 // D4PG's categorical critic, between the critic's forward-only launch and its backward-only launch from SEED_PTR
-// (learner.hip c51_critic_step, actor_phase).
+// (learner_modes.hip c51_critic_step, c51_action_grads).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
 // c51_seed.hip — k_c51_critic_seed / k_c51_actor_seed: the loss-gradient seeds of D4PG's categorical critic (Bellemare et
 // al. 2017; Barth-Maron et al. 2018), between the critic's forward-only launch, which leaves the logits [B][ld] in
-// memory, and its backward-only launch from SEED_PTR (learner.hip).
+// memory, and its backward-only launch from SEED_PTR (learner_modes.hip).
 //
 // One wave per minibatch row, lane j = atom j (N <= 48 < 64; the lanes past N hold the neutral element of every
 // reduction).  A workgroup is 16 waves = one slice of kR = 16 rows, the slice of the slice kernels, so the per-slice sums

@@ -1,7 +1,7 @@
 // cql_seed.h — the argument blocks of k_cql_rows / k_cql_seed (cql_seed.hip): the conservative-Q-learning mode of a SAC
 // learner (Kumar et al. 2020, CQL(H) with a fixed penalty weight).  The first builds the WIDE rows of the
 // critic step — the minibatch's (s, a) and 3 N sampled actions per state — the second sits between the critics'
-// forward-only launch on those rows and their backward-only launch from SEED_PTR (learner.hip cql_critic_step).
+// forward-only launch on those rows and their backward-only launch from SEED_PTR (learner_modes.hip cql_critic_step).
 //
 // The wide rows, Bw = B (1 + 3 N) of them:
 //   row b, b < B:                      (s_b, a_b), the data rows: the first (B + 15) / 16 slices are theirs;

@@ -1,5 +1,5 @@
 // host_err.h — how a host translation unit reports a failure and brackets a profiled launch: the declarations of
-// set_err / prof_begin / prof_end (defined in learner.hip) and the HIPC / RC early-return macros.  Included by
+// set_err / prof_begin / prof_end (defined in learner.hip), the HIPC / RC early-return macros and profiled().  Included by
 // learner_internal.h and replay_internal.h, so every unit sees one definition of each.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,3 +27,13 @@ using oprl::set_err;
     int _rc = (x);                  \
     if (_rc != OPRL_OK) return _rc; \
   } while (0)
+
+// One launch counted and timed as profile kind `kind`: launch() returns the launcher's hipError_t
+template <class F>
+int profiled(int kind, hipStream_t st, F&& launch) {
+  oprl::prof_begin(kind, st);
+  const hipError_t e = launch();
+  oprl::prof_end(st);
+  HIPC(e);
+  return OPRL_OK;
+}

@@ -1,7 +1,7 @@
 // iql_seed.h — the argument blocks of k_iql_value_seed / k_iql_actor_seed (iql_seed.hip): the implicit-Q-learning mode of a
 // TD3 learner (Kostrikov et al. 2021).  The first sits between the value net's forward-only launch on s and
-// its backward-only launch from SEED_PTR, the second between the actor's forward and its backward (learner.hip
-// iql_value_step / actor_phase).
+// its backward-only launch from SEED_PTR, the second between the actor's forward and its backward (learner_modes.hip
+// iql_critic_phase / iql_action_grads).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,17 +1,14 @@
 // learner.hip — host orchestration of update() for DDPG / TD3 / SAC / TQC and the
 // C-ABI of include/oprl_amd.h.  Each update() is a short fixed sequence of
 // k_mlp_slice / k_dw_adam launches on the caller's stream; no host sync inside.
+// Here: the fused launch forms, the dW + Adam launch, the update's entry points and step_n; critic_phase / actor_phase
+// dispatch to the fused branches or to the generic per-net sequence (learner_generic.hip; the modes: learner_modes.hip).
 //
 // Order of operations follows the reference exactly (it matters: the actor
 // loss sees the post-Adam critic, Polyak sees both updated nets):
 //   DDPG  algos/ddpg.py:61-107      TD3  algos/td3.py:71-146
 //   SAC   algos/sac.py:75-155       TQC  algos/tqc.py:116-189
 #include "learner_internal.h"
-#include "per_seed.h"
-#include "c51_seed.h"
-#include "bc_seed.h"
-#include "iql_seed.h"
-#include "cql_seed.h"
 #include "philox.h"
 
 namespace oprl {
@@ -293,48 +290,8 @@ bool tp_generic(const oprl_learner* h, const oprl_net& n, int B) {
   if (n.n_layers != 3 || n.dims[1] != 256 || n.dims[2] != 256) return false;
   if (n.dims[0] > 96 || n.dims[3] > kNarrowMax) return false;
   if (((h->S & 15) + h->A - 1) / 16 >= 4) return false;          // input-gradient column span
-  const int slices = (B + kR - 1) / kR;
+  const int slices = n_slices(B);
   return slices * 4 <= h->n_cus;
-}
-
-MlpArgs base_args(oprl_learner* h, const oprl_net& n, bool target, int B) {
-  MlpArgs a;
-  memset(&a, 0, sizeof a);
-  if (tp_generic(h, n, B)) {
-    a.tp_xbuf = h->xbuf;
-    a.tp_tag_counter = &h->tp_tag;
-    a.tp_xbuf_bytes = h->xbuf_granules * sizeof(unsigned long long);
-  }
-  if (h->trace != nullptr && h->trace_slot < OPRL_TRACE_SLOTS)
-    a.trace = h->trace + (size_t)(h->trace_slot++) * 64 * kTraceStamps * 2;
-  a.net = net_view(eff(h, n), target);
-  a.err = h->err_dev;
-  if (h->bf16 || h->x2) {     // (the 16-bit packs of the net's layers: bf16, or two fp16 planes per block)
-    int idx = -1;                                      // 0 = actor, 1 + j = critic j
-    if (&n == &h->cfg.actor) idx = 0;
-    for (int j = 0; j < h->nc; ++j) if (&n == &h->cfg.critics[j]) idx = 1 + j;
-    const float* pk16 = idx < 0 ? nullptr : (target ? h->pack16_t[idx] : h->pack16[idx]);
-    for (int l = 0; pk16 != nullptr && l < n.n_layers; ++l) {
-      a.pf16[l] = pk16 + pack16_off_fwd(n, l, h->planes);
-      a.pb16[l] = target ? nullptr : pk16 + pack16_off_bwd(n, l, h->planes);
-    }
-  }
-  a.B = B;
-  a.action_dim = h->A;
-  a.policy_noise = (float)h->cfg.hp.policy_noise;
-  a.noise_clip = (float)h->cfg.hp.noise_clip;
-  a.max_action = (float)h->cfg.hp.max_action;
-  return a;
-}
-
-void with_store(MlpArgs& a, const NetWs& ws, bool x, bool dy) {
-  for (int l = 0; l < kMaxLayers; ++l) {
-    a.Xg[l] = x ? ws.X[l] : nullptr;
-    a.dYg[l] = dy ? ws.dY[l] : nullptr;
-  }
-  a.ldx0 = ws.ldx0;
-  a.lddo = ws.lddo;
-  a.dY0_stride = ws.dY0_stride;
 }
 
 hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st) {
@@ -343,16 +300,6 @@ hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st) {
   hipError_t e = launch_dw_adam(a, st);
   prof_end(st);
   return e;
-}
-
-// One round of the generic launch sequence: make_j(j) builds the arguments of net j in [0, n), and launch_round
-// (net_rounds.hip) decides from the list how they go out.
-template <class F>
-int for_each_net(oprl_learner* h, int n, int width, hipStream_t st, F&& make_j) {
-  MlpArgs a[OPRL_MAX_CRITICS];
-  if (n > OPRL_MAX_CRITICS) { set_err("internal: a round of %d nets", n); return OPRL_ERR_STATE; }
-  for (int j = 0; j < n; ++j) a[j] = make_j(j);
-  return launch_round(h, a, n, width, st);
 }
 
 const double* alpha_ptr(const oprl_learner* h) {
@@ -377,7 +324,6 @@ unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id) {
   }
   return 0x0b5e55edULL + stream_id + x;
 }
-unsigned long long noise_key(const oprl_learner* h, uint64_t stream_id) { return noise_key(h->noise_seed, h->noise_rank, stream_id); }
 
 // REDQ's target subset (include/oprl_amd.h oprl_redq_subset): a partial Fisher-Yates shuffle of 0 .. n-1 driven by the
 // words of Philox blocks (stream 3, counter `counter`, block index in the third counter word)
@@ -397,12 +343,6 @@ void redq_subset(uint64_t seed, int rank, uint64_t counter, int n, int m, int* o
   }
 }
 
-void seed_rng(MlpArgs& a, const oprl_learner* h, const float* noise, uint64_t stream_id) {
-  a.noise = noise;
-  a.rng_seed = noise_key(h, stream_id);
-  a.rng_ctr = (unsigned long long)h->update_count;
-}
-
 // ------------------------------------------------------------ fused DDPG / TD3
 bool actor_due(const oprl_learner* h);
 
@@ -411,7 +351,7 @@ int chain_rows(const oprl_learner* h, int B) {
   int tiles64[2] = {0, 0};
   for (size_t i = 0; i < h->items_host.size(); ++i)
     tiles64[(int)i < h->n_items_critic ? 0 : 1] += ((h->items_host[i].N + 15) / 16) * ((h->items_host[i].K + 63) / 64);
-  const int sl = (B + kR - 1) / kR, mt = tiles64[0] > tiles64[1] ? tiles64[0] : tiles64[1];
+  const int sl = n_slices(B), mt = tiles64[0] > tiles64[1] ? tiles64[0] : tiles64[1];
   return 16 + chain_tile_rows(mt, sl);
 }
 
@@ -420,7 +360,7 @@ int chain_rows(const oprl_learner* h, int B) {
 FusedForm fused_form(const oprl_learner* h, int B, bool dp_inline) {
   const oprl_learner_config& c = h->cfg;
   const Switches& sw = h->sw;
-  const int slices = (B + kR - 1) / kR;
+  const int slices = n_slices(B);
   const bool sac = c.algo == OPRL_SAC;
   FusedForm f;
   f.nc = h->nc_cluster(B);
@@ -710,7 +650,7 @@ DwXchg xchg_args(const oprl_learner* h, unsigned long long seq) {
 }
 
 // one dW + Adam launch of its own (the actor's carries the temperature step where it rides)
-int dw_step(oprl_learner* h, bool critic, int B, hipStream_t st, const PrefetchJob* prefetch = nullptr) {
+int dw_step(oprl_learner* h, bool critic, int B, hipStream_t st, const PrefetchJob* prefetch) {
   DwArgs dw = dw_args(h, critic, B, (critic ? h->opt_step_critic : h->opt_step_actor) + 1);
   if (!critic && alpha_rides(h)) dw.alpha = alpha_job(h, B, h->opt_step_alpha + 1);
   dw.prefetch = prefetch;
@@ -741,29 +681,11 @@ int dw_step(oprl_learner* h, bool critic, int B, hipStream_t st, const PrefetchJ
   return OPRL_OK;
 }
 
-// the actor's forward on s with the activations kept for its backward (actor_phase step 5)
-MlpArgs actor_forward_args(oprl_learner* h, const float* s, int B, const float* noise1) {
-  const oprl_learner_config& c = h->cfg;
-  const bool gauss = gauss_actor(h);
-  MlpArgs f = base_args(h, c.actor, false, B);
-  f.do_fwd = 1;
-  f.x0 = s; f.k0 = h->S;
-  with_store(f, h->ws_actor, true, false);
-  f.out = h->pi; f.ldo = h->A;
-  if (gauss) {
-    f.out_act = ACT_GAUSS; f.raw_out = h->raw; f.ldraw = 2 * h->A; f.logp = h->logp;
-    seed_rng(f, h, noise1, 2);
-  } else {
-    f.out_act = ACT_TANH;
-  }
-  return f;
-}
-
 // ------------------------------------------------------------ critic phase
 // The gates of the dW tiles that ride on a phase launch (DwGate): the common fields of the critic's tiles (phase 1's
 // roles flag their rows, the TD-error seeds come as granules, one per row) ...
 void critic_gate(const oprl_learner* h, const DdpgArgs& fa, int B, DwGate& g) {
-  const int slices = (B + kR - 1) / kR;
+  const int slices = n_slices(B);
   g.rows = fa.gate_flags; g.n_rows = 4 * slices * h->nc;
   g.seed = fa.y_granules; g.n_seed = B;
   g.late_dY = h->ws_critic[0].dY[h->cfg.critics[0].n_layers - 1];
@@ -787,7 +709,7 @@ void actor_gate(const oprl_learner* h, const DdpgArgs& fa, int B, DwGate& g) {
 // the exchange tags and, data parallel, this rank's tile sequence — is committed once it is out: after an error return
 // Adam's bias corrections and the peers' sequence numbers are where they were.
 int whole_update(oprl_learner* h, StepRows& rows, DdpgArgs& fa, const FusedForm& form, int B, hipStream_t st) {
-  const int slices = (B + kR - 1) / kR;
+  const int slices = n_slices(B);
   const int U = rows.n_upd < form.chain_max ? rows.n_upd : form.chain_max;
   const int step_c = h->opt_step_critic + 1, step_a = h->opt_step_actor + 1;     // update 0's
   fa.prefetch_next = 0;
@@ -892,709 +814,110 @@ int whole_update(oprl_learner* h, StepRows& rows, DdpgArgs& fa, const FusedForm&
   return OPRL_OK;
 }
 
-// online critic j on (s, a), activations and dY stored for its dW launch: the critic step's forward, with the backward or not
-MlpArgs critic_sa_args(oprl_learner* h, int j, const float* s, const float* a, int B, bool bwd) {
-  MlpArgs f = base_args(h, h->cfg.critics[j], false, B);
-  f.do_fwd = 1; f.do_bwd = bwd ? 1 : 0;
-  f.x0 = s; f.k0 = h->S; f.x1 = a; f.k1 = h->A;
-  with_store(f, h->ws_critic[j], true, true);
-  return f;
-}
-
-// SEED_MSE_TD's operands, all but the debug rows y_out / q_out.  n_min: REDQ's target critics (else unused)
-SeedArgs mse_td_seed(const oprl_learner* h, const float* r, const float* d, int B, int n_min) {
+// phase 1 of a fused update — or the whole update, or phase 1 with the critic's dW tiles — and the critic's dW + Adam
+static int fused_critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
-  const bool redq = c.algo == OPRL_REDQ;
-  SeedArgs sd;
-  memset((void*)&sd, 0, sizeof sd);
-  sd.p0 = h->qn;
-  sd.p1 = h->nc > 1 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
-  if (redq) {      // the minimum over the subset's slots: one or two rows here, else k_redq_min's row
-    sd.p0 = n_min > 2 ? h->target : h->qn;
-    sd.p1 = n_min == 2 ? h->qn + (size_t)h->Bmax * h->ldq : nullptr;
+  h->epoch += 1;
+  if (h->epoch == 0 || h->epoch > 0xFFFFFFFFu - (unsigned)kChainMax) {   // the TD-target tag wrapped (or would inside a chain launch): retire every stale granule
+    h->epoch = 1;
+    HIPC(hipMemsetAsync(h->y_granules, 0, ((size_t)4 * h->Bmax + 256) * sizeof(unsigned long long), st));
+    if (h->du_granules != nullptr) {
+      HIPC(hipMemsetAsync(h->du_granules, 0, (size_t)(h->Bmax < 256 ? h->Bmax : 256) * kDuLd * sizeof(unsigned long long), st));
+      HIPC(hipMemsetAsync(h->g1_granules, 0, (size_t)16 * (h->Bmax < 256 ? h->Bmax : 256) * 16 * sizeof(unsigned long long), st));
+      HIPC(hipMemsetAsync(h->w_flags, 0, 256 * sizeof(unsigned long long), st));
+      HIPC(hipMemsetAsync(h->chain_flags, 0, (192 + 192 + 64 + 128 + 1024) * sizeof(unsigned long long), st));
+    }
   }
-  sd.p2 = (c.algo == OPRL_SAC || redq) ? h->logp2 : nullptr;
-  sd.log_alpha = alpha_ptr(h); sd.alpha_const = (float)c.hp.alpha_init;
-  sd.r = r; sd.d = d; sd.gamma = (float)c.hp.gamma;
-  sd.cval = 1.0f / (float)B;
-  return sd;
-}
-
-// Step 3 of the generic critic phase under importance weights (rows.w; oprl_learner_update_weighted): the
-// launch that is forward + seed + backward there, as three — the critics' forward with the activations stored and q into
-// qpi (idle until the actor phase), k_td_weighted_seed (per_seed.hip) on those q and the target operands SEED_MSE_TD takes,
-// the critics' backward from the stored activations with the seed read from memory (SEED_PTR).  The same rounds
-// (for_each_net) and the same stores, so step 4's dW + Adam reads what it always reads.
-int weighted_critic_step(oprl_learner* h, const StepRows& rows, int B, int n_min, hipStream_t st) {
-  const oprl_learner_config& c = h->cfg;
-  const int nc = h->nc;
-  if (h->per_seed == nullptr || rows.td_abs == nullptr) { set_err("internal: weighted critic step without its buffers"); return OPRL_ERR_STATE; }
-  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = critic_sa_args(h, j, rows.cur.s, rows.cur.a, B, false);
-    f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
-    return f;
-  }));
-  TdSeedArgs t;
-  memset((void*)&t, 0, sizeof t);
-  t.s = mse_td_seed(h, rows.cur.r, rows.cur.d, B, n_min);
-  t.s.y_out = h->ydbg; t.s.q_out = h->qdbg;
-  t.q = h->qpi; t.q_stride = h->Bmax;
-  t.w = rows.w;
-  t.seed = h->per_seed; t.seed_stride = h->Bmax;
-  t.td_abs = rows.td_abs;
-  t.partials = h->part_c;
-  t.nc = nc; t.B = B; t.n_slices = (B + kR - 1) / kR;
-  prof_begin(0, st);
-  hipError_t e = launch_td_weighted_seed(t, st);
-  prof_end(st);
-  HIPC(e);
-  return for_each_net(h, nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = base_args(h, c.critics[j], false, B);
-    f.do_bwd = 1;
-    with_store(f, h->ws_critic[j], true, true);
-    f.seed_mode = SEED_PTR;
-    f.seed.p0 = h->per_seed + (size_t)j * h->Bmax; f.seed.ld0 = 1;
-    return f;
-  });
-}
-
-// D4PG's seed operands: the atoms, the row count and the logits / seed rows of this learner (c51_seed.h)
-C51Args c51_args(const oprl_learner* h, int B) {
-  const oprl_net& q = h->cfg.critics[0];
-  C51Args a;
-  memset((void*)&a, 0, sizeof a);
-  a.z = h->c51_logits;
-  a.seed = h->c51_seed;
-  a.gamma = (float)h->cfg.hp.gamma; a.v_min = (float)h->cfg.hp.v_min; a.v_max = (float)h->cfg.hp.v_max;
-  a.inv_B = 1.0f / (float)B;
-  a.N = q.dims[q.n_layers]; a.B = B; a.ld = h->ldq;
-  a.n_slices = (B + kR - 1) / kR;
-  return a;
-}
-
-// the critic's backward-only launch from the seed rows k_c51_*_seed left (SEED_PTR, ld0 = ldq)
-MlpArgs c51_backward_args(oprl_learner* h, int B, bool store_dy) {
-  MlpArgs f = base_args(h, h->cfg.critics[0], false, B);
-  f.do_bwd = 1;
-  with_store(f, h->ws_critic[0], true, store_dy);
-  f.seed_mode = SEED_PTR;
-  f.seed.p0 = h->c51_seed; f.seed.ld0 = h->ldq;
-  return f;
-}
-
-// Step 3 of the generic critic phase for D4PG's categorical critic, in weighted_critic_step's form: the
-// critic's forward with the activations stored and its logits into c51_logits, k_c51_critic_seed (c51_seed.hip) on those
-// logits and the target critic's (qn), the critic's backward from the stored activations with the seed rows read from
-// memory.  Step 4's dW + Adam reads what it always reads.
-int c51_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st) {
-  if (h->c51_logits == nullptr || h->c51_seed == nullptr) { set_err("internal: categorical critic step without its buffers"); return OPRL_ERR_STATE; }
-  RC(for_each_net(h, 1, h->w_critic, st, [&](int j) {
-    MlpArgs f = critic_sa_args(h, j, rows.cur.s, rows.cur.a, B, false);
-    f.out = h->c51_logits; f.ldo = h->ldq;
-    return f;
-  }));
-  C51Args t = c51_args(h, B);
-  t.zt = h->qn;
-  t.r = rows.cur.r; t.d = rows.cur.d;
-  t.q_out = h->qdbg; t.y_out = h->ydbg;
-  t.partials = h->part_c;
-  prof_begin(3, st);
-  hipError_t e = launch_c51_critic_seed(t, st);
-  prof_end(st);
-  HIPC(e);
-  return for_each_net(h, 1, h->w_critic, st, [&](int) { return c51_backward_args(h, B, true); });
-}
-
-// Step 3 of the generic critic phase of a SAC learner with the conservative-Q-learning mode on (oprl_learner_set_cql;
-// DESIGN.md §19), in weighted_critic_step's form at a wider row count: Bw = B (1 + 3 N) rows, the minibatch's (s, a) first and
-// then N uniform actions, N from pi(.|s_b) and N from pi(.|s'_b) per state, all at s_b (cql_seed.h has the layout).  The
-// actor's raw head row on s' is step 1's (raw_out); the one on s is a forward-only launch here: the actor does not run N times.
-// Then k_cql_rows | the critics' forward on the wide rows with the activations stored, q into qpi | k_cql_seed | the critics'
-// backward from SEED_PTR: 5 launches where SAC has 1, and step 4's dW + Adam + Polyak reads what it always reads, Bw rows of it.
-int cql_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st) {
-  const oprl_learner_config& c = h->cfg;
-  const int S = h->S, A = h->A, nc = h->nc, N = h->cql_n;
-  const int Bw = B * (1 + 3 * N);
-  if (c.algo != OPRL_SAC || h->cql_base == nullptr || Bw > h->Bmax) { set_err("internal: conservative-Q-learning critic step without its buffers"); return OPRL_ERR_STATE; }
-  {
-    MlpArgs f = base_args(h, c.actor, false, B);
-    f.do_fwd = 1;
-    f.x0 = rows.cur.s; f.k0 = S;
-    f.out = h->cql_raw_s; f.ldo = 2 * A;
-    f.out_act = ACT_NONE;
-    RC(launch(f, h->w_actor, st));
+  const FusedForm form = fused_form(h, B, h->dp_inline);
+  DdpgArgs fa = ddpg_args(h, rows, B);
+  if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));     // (a batch the lean kernels do not take: fp32 packs)
+  fa.noise = noise0;
+  if (rows.stage == StepRows::kPhase1) {
+    // (step_n asks phase 1 to stage only for a form with merged bits, which the rt2 form never has)
+    if (fa.rt2 != 0) { set_err("internal: phase 1 asked to stage the next rows in the rt2 form"); return OPRL_ERR_STATE; }
+    fa.prefetch_p1 = 1;
+    rows.staged = true;
   }
-  CqlRowsArgs g;
-  memset((void*)&g, 0, sizeof g);
-  g.s = rows.cur.s; g.a = rows.cur.a;
-  g.raw_s = h->cql_raw_s; g.raw_s2 = h->cql_raw_s2;
-  g.eps = h->cql_eps; g.uni = h->cql_uni;
-  g.key_eps = noise_key(h, 4); g.key_uni = noise_key(h, 5);       // (streams 1 .. 3: seed_rng's two and REDQ's subset)
-  g.ctr = (unsigned long long)h->update_count;
-  g.B = B; g.S = S; g.A = A; g.N = N;
-  g.ws = h->cql_ws; g.wa = h->cql_wa; g.logd = h->cql_logd;
-  prof_begin(3, st);
-  hipError_t e = launch_cql_rows(g, st);
-  prof_end(st);
-  HIPC(e);
-  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = critic_sa_args(h, j, h->cql_ws, h->cql_wa, Bw, false);
-    f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
-    return f;
-  }));
-  CqlSeedArgs t;
-  memset((void*)&t, 0, sizeof t);
-  t.s = mse_td_seed(h, rows.cur.r, rows.cur.d, B, 0);
-  t.s.y_out = h->ydbg; t.s.q_out = h->qdbg;
-  t.q = h->qpi; t.q_stride = h->Bmax;
-  t.logd = h->cql_logd;
-  t.ca = (float)h->cql_alpha;
-  t.seed = h->cql_seed; t.seed_stride = h->Bmax;
-  t.partials = h->part_c; t.part_cql = h->cql_part;
-  t.nc = nc; t.B = B; t.N = N; t.n_slices = (B + kR - 1) / kR;
-  t.g = rows.g;                    // the calibrated seed when the rows carry returns-to-go
-  prof_begin(3, st);
-  e = launch_cql_seed(t, st);
-  prof_end(st);
-  HIPC(e);
-  h->cql_B = B; h->cql_last_n = N; h->cql_last_cal = rows.g != nullptr;
-  return for_each_net(h, nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = base_args(h, c.critics[j], false, Bw);
-    f.do_bwd = 1;
-    with_store(f, h->ws_critic[j], true, true);
-    f.seed_mode = SEED_PTR;
-    f.seed.p0 = h->cql_seed + (size_t)j * h->Bmax; f.seed.ld0 = 1;
-    return f;
-  });
-}
-
-// The critic phase of a TD3 learner with the implicit-Q-learning mode on (oprl_learner_set_iql).  No action
-// outside the batch is evaluated: V on s' where TD3 runs the target actor and the target critics on (s', a'), the target
-// critics on the batch's own (s, a), V's expectile step as forward | k_iql_value_seed | backward from SEED_PTR with a dW +
-// Adam launch of its own (its item table, its learning rate, its step count; no target, no Polyak), then TD3's critic
-// launch with the one target row V(s') — taken BEFORE V's step — and the critics' unchanged dW + Adam + Polyak: 8 launches.
-int iql_critic_phase(oprl_learner* h, const StepRows& rows, int B, hipStream_t st) {
-  const oprl_learner_config& c = h->cfg;
-  const float *s = rows.cur.s, *a = rows.cur.a, *r = rows.cur.r, *d = rows.cur.d, *s2 = rows.cur.s2;
-  const int S = h->S, A = h->A, nc = h->nc;
-  const int n_slices = (B + kR - 1) / kR;
-  const oprl_net& V = h->iql_value;
-  if (c.algo != OPRL_TD3 || nc != 2 || h->iql_base == nullptr) { set_err("internal: implicit-Q-learning critic step without its buffers"); return OPRL_ERR_STATE; }
-  const int wv = V.dims[1];
-  // 1. V(s'), from V as it is before this update's step
-  {
-    MlpArgs f = base_args(h, V, false, B);
-    f.do_fwd = 1;
-    f.x0 = s2; f.k0 = S;
-    f.out = h->iql_vn; f.ldo = 1;
-    RC(launch(f, wv, st));
+  if (h->trace != nullptr) fa.trace = h->trace;   // roles use slots 0 .. 1 + n_critics
+  h->whole_done = false;
+  if (form.whole) return whole_update(h, rows, fa, form, B, st);
+  RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
+  if ((fa.merged & 1) != 0) {
+    // phase 1 and the critic's dW + Adam tiles as ONE launch: the tiles wait for the roles' flag granules
+    const DwArgs dw = dw_args(h, true, B, h->opt_step_critic + 1);
+    DwKArgs kd;
+    if (fill_dw_kargs(dw, &kd, ((fa.x2 && fused_x2_tiles()) || (h->nc == 2 && fused_tile64_all())) ? 64 : 32) < 0) { set_err("merged phase 1: bad dW table"); return OPRL_ERR_INVALID; }
+    critic_gate(h, fa, B, kd.gate);
+    if (h->nc == 2) {      // (twin critics: the second one's items, seeds and output-layer dY)
+      kd.gate.item_split = c.critics[0].n_layers;
+      kd.gate.seed2 = fa.seed2_granules;
+      kd.gate.late_dY2 = h->ws_critic[1].dY[c.critics[1].n_layers - 1];
+    }
+    RC(profiled(4, st, [&] { return launch_ddpg_phase1_dw(fa, kd, st); }));
+    dw_commit(h, true, dw, 1);
+    return OPRL_OK;
   }
-  // 2. the target critics on (s, a)
-  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = base_args(h, c.critics[j], true, B);
-    f.do_fwd = 1;
-    f.x0 = s; f.k0 = S; f.x1 = a; f.k1 = A;
-    f.out = h->qn + (size_t)j * h->Bmax * h->ldq; f.ldo = h->ldq;
-    return f;
-  }));
-  // 3. V's step: forward on s with the activations stored | the seed rows, u and w | backward from the seed rows
-  {
-    MlpArgs f = base_args(h, V, false, B);
-    f.do_fwd = 1;
-    f.x0 = s; f.k0 = S;
-    with_store(f, h->ws_value, true, true);
-    f.out = h->iql_vs; f.ldo = 1;
-    RC(launch(f, wv, st));
-  }
-  IqlValueArgs t;
-  memset((void*)&t, 0, sizeof t);
-  t.q1 = h->qn; t.q2 = h->qn + (size_t)h->Bmax * h->ldq; t.v = h->iql_vs;
-  t.tau = (float)h->iql_tau; t.omtau = (float)(1.0 - h->iql_tau);
-  t.beta = (float)h->iql_beta; t.clip = (float)h->iql_clip;
-  t.inv_B = 1.0f / (float)B;
-  t.B = B; t.n_slices = n_slices;
-  t.u = h->iql_u; t.seed = h->iql_seed; t.w = h->iql_w;
-  t.part_v = h->iql_part_v; t.part_w = h->iql_part_w;
-  prof_begin(3, st);
-  hipError_t e = launch_iql_value_seed(t, st);
-  prof_end(st);
-  HIPC(e);
-  h->iql_B = B;
-  {
-    MlpArgs f = base_args(h, V, false, B);
-    f.do_bwd = 1;
-    with_store(f, h->ws_value, true, true);
-    f.seed_mode = SEED_PTR;
-    f.seed.p0 = h->iql_seed; f.seed.ld0 = 1;
-    RC(launch(f, wv, st));
-  }
-  // 4. V's dW + Adam, committed to V's counter only
-  {
-    DwArgs dw;
-    dw.items = h->iql_items.data();
-    dw.n_items = (int)h->iql_items.size();
-    dw.total_tiles = h->iql_tiles;
-    dw.ad = adam_scalars(h, h->iql_lr, h->opt_step_value + 1, false, 1.0f);
-    dw.B = B;
-    dw.n_part = tp_generic(h, V, B) ? 4 : 1;
-    dw.dy_tiled = dw.n_part > 1 ? 1 : 0;
-    HIPC(launch_dw_prof(h, dw, st));
-    h->opt_step_value += 1;
-  }
-  // 5. the online critics: TD3's launch, y = r + ((1 - d) gamma) V(s'); 6. their dW + Adam + Polyak
-  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = critic_sa_args(h, j, s, a, B, true);
-    f.partials = h->part_c + (size_t)j * n_slices * 4;
-    f.seed_mode = SEED_MSE_TD;
-    f.seed = mse_td_seed(h, r, d, B, 0);
-    f.seed.p0 = h->iql_vn; f.seed.p1 = nullptr; f.seed.p2 = nullptr;
-    if (j == 0) { f.seed.y_out = h->ydbg; f.seed.q_out = h->qdbg; }
-    return f;
-  }));
+  RC(profiled(4, st, [&] { return launch_ddpg_phase1(fa, st); }));
   return dw_step(h, true, B, st);
 }
 
+// The two phases of an update: the fused launches where the learner has them at this batch (use_fused), else the generic
+// launch sequence (learner_generic.hip)
 int critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hipStream_t st) {
-  const oprl_learner_config& c = h->cfg;
-  const float *s = rows.cur.s, *a = rows.cur.a, *r = rows.cur.r, *d = rows.cur.d, *s2 = rows.cur.s2;
-  if (rows.w != nullptr && (use_fused(h, B) || c.algo == OPRL_TQC || c.algo == OPRL_D4PG)) {      // (the entry point refuses all three)
+  if (rows.w != nullptr && (use_fused(h, B) || h->cfg.algo == OPRL_TQC || h->cfg.algo == OPRL_D4PG)) {      // (the entry point refuses all three)
     set_err("internal: importance weights reached a launch form that does not apply them");
     return OPRL_ERR_STATE;
   }
-  if (use_fused(h, B)) {
-    h->epoch += 1;
-    if (h->epoch == 0 || h->epoch > 0xFFFFFFFFu - (unsigned)kChainMax) {   // the TD-target tag wrapped (or would inside a chain launch): retire every stale granule
-      h->epoch = 1;
-      HIPC(hipMemsetAsync(h->y_granules, 0, ((size_t)4 * h->Bmax + 256) * sizeof(unsigned long long), st));
-      if (h->du_granules != nullptr) {
-        HIPC(hipMemsetAsync(h->du_granules, 0, (size_t)(h->Bmax < 256 ? h->Bmax : 256) * kDuLd * sizeof(unsigned long long), st));
-        HIPC(hipMemsetAsync(h->g1_granules, 0, (size_t)16 * (h->Bmax < 256 ? h->Bmax : 256) * 16 * sizeof(unsigned long long), st));
-        HIPC(hipMemsetAsync(h->w_flags, 0, 256 * sizeof(unsigned long long), st));
-        HIPC(hipMemsetAsync(h->chain_flags, 0, (192 + 192 + 64 + 128 + 1024) * sizeof(unsigned long long), st));
-      }
-    }
-    const FusedForm form = fused_form(h, B, h->dp_inline);
-    DdpgArgs fa = ddpg_args(h, rows, B);
-    if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));     // (a batch the lean kernels do not take: fp32 packs)
-    fa.noise = noise0;
-    if (rows.stage == StepRows::kPhase1) {
-      // (step_n asks phase 1 to stage only for a form with merged bits, which the rt2 form never has)
-      if (fa.rt2 != 0) { set_err("internal: phase 1 asked to stage the next rows in the rt2 form"); return OPRL_ERR_STATE; }
-      fa.prefetch_p1 = 1;
-      rows.staged = true;
-    }
-    if (h->trace != nullptr) fa.trace = h->trace;   // roles use slots 0 .. 1 + n_critics
-    h->whole_done = false;
-    if (form.whole) return whole_update(h, rows, fa, form, B, st);
-    RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
-    if ((fa.merged & 1) != 0) {
-      // phase 1 and the critic's dW + Adam tiles as ONE launch: the tiles wait for the roles' flag granules
-      const DwArgs dw = dw_args(h, true, B, h->opt_step_critic + 1);
-      DwKArgs kd;
-      if (fill_dw_kargs(dw, &kd, ((fa.x2 && fused_x2_tiles()) || (h->nc == 2 && fused_tile64_all())) ? 64 : 32) < 0) { set_err("merged phase 1: bad dW table"); return OPRL_ERR_INVALID; }
-      critic_gate(h, fa, B, kd.gate);
-      if (h->nc == 2) {      // (twin critics: the second one's items, seeds and output-layer dY)
-        kd.gate.item_split = c.critics[0].n_layers;
-        kd.gate.seed2 = fa.seed2_granules;
-        kd.gate.late_dY2 = h->ws_critic[1].dY[c.critics[1].n_layers - 1];
-      }
-      prof_begin(4, st);
-      hipError_t e = launch_ddpg_phase1_dw(fa, kd, st);
-      prof_end(st);
-      HIPC(e);
-      dw_commit(h, true, dw, 1);
-      return OPRL_OK;
-    }
-    prof_begin(4, st);
-    hipError_t e = launch_ddpg_phase1(fa, st);
-    prof_end(st);
-    HIPC(e);
-    return dw_step(h, true, B, st);
-  }
-  RC(fresh32_tables(h, 3, st));      // (a PrecX2 learner's generic launches read the fp32 packs)
-  const int S = h->S, A = h->A, nc = h->nc;
-  const int algo = c.algo;
-  const int n_slices = (B + kR - 1) / kR;
-  if (h->iql_on) {                 // the implicit-Q-learning mode: its own sequence (the entry points refuse weights)
-    if (rows.w != nullptr) { set_err("internal: importance weights reached the implicit-Q-learning critic step"); return OPRL_ERR_STATE; }
-    return iql_critic_phase(h, rows, B, st);
-  }
-  // 1. next action
-  {
-    const bool use_target_actor = (algo == OPRL_DDPG || algo == OPRL_TD3 || algo == OPRL_D4PG);
-    MlpArgs f = base_args(h, c.actor, use_target_actor, B);
-    f.do_fwd = 1;
-    f.x0 = s2; f.k0 = S;
-    f.out = h->a2; f.ldo = A;
-    if (algo == OPRL_DDPG || algo == OPRL_D4PG) f.out_act = ACT_TANH;
-    else if (algo == OPRL_TD3) { f.out_act = ACT_TANH_SMOOTH; seed_rng(f, h, noise0, 1); }
-    else { f.out_act = ACT_GAUSS; f.logp = h->logp2; seed_rng(f, h, noise0, 1); }
-    if (h->cql_n > 0) { f.raw_out = h->cql_raw_s2; f.ldraw = 2 * A; }      // (the CQL mode samples from this head row too: cql_critic_step)
-    // TQC: this launch is 64 workgroups on 256 CUs, and the online critics' first two layers on (s, a) — the
-    // first launch of step 3 — depend on nothing of it: they ride behind it (k_slice_tp_fin, layerwise.hip)
-    bool fin_ride = false, fin16 = false;
-    MlpArgs* fin_args = h->fin_args;
-    h->fin_done = false;
-    h->fin_l2_done = false;
-    h->fin_tail0 = -1;
-    if (algo == OPRL_TQC && !h->sw.no_fin_ride && !h->sw.no_layerwise && nc > 2 && nc <= kMaxMulti &&
-        h->lw_scratch != nullptr && h->w_critic == 512 && f.tp_xbuf != nullptr) {
-      fin16 = h->bf16 || h->x2;
-      for (int j = 0; j < nc; ++j) {
-        MlpArgs g = critic_sa_args(h, j, s, a, B, true);
-        for (int l = 1; l + 1 < g.net.n_layers; ++l) fin16 = fin16 && g.pf16[l] != nullptr && g.pb16[l] != nullptr;
-        fin_args[j] = g;
-      }
-      if (fin16)
-        for (int j = 0; j < nc; ++j)
-          for (int l = 1; l + 1 < fin_args[j].net.n_layers; ++l) fin_args[j].net.pf[l] = fin_args[j].pf16[l];
-      fin_ride = mlp_layerwise_fin_ok(fin_args, nc, h->w_critic);
-    }
-    // as many nets as fit beside the forward's 4 x slices workgroups with everything resident at once (4 of TQC's 5)
-    const int n_ride = fin_ride ? mlp_layerwise_fin_fit(fin_args, nc, 4 * n_slices, h->n_cus) : 0;
-    if (fin_ride && n_ride >= 1) {
-      MlpArgs ff = f;
-      RC(next_tp_tag(ff.tp_tag_counter, ff.tp_xbuf, ff.tp_xbuf_bytes, st, &ff.tp_tag));
-      prof_begin(0, st);
-      hipError_t e = launch_slice_tp_with_fin(ff, fin_args, nc, n_ride, h->w_critic, h->n_cus, st, fin16 ? (h->x2 ? 2 : 1) : 0);
-      prof_end(st);
-      HIPC(e);
-      h->fin_done = true;
-      h->fin16 = fin16;
-      if (n_ride < nc) h->fin_tail0 = n_ride;
-    } else {
-      RC(launch(f, h->w_actor, st));
-    }
-  }
-  // 2. target critics on (s', a')   (independent: one stream each)
-  if (algo == OPRL_TQC && h->tqc_counter != nullptr && !h->sw.no_tqc_ride) {
-    TqcJob& J = h->tqc_job;
-    J.counter = h->tqc_counter;
-    J.z = h->qn; J.net_stride = (long)h->Bmax * h->ldq; J.ldz = h->ldq;
-    J.n_nets = nc; J.Q = c.hp.n_quantiles; J.drop = c.hp.top_quantiles_to_drop;
-    J.r = r; J.d = d; J.logp = h->logp2; J.log_alpha = c.log_alpha; J.gamma = (float)c.hp.gamma;
-    J.target = h->target;
-    h->tqc_job_pending = true;
-  }
-  // REDQ: only the M target critics of this update's subset run, net redq_subset[j] into slot j of qn
-  const bool redq = algo == OPRL_REDQ;
-  const int n_min = redq ? c.hp.n_min : 0;
-  if (redq) redq_subset(h->noise_seed, h->noise_rank, (uint64_t)h->update_count, nc, n_min, h->redq_subset);
-  RC(for_each_net(h, redq ? n_min : nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = base_args(h, c.critics[redq ? h->redq_subset[j] : j], true, B);
-    f.do_fwd = 1;
-    f.x0 = s2; f.k0 = S; f.x1 = h->a2; f.k1 = A;
-    f.out = h->qn + (size_t)j * h->Bmax * h->ldq; f.ldo = h->ldq;
-    return f;
-  }));
-  // (M > 2: their minimum as one row, k_redq_min, into the TQC target's buffer, which REDQ does not use)
-  if (redq && n_min > 2) HIPC(launch_redq_min(h->qn, (long)h->Bmax * h->ldq, h->ldq, n_min, B, h->target, st));
-  if (h->fin_tail0 >= 0) {                           // (the rest of the early first launch found no head launch to ride on)
-    prof_begin(0, st);
-    hipError_t e = launch_mlp_layerwise_first(h->fin_args, nc, h->fin_tail0, h->w_critic, h->n_cus, st, h->fin16 ? (h->x2 ? 2 : 1) : 0);
-    prof_end(st);
-    HIPC(e);
-    h->fin_tail0 = -1;
-  }
-  // (the job did not ride — not the layer-by-layer path — or was never offered)
-  if (algo == OPRL_TQC && (h->tqc_job_pending || h->tqc_counter == nullptr || h->sw.no_tqc_ride)) {
-    h->tqc_job_pending = false;
-    const int Q = c.hp.n_quantiles, drop = c.hp.top_quantiles_to_drop;
-    HIPC(launch_tqc_target(h->qn, (long)h->Bmax * h->ldq, h->ldq, nc, Q, drop, r, d, h->logp2,
-                           c.log_alpha, (float)c.hp.gamma, B, h->target, st));
-  }
-  // 3. online critics: forward + loss seed + backward   (independent: one stream each)
-  // TQC: the actor step's forward on s depends on nothing of the critic step: offered as a rider of this launch's
-  // heads (k_lw_head: 80 workgroups on 256 CUs), with the noise and the counter actor_phase would give it
-  h->rider_pending = false;
-  h->rider_done = false;
-  if (h->cql_n > 0) {              // the conservative-Q-learning mode: the critic step on the wide rows, then step 4 on as many
-    if (rows.w != nullptr) { set_err("internal: importance weights reached the conservative-Q-learning critic step"); return OPRL_ERR_STATE; }
-    RC(cql_critic_step(h, rows, B, st));
-    return dw_step(h, true, B * (1 + 3 * h->cql_n), st);
-  }
-  if (rows.w != nullptr) {         // importance weights: the same step as three launches per grouping, then step 4
-    RC(weighted_critic_step(h, rows, B, n_min, st));
-    return dw_step(h, true, B, st);
-  }
-  if (algo == OPRL_D4PG) {         // the categorical critic: forward | k_c51_critic_seed | backward, then step 4
-    RC(c51_critic_step(h, rows, B, st));
-    return dw_step(h, true, B, st);
-  }
-  if (algo == OPRL_TQC && !h->sw.no_af_ride && !c.export_grads && actor_due(h)) {
-    MlpArgs f = actor_forward_args(h, s, B, h->noise1_pending);
-    if (f.tp_xbuf != nullptr) {
-      RC(next_tp_tag(f.tp_tag_counter, f.tp_xbuf, f.tp_xbuf_bytes, st, &f.tp_tag));
-      h->rider = f;
-      h->rider_pending = true;
-    }
-  }
-  RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
-    MlpArgs f = critic_sa_args(h, j, s, a, B, true);
-    f.partials = h->part_c + (size_t)j * n_slices * 4;
-    SeedArgs& sd = f.seed;
-    if (algo == OPRL_TQC) {
-      const int Q = c.hp.n_quantiles, M = nc * Q - c.hp.top_quantiles_to_drop;
-      f.seed_mode = SEED_QHUBER;
-      sd.p0 = h->target; sd.M = M; sd.Q = Q;
-      sd.cval = 1.0f / ((float)B * (float)nc * (float)Q * (float)M);
-    } else {
-      f.seed_mode = SEED_MSE_TD;
-      sd = mse_td_seed(h, r, d, B, n_min);
-      if (j == 0) { sd.y_out = h->ydbg; sd.q_out = h->qdbg; }
-    }
-    return f;
-  }));
-  h->rider_pending = false;          // (not taken: actor_phase launches the forward itself)
-  if (h->fin_done) {                 // the early first launch was not picked up: step 3 did not run layer by layer
-    h->fin_done = false;
-    set_err("TQC critic step: the online critics' early first launch has no layer-by-layer continuation");
-    return OPRL_ERR_STATE;
-  }
-  // 4. dW + Adam (+ Polyak where the reference does it every step)
-  return dw_step(h, true, B, st);
+  return use_fused(h, B) ? fused_critic_phase(h, rows, B, noise0, st) : generic_critic_phase(h, rows, B, noise0, st);
 }
 
 // ------------------------------------------------------------- actor phase
-int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hipStream_t st) {
+// phase 2 of a fused update (with the actor's dW tiles where they ride), the actor's dW + Adam and the temperature step
+static int fused_actor_phase(oprl_learner* h, StepRows& rows, int B, hipStream_t st) {
   const oprl_learner_config& c = h->cfg;
-  const float* s = rows.cur.s;
+  DdpgArgs fa = ddpg_args(h, rows, B);
+  if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));
+  RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
+  if (h->trace != nullptr && c.algo == OPRL_DDPG) fa.trace = h->trace + (size_t)3 * 64 * kTraceStamps * 2;   // slot 3
+  else if (h->trace != nullptr && h->nc == 2) fa.trace = h->trace + (size_t)6 * 64 * kTraceStamps * 2;      // twin critics: roles 0 .. 3 are phase 1's, slot 6
+  fa.prefetch_next = rows.stage == StepRows::kPhase2 ? 1 : 0;
+  // Where phase 2's own workgroups already fill the chip (SAC at B = 1024: 4 x 64), its prefetch row is a round of
+  // its own; the actor's dW launch, which follows and leaves 40 % of the chip idle, carries the row instead
+  // (prefetch_rows_direct, the same rows).
+  bool pf_on_dw = false;
+  PrefetchJob pj;
+  {
+    const int slices = n_slices(B);
+    const int grid_rows = (fa.wide & 2) != 0 ? 8 : fa.nc * ((fa.sac && fa.p2_pair) ? 2 : 1);
+    if (fa.prefetch_next && (grid_rows + 1) * slices > h->n_cus && !h->dp_inline) {
+      pf_on_dw = true;
+      fa.prefetch_next = 0;
+      memset((void*)&pj, 0, sizeof pj);
+      pj.next = fa.next; pj.S = h->S; pj.A = h->A; pj.B = B; pj.z0 = -1;
+    }
+  }
+  if (rows.stage == StepRows::kPhase2) rows.staged = true;
+  if ((fa.merged & 2) != 0 && !pf_on_dw) {
+    // phase 2 and the actor's dW + Adam tiles as ONE launch: the tiles wait for the du (first layer: dz1) granules
+    const DwArgs dw = dw_args(h, false, B, h->opt_step_actor + 1);
+    DwKArgs kd;
+    if (fill_dw_kargs(dw, &kd, (fa.x2 && fused_x2_tiles()) ? 64 : 32) < 0 || dw.n_items != 3) { set_err("merged phase 2: bad dW table"); return OPRL_ERR_INVALID; }
+    actor_gate(h, fa, B, kd.gate);
+    RC(profiled(5, st, [&] { return launch_ddpg_phase2_dw(fa, kd, st); }));
+    dw_commit(h, false, dw, 1);
+    return OPRL_OK;
+  }
+  RC(profiled(5, st, [&] { return launch_ddpg_phase2(fa, st); }));
+  RC(dw_step(h, false, B, st, pf_on_dw ? &pj : nullptr));
+  return temperature_step(h, B, st);      // SAC temperature (sac.py:129-141), from role C's log pi
+}
+
+int actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hipStream_t st) {
   if (h->whole_done) {          // (this update's actor step ran inside the critic phase's launch: k_ddpg_update)
     h->whole_done = false;
     return OPRL_OK;
   }
-  if (use_fused(h, B)) {
-    DdpgArgs fa = ddpg_args(h, rows, B);
-    if (h->x2 && !fa.x2) RC(fresh32_tables(h, 3, st));
-    RC(next_tp_tag(&h->tp_tag, h->xbuf, h->xbuf_granules * sizeof(unsigned long long), st, &fa.cluster_tag));
-    if (h->trace != nullptr && c.algo == OPRL_DDPG) fa.trace = h->trace + (size_t)3 * 64 * kTraceStamps * 2;   // slot 3
-    else if (h->trace != nullptr && h->nc == 2) fa.trace = h->trace + (size_t)6 * 64 * kTraceStamps * 2;      // twin critics: roles 0 .. 3 are phase 1's, slot 6
-    fa.prefetch_next = rows.stage == StepRows::kPhase2 ? 1 : 0;
-    // Where phase 2's own workgroups already fill the chip (SAC at B = 1024: 4 x 64), its prefetch row is a round of
-    // its own; the actor's dW launch, which follows and leaves 40 % of the chip idle, carries the row instead
-    // (prefetch_rows_direct, the same rows).
-    bool pf_on_dw = false;
-    PrefetchJob pj;
-    {
-      const int slices = (B + kR - 1) / kR;
-      const int grid_rows = (fa.wide & 2) != 0 ? 8 : fa.nc * ((fa.sac && fa.p2_pair) ? 2 : 1);
-      if (fa.prefetch_next && (grid_rows + 1) * slices > h->n_cus && !h->dp_inline) {
-        pf_on_dw = true;
-        fa.prefetch_next = 0;
-        memset((void*)&pj, 0, sizeof pj);
-        pj.next = fa.next; pj.S = h->S; pj.A = h->A; pj.B = B; pj.z0 = -1;
-      }
-    }
-    if (rows.stage == StepRows::kPhase2) rows.staged = true;
-    if ((fa.merged & 2) != 0 && !pf_on_dw) {
-      // phase 2 and the actor's dW + Adam tiles as ONE launch: the tiles wait for the du (first layer: dz1) granules
-      const DwArgs dw = dw_args(h, false, B, h->opt_step_actor + 1);
-      DwKArgs kd;
-      if (fill_dw_kargs(dw, &kd, (fa.x2 && fused_x2_tiles()) ? 64 : 32) < 0 || dw.n_items != 3) { set_err("merged phase 2: bad dW table"); return OPRL_ERR_INVALID; }
-      actor_gate(h, fa, B, kd.gate);
-      prof_begin(5, st);
-      hipError_t e = launch_ddpg_phase2_dw(fa, kd, st);
-      prof_end(st);
-      HIPC(e);
-      dw_commit(h, false, dw, 1);
-      return OPRL_OK;
-    }
-    prof_begin(5, st);
-    hipError_t e = launch_ddpg_phase2(fa, st);
-    prof_end(st);
-    HIPC(e);
-    RC(dw_step(h, false, B, st, pf_on_dw ? &pj : nullptr));
-    return temperature_step(h, B, st);      // SAC temperature (sac.py:129-141), from role C's log pi
-  }
-  RC(fresh32_tables(h, 3, st));
-  const int S = h->S, A = h->A, nc = h->nc;
-  const int algo = c.algo;
-  const bool gauss = gauss_actor(h);
-  const int n_q = (algo == OPRL_TD3 || algo == OPRL_DDPG || algo == OPRL_D4PG) ? 1 : nc;   // TD3 uses Q1 only
-  // (the offers to the riding launches below never outlive this update: after an error return the next must not find one)
-  struct ClearOffers {
-    oprl_learner* h;
-    ~ClearOffers() { h->bwd_rider_pending = false; h->bwd_rider_done = false; h->bwd_tiles_pending = false; h->bwd_tiles_done = false; }
-  } clear_offers{h};
-  auto actor_backward_args = [&]() {      // step 8's launch
-    MlpArgs f = base_args(h, c.actor, false, B);
-    f.do_bwd = 1;
-    with_store(f, h->ws_actor, true, true);
-    SeedArgs& sd = f.seed;
-    if (gauss) {
-      f.seed_mode = SEED_GAUSS;
-      sd.p0 = h->da; sd.ld0 = A; sd.n_da = n_q; sd.da_stride = (long)h->Bmax * A;
-      sd.p1 = h->raw;
-      seed_rng(f, h, noise1, 2);   // backward re-reads (or re-draws) the forward's eps
-      sd.log_alpha = alpha_ptr(h); sd.alpha_const = (float)c.hp.alpha_init;
-      sd.cval = 1.0f / (float)B;
-    } else {
-      f.seed_mode = SEED_TANH;
-      sd.p0 = h->da; sd.ld0 = A; sd.p1 = h->pi;
-    }
-    return f;
-  };
-  DwArgs actor_dw;                        // step 9's table where it rides (built with this update's step counts)
-  // 5. actor forward (activations kept for its backward) — unless it rode on the critic step's heads (critic_phase)
-  if (h->rider_done) {
-    h->rider_done = false;
-  } else {
-    const MlpArgs f = actor_forward_args(h, s, B, noise1);
-    RC(launch(f, h->w_actor, st));
-  }
-  // 6./7. critics on (s, pi): gradient wrt the action columns
-  if (algo == OPRL_SAC) {
-    RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {   // both q's before either seed (min)
-      MlpArgs f = base_args(h, c.critics[j], false, B);
-      f.do_fwd = 1;
-      f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
-      with_store(f, h->ws_critic[j], true, false);
-      f.out = h->qpi + (size_t)j * h->Bmax; f.ldo = 1;
-      return f;
-    }));
-    RC(for_each_net(h, nc, h->w_critic, st, [&](int j) {
-      MlpArgs f = base_args(h, c.critics[j], false, B);
-      f.do_bwd = 1;
-      with_store(f, h->ws_critic[j], true, false);
-      f.seed_mode = SEED_MINQ;
-      f.seed.p0 = h->qpi; f.seed.p1 = h->qpi + h->Bmax; f.seed.which = j;
-      f.seed.cval = 1.0f / (float)B;
-      f.dact_col0 = S; f.dact_cols = A; f.dact = h->da + (size_t)j * h->Bmax * A; f.lddact = A;
-      if (j == 0) f.partials = h->part_a;
-      return f;
-    }));
-  } else if (algo == OPRL_D4PG) {
-    // the categorical critic on (s, pi): its logits, then the seed -(1/B) p_j (z_j - Q) of the loss -(1/B) sum_b Q_b
-    // (k_c51_actor_seed), then the backward that leaves the action gradients
-    if (h->c51_logits == nullptr || h->c51_seed == nullptr) { set_err("internal: categorical actor step without its buffers"); return OPRL_ERR_STATE; }
-    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
-      MlpArgs f = base_args(h, c.critics[0], false, B);
-      f.do_fwd = 1;
-      f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
-      with_store(f, h->ws_critic[0], true, false);
-      f.out = h->c51_logits; f.ldo = h->ldq;
-      return f;
-    }));
-    C51Args t = c51_args(h, B);
-    t.partials = h->part_a;
-    prof_begin(3, st);
-    hipError_t e = launch_c51_actor_seed(t, st);
-    prof_end(st);
-    HIPC(e);
-    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
-      MlpArgs f = c51_backward_args(h, B, false);
-      f.dact_col0 = S; f.dact_cols = A; f.dact = h->da; f.lddact = A;
-      return f;
-    }));
-  } else if (h->iql_on) {
-    // implicit Q-learning (oprl_learner_set_iql): no critic runs on (s, pi).  The action gradients are
-    // (2/B) w_b (pi - a) with the weights the critic phase's k_iql_value_seed left, written in full by k_iql_actor_seed
-    if (algo != OPRL_TD3 || h->iql_base == nullptr) { set_err("internal: implicit-Q-learning actor step without its buffers"); return OPRL_ERR_STATE; }
-    IqlActorArgs m;
-    memset((void*)&m, 0, sizeof m);
-    m.pi = h->pi; m.a = rows.cur.a; m.w = h->iql_w;
-    m.two_inv_B = 2.0f / (float)B;
-    m.B = B; m.A = A; m.n_slices = (B + kR - 1) / kR;
-    m.da = h->da; m.part = h->part_a;
-    prof_begin(3, st);
-    hipError_t e = launch_iql_actor_seed(m, st);
-    prof_end(st);
-    HIPC(e);
-  } else if (h->bc_alpha > 0.0) {
-    // TD3 + BC (oprl_learner_set_bc): where TD3 runs one forward + backward launch of critic 0 from
-    // SEED_CONST -1/B, the seed is -lambda/B with lambda = alpha / mean |Q1(s, pi)|, which needs every row's q first — so
-    // critic 0's forward with the activations stored and q into qpi (idle since the critic step), k_bc_seed, critic 0's
-    // backward from the seed rows (SEED_PTR, ld0 = 1), and k_bc_mix, which adds (2 / (B A)) (pi - a) to the action gradients
-    if (algo != OPRL_TD3 || h->bc_seed == nullptr) { set_err("internal: behaviour-cloning actor step without its buffers"); return OPRL_ERR_STATE; }
-    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
-      MlpArgs f = base_args(h, c.critics[0], false, B);
-      f.do_fwd = 1;
-      f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
-      with_store(f, h->ws_critic[0], true, false);
-      f.out = h->qpi; f.ldo = 1;
-      return f;
-    }));
-    BcSeedArgs t;
-    memset((void*)&t, 0, sizeof t);
-    t.q = h->qpi; t.alpha = (float)h->bc_alpha;
-    t.B = B; t.n_slices = (B + kR - 1) / kR;
-    t.seed = h->bc_seed; t.scal = h->bc_scal; t.partials = h->part_a;
-    prof_begin(3, st);
-    hipError_t e = launch_bc_seed(t, st);
-    prof_end(st);
-    HIPC(e);
-    RC(for_each_net(h, 1, h->w_critic, st, [&](int) {
-      MlpArgs f = base_args(h, c.critics[0], false, B);
-      f.do_bwd = 1;
-      with_store(f, h->ws_critic[0], true, false);
-      f.seed_mode = SEED_PTR;
-      f.seed.p0 = h->bc_seed; f.seed.ld0 = 1;
-      f.dact_col0 = S; f.dact_cols = A; f.dact = h->da; f.lddact = A;
-      return f;
-    }));
-    BcMixArgs m;
-    memset((void*)&m, 0, sizeof m);
-    m.pi = h->pi; m.a = rows.cur.a; m.da = h->da; m.part = h->bc_part;
-    m.B = B; m.A = A;
-    prof_begin(3, st);
-    e = launch_bc_mix(m, st);
-    prof_end(st);
-    HIPC(e);
-    h->bc_parts = bc_mix_slices(B, A); h->bc_B = B;
-  } else {
-    // TQC: the actor's backward (step 8) consumes the action gradients the launch sequence below ends with (k_lw_dact):
-    // offered as a rider of that launch (r06-16; the tag its launch would draw, now)
-    h->bwd_rider_pending = false;
-    h->bwd_rider_done = false;
-    if (algo == OPRL_TQC && gauss && !c.export_grads && !h->sw.no_bwd_ride) {
-      MlpArgs f = actor_backward_args();
-      if (f.tp_xbuf != nullptr && mlp_slice_tp_shape_ok(f, h->w_actor)) {
-        RC(next_tp_tag(f.tp_tag_counter, f.tp_xbuf, f.tp_xbuf_bytes, st, &f.tp_tag));
-        h->bwd_rider = f;
-        h->bwd_rider_pending = true;
-        // ... and step 9's tiles behind it (the 16 x 32 tiles of k_dw_adam, the temperature's step as the workgroup one past
-        // them): built with THIS update's step counts, committed once they have ridden; if the launch does not take them,
-        // step 9 launches the same table
-        h->bwd_tiles_pending = false;
-        h->bwd_tiles_done = false;
-        if (!h->sw.no_bwd_tiles && alpha_rides(h) && h->n_items_actor <= kDwMaxItems) {
-          actor_dw = dw_args(h, false, B, h->opt_step_actor + 1);
-          actor_dw.alpha = alpha_job(h, B, h->opt_step_alpha + 1);
-          const int total = fill_dw_kargs(actor_dw, &h->bwd_tiles, 32);
-          if (total > 0) {
-            h->bwd_tile_wgs = total + (actor_dw.alpha.log_alpha != nullptr ? 1 : 0);
-            h->bwd_tiles_pending = true;
-          }
-        }
-      }
-    }
-    RC(for_each_net(h, n_q, h->w_critic, st, [&](int j) {
-      MlpArgs f = base_args(h, c.critics[j], false, B);
-      f.do_fwd = 1; f.do_bwd = 1;
-      f.x0 = s; f.k0 = S; f.x1 = h->pi; f.k1 = A;
-      f.seed_mode = SEED_CONST;
-      f.seed.cval = (algo == OPRL_TQC) ? -1.0f / ((float)B * (float)nc * (float)c.hp.n_quantiles)
-                    : (algo == OPRL_REDQ) ? -1.0f / ((float)B * (float)nc)      // the mean over the ensemble
-                                          : -1.0f / (float)B;
-      f.dact_col0 = S; f.dact_cols = A; f.dact = h->da + (size_t)j * h->Bmax * A; f.lddact = A;
-      if (j == 0) f.partials = h->part_a;
-      if (algo == OPRL_REDQ) f.partials = h->part_a + (size_t)j * ((B + kR - 1) / kR) * 4;   // (read_scalars: mean over all N)
-      return f;
-    }));
-  }
-  // 8. actor backward from the stored activations — unless it rode on the k_lw_dact launch above
-  h->bwd_rider_pending = false;
-  if (h->bwd_rider_done) {
-    h->bwd_rider_done = false;
-  } else {
-    RC(launch(actor_backward_args(), h->w_actor, st));
-  }
-  // 9. dW + Adam (+ Polyak of the actor target for DDPG / TD3) — unless the tiles rode behind the riding backward
-  h->bwd_tiles_pending = false;
-  if (h->bwd_tiles_done) dw_commit(h, false, actor_dw, 1);
-  else RC(dw_step(h, false, B, st));
-  // 10. temperature (when it did not ride on the actor's dW launch)
-  return temperature_step(h, B, st);
+  return use_fused(h, B) ? fused_actor_phase(h, rows, B, st) : generic_actor_phase(h, rows, B, noise1, st);
 }
 
 // master -> packs for a list of nets (which: bit0 online, bit1 target).  The item
@@ -1667,14 +990,6 @@ int check_batch(const oprl_learner* h, const void* s, const void* a, const void*
 }
 
 // Has a kernel of this learner reported an expired wait?  (Sticky until oprl_learner_clear_error.)
-// the conservative-Q-learning mode's critic step runs on B (1 + 3 N) rows of the workspace
-int cql_rows_fit(const oprl_learner* h, const char* who, int B) {
-  if (h->cql_n == 0 || (long)B * (1 + 3 * h->cql_n) <= (long)h->Bmax) return OPRL_OK;
-  set_err("%s: the conservative-Q-learning mode's critic step needs batch x (1 + 3 n_actions) = %d x %d = %ld rows of a workspace "
-          "of max_batch=%d; create the learner with a larger max_batch or lower n_actions", who, B, 1 + 3 * h->cql_n,
-          (long)B * (1 + 3 * h->cql_n), h->Bmax);
-  return OPRL_ERR_INVALID;
-}
 
 int check_device_error(const oprl_learner* h) {
   if (h == nullptr || h->err_host == nullptr) return OPRL_OK;
@@ -1788,12 +1103,12 @@ extern "C" int oprl_abi_version(void) { return OPRL_ABI_VERSION; }
 namespace oprl_host {
 int learner_update_phase(oprl_learner* h, int phase, StepRows& rows, int B, const float* noise0, const float* noise1, void* stream) {
   RC(check_batch(h, rows.cur.s, rows.cur.a, rows.cur.r, rows.cur.d, rows.cur.s2, B));
-  if (h->calql_on && rows.g == nullptr) {
+  if (h->cql.cal_on && rows.g == nullptr) {
     set_err("update: the learner's calibrated mode is on (oprl_learner_set_calql) and these rows carry no returns-to-go; "
             "oprl_learner_update_calql takes them, oprl_learner_step_n computes them");
     return OPRL_ERR_STATE;
   }
-  if (!h->calql_on && rows.g != nullptr) {
+  if (!h->cql.cal_on && rows.g != nullptr) {
     set_err("update: returns-to-go for a learner whose calibrated mode is off (oprl_learner_set_calql)");
     return OPRL_ERR_STATE;
   }
@@ -1971,7 +1286,7 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
   int nstep = 1;
   RC(RowStager::check("step_n", h, replay, false, K, B, &nstep));
   RC(cql_rows_fit(h, "step_n", B));
-  if (h->calql_on && replay_her(replay) > 0) {      // (before anything is launched; oprl_replay_returns would say the same after the sample)
+  if (h->cql.cal_on && replay_her(replay) > 0) {      // (before anything is launched; oprl_replay_returns would say the same after the sample)
     set_err("step_n: the learner's calibrated mode is on (oprl_learner_set_calql) and the replay relabels goals in hindsight "
             "(oprl_replay_set_her): its rewards are relabelled per sample, so its slots have no returns-to-go");
     return OPRL_ERR_STATE;
@@ -2027,11 +1342,11 @@ extern "C" int oprl_learner_step_n(oprl_learner* h, oprl_replay* replay, int32_t
     return rc;
   }
   for (int k = 0; k < K; ++k) {
-    if (h->calql_on) {      // the sampler's slots -> their returns-to-go with the learner's gamma -> the calibrated update
+    if (h->cql.cal_on) {      // the sampler's slots -> their returns-to-go with the learner's gamma -> the calibrated update
       RC(oprl_replay_sample(replay, B, nullptr, seed, (uint64_t)h->update_count, h->bs, h->ba, h->br,
-                            h->bd, h->bs2, h->calql_ep, h->calql_step, stream));
-      RC(oprl_replay_returns(replay, B, h->calql_ep, h->calql_step, h->cfg.hp.gamma, h->calql_g, stream));
-      RC(oprl_learner_update_calql(h, h->bs, h->ba, h->br, h->bd, h->bs2, h->calql_g, B, nullptr, nullptr, stream));
+                            h->bd, h->bs2, h->cql.ep, h->cql.step, stream));
+      RC(oprl_replay_returns(replay, B, h->cql.ep, h->cql.step, h->cfg.hp.gamma, h->cql.g, stream));
+      RC(oprl_learner_update_calql(h, h->bs, h->ba, h->br, h->bd, h->bs2, h->cql.g, B, nullptr, nullptr, stream));
       continue;
     }
     RC(oprl_replay_sample(replay, B, nullptr, seed, (uint64_t)h->update_count, h->bs, h->ba, h->br,

@@ -133,13 +133,12 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   const int B = h->Bmax, S = h->S, A = h->A, nc = h->nc;
   // scalar critics: q' is read with stride 1 by the TD seed; TQC: [B][ldq] quantile rows; D4PG: [B][ldq] rows of logits
   h->ldq = (cfg->algo == OPRL_TQC || cfg->algo == OPRL_D4PG) ? round_up(cfg->critics[0].dims[cfg->critics[0].n_layers], 4) : 1;
-  const int n_slices = (B + kR - 1) / kR;
   size_t floats = net_ws_floats(cfg->actor, B);
   for (int j = 0; j < nc; ++j) floats += net_ws_floats(cfg->critics[j], B);
   floats += (size_t)B * A + B + (size_t)nc * B * h->ldq + (size_t)B * A + (size_t)B * 2 * A + B +
             (size_t)nc * B * A + (size_t)nc * B + (size_t)B * 128 + 2 * (size_t)B;
   const int n_part_a = cfg->algo == OPRL_REDQ ? nc : 1;   // (REDQ: every critic's actor-step sums, the ensemble mean)
-  floats += (size_t)(nc + n_part_a) * n_slices * 4 + 16;
+  floats += (size_t)(nc + n_part_a) * n_slices(B) * 4 + 16;
   floats += (size_t)B * (2 * S + A + 2);
   if (cfg->algo == OPRL_D4PG) floats += 2 * ((size_t)B * h->ldq + 64);     // (the online logits and their seed rows)
   floats += 64 * 32 + 8 * (size_t)B + 512;      // (granule arrays: y, q1, q2, the twin's seeds; 256 gate flags)
@@ -196,8 +195,8 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   h->target = p.take<float>((size_t)B * 128);
   h->ydbg = p.take<float>(B);
   h->qdbg = p.take<float>(B);
-  h->part_c = p.take<float>((size_t)nc * n_slices * 4);
-  h->part_a = p.take<float>((size_t)n_part_a * n_slices * 4);
+  h->part_c = p.take<float>((size_t)nc * n_slices(B) * 4);
+  h->part_a = p.take<float>((size_t)n_part_a * n_slices(B) * 4);
   h->scalars = p.take<float>(16);
   h->alpha_grad = cfg->log_alpha_grad ? cfg->log_alpha_grad : p.take<double>(2);
   h->y_granules = p.take<unsigned long long>((size_t)4 * B + 256);      // [TD target / seeds | q1 | q2 | 256 gate flags | the twin critic's seeds]
@@ -213,8 +212,8 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
     h->w3buf1 = p.take<float>(16 * 256);
   }
   if (cfg->algo == OPRL_D4PG) {
-    h->c51_logits = p.take<float>((size_t)B * h->ldq);
-    h->c51_seed = p.take<float>((size_t)B * h->ldq);
+    h->c51.logits = p.take<float>((size_t)B * h->ldq);
+    h->c51.seed = p.take<float>((size_t)B * h->ldq);
   }
   h->bs = p.take<float>((size_t)B * S);
   h->ba = p.take<float>((size_t)B * A);
@@ -328,7 +327,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
       }
     }
     if (cfg->algo == OPRL_TQC && nc * cfg->hp.n_quantiles <= 128) {
-      const size_t slices = (size_t)(h->Bmax + kR - 1) / kR;
+      const size_t slices = (size_t)n_slices(h->Bmax);
       if (hipMalloc(&h->tqc_counter, slices * sizeof(unsigned long long)) != hipSuccess) h->tqc_counter = nullptr;   // (then: the stand-alone launch)
       else (void)hipMemset(h->tqc_counter, 0, slices * sizeof(unsigned long long));
     }
@@ -338,7 +337,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
     h->tp_generic_on = !h->sw.no_lean && h->ncl == 4;
   }
   if (h->fused || h->tp_generic_on) {
-    const size_t slices = (size_t)(h->Bmax + kR - 1) / kR;
+    const size_t slices = (size_t)n_slices(h->Bmax);
     // (areas laid out for clusters of eight where wide clusters may run: DDPG / TD3, fp32, lean passes)
     h->xnc = (h->fused && (!h->bf16 || h->bchain) && !h->sw.no_lean && !h->sw.no_wide && h->ncl == 4 &&
               (cfg->algo == OPRL_DDPG || cfg->algo == OPRL_TD3)) ? 8 : kMaxCluster;
@@ -387,8 +386,8 @@ extern "C" int oprl_learner_sync_params(oprl_learner* h, void* stream) {
     RC(repack_nets(fn, 2, 3, (hipStream_t)stream));
   }
   RC(repack_nets(nets, h->nc + 1, 3, (hipStream_t)stream, (h->bf16 || h->x2) ? p16 : nullptr, (h->bf16 || h->x2) ? p16t : nullptr, h->planes));
-  if (h->iql_on) {                           // the value net of the implicit-Q-learning mode (f32 learners only; no target)
-    const oprl_net* v[1] = {&h->iql_value};
+  if (h->iql.on) {                           // the value net of the implicit-Q-learning mode (f32 learners only; no target)
+    const oprl_net* v[1] = {&h->iql.value};
     RC(repack_nets(v, 1, 1, (hipStream_t)stream));
   }
   return OPRL_OK;
@@ -420,11 +419,7 @@ extern "C" int oprl_learner_destroy(oprl_learner* h) {
   if (h->lw_scratch) (void)hipFree(h->lw_scratch);
   if (h->lw_pairs.flags) (void)hipFree(h->lw_pairs.flags);
   dev_free(h->batch_alt);
-  if (h->per_seed) (void)hipFree(h->per_seed);
-  if (h->bc_seed) (void)hipFree(h->bc_seed);
-  if (h->iql_base) (void)hipFree(h->iql_base);
-  if (h->cql_base) (void)hipFree(h->cql_base);
-  if (h->calql_ep) (void)hipFree(h->calql_ep);
+  free_modes(h);
   dev_free(h->uc_base);
   if (h->err_host) (void)hipHostFree(h->err_host);
   if (h->act_pin) (void)hipHostFree(h->act_pin);

@@ -40,11 +40,11 @@ extern "C" int oprl_group_create(oprl_learner** learners, int32_t n, oprl_group*
   const int algo0 = learners[0] ? learners[0]->cfg.algo : -1;
   for (int i = 0; i < n; ++i) {
     oprl_learner* h = learners[i];
-    if (h && h->bc_alpha > 0.0) {
+    if (h && h->bc.alpha > 0.0) {
       set_err("oprl_group_create: member %d has the behaviour-cloning mode on (oprl_learner_set_bc); packed learners run the fused launches, which have no BC step", i);
       return OPRL_ERR_STATE;
     }
-    if (h && h->iql_on) {
+    if (h && h->iql.on) {
       set_err("oprl_group_create: member %d has the implicit-Q-learning mode on (oprl_learner_set_iql); packed learners run the fused launches, which have no value net", i);
       return OPRL_ERR_STATE;
     }
@@ -64,7 +64,7 @@ extern "C" int oprl_group_create(oprl_learner** learners, int32_t n, oprl_group*
   {
     oprl_learner* h0 = learners[0];
     // (the lean passes on clusters of four, as the members will run them: nc_cluster with ncl = 4)
-    const bool lean = 4 * ((h0->Bmax + kR - 1) / kR) <= h0->n_cus && fused_ddpg_is_lean(4, h0->sw.no_lean, h0->S, h0->A, algo0 == OPRL_SAC);
+    const bool lean = 4 * n_slices(h0->Bmax) <= h0->n_cus && fused_ddpg_is_lean(4, h0->sw.no_lean, h0->S, h0->A, algo0 == OPRL_SAC);
     if (!lean || (algo0 == OPRL_DDPG && !h0->bf16 && !h0->x2)) group_nc = 1;
     if (group_nc == 1 && (h0->bf16 || h0->x2 || algo0 != OPRL_DDPG)) {
       set_err("oprl_group_create: TD3 / SAC members and the bf16 / x2 modes need nets the lean passes take (256-wide hidden layers, narrow inputs)");

@@ -226,6 +226,8 @@ struct NetWs {
   long dY0_stride = 0;   // dY[0] is kMaxCluster buffers this many floats apart (dz1 partials)
 };
 
+inline int n_slices(int B) { return (B + kR - 1) / kR; }   // row slices of kR rows: the grid of a net pass, the rows of a partials table
+
 struct Pool {  // one hipMalloc, bump allocated
   char* base = nullptr;
   size_t cap = 0, used = 0;
@@ -286,7 +288,7 @@ struct StepRows {
   const float* other_set[5] = {};  // ... and the other staging set (cur's s .. s2 are set 0 of the launch)
   bool staged = false;         // out: a launch that stages the next update's rows has gone out
   // training from prioritized replay (oprl_learner_update_weighted): the rows' importance weights [B] and where their
-  // |TD| goes [B]; null: the plain update.  Generic launch sequence only (critic_phase).
+  // |TD| goes [B]; null: the plain update.  Generic launch sequence only (generic_critic_phase).
   const float* w = nullptr;
   float* td_abs = nullptr;
   // calibrated Q-learning (oprl_learner_update_calql): the rows' returns-to-go [B], the lower bound of the
@@ -302,6 +304,8 @@ inline StepRows plain_rows(const float* s, const float* a, const float* r, const
 }  // namespace oprl_host
 
 using namespace oprl_host;
+
+#include "learner_modes.h"
 
 struct oprl_learner {
   Switches sw;                 // the environment switches, read by oprl_learner_create
@@ -345,62 +349,24 @@ struct oprl_learner {
   DwXchg dw_xchg;
   PrefetchJob prefetch;        // step_n on the generic path (TQC): the next update's rows as riders of this update's k_lw_dact launch
   bool prefetch_pending = false, prefetch_done = false;
-  // training from prioritized replay (learner_per.hip): one allocation of its own, made by the first weighted update —
-  // the weighted seeds [nc][Bmax], and step_n_prio's weights, |TD| and slots [Bmax] each; null on every other learner
-  float *per_seed = nullptr, *per_w = nullptr, *per_td = nullptr;
-  int* per_slots = nullptr;
-  // D4PG (c51_seed.hip): the online critic's logits [Bmax][ldq] between its forward-only and backward-only launches, and
-  // the seed rows SEED_PTR reads; in the pool, null on every other learner
-  float *c51_logits = nullptr, *c51_seed = nullptr;
-  // the behaviour-cloning mode of a TD3 learner's actor step (oprl_learner_set_bc, bc_seed.hip): alpha (0:
-  // off), and one allocation of its own, made when the mode is first turned on — the seed rows [Bmax] | lambda, mean |Q|
-  // and two spares [4] | k_bc_mix's partial sums [bc_mix_slices(Bmax, A)]; bc_parts: how many the last actor step wrote
-  double bc_alpha = 0.0;
-  float *bc_seed = nullptr, *bc_scal = nullptr, *bc_part = nullptr;
-  int bc_parts = 0, bc_B = 0;
-  // the implicit-Q-learning mode of a TD3 learner (oprl_learner_set_iql, iql_seed.hip): the caller's value
-  // net V(s) (iql_on: the mode), its hyper-parameters and its own Adam step count, and one allocation of its own, made when
-  // the mode is first turned on — V's workspace rows | V(s') | V(s) | u | w | the V seed [Bmax] each | the two tables of
-  // k_iql_value_seed's per-slice sums [slices at Bmax][4] each (the actor's go to part_a); V's dW items with their tiles
-  bool iql_on = false;
-  oprl_net iql_value = {};
-  double iql_tau = 0.0, iql_beta = 0.0, iql_clip = 0.0, iql_lr = 0.0;
-  int opt_step_value = 0;
-  float* iql_base = nullptr;
-  NetWs ws_value;
-  float *iql_vn = nullptr, *iql_vs = nullptr, *iql_u = nullptr, *iql_w = nullptr, *iql_seed = nullptr;
-  float *iql_part_v = nullptr, *iql_part_w = nullptr;
-  std::vector<DwItem> iql_items;
-  int iql_tiles = 0, iql_B = 0;
-  // the conservative-Q-learning mode of a SAC learner (oprl_learner_set_cql, cql_seed.hip): the penalty
-  // weight and the sampled actions per kind (cql_n = 0: off), and one allocation of its own, made when the mode is first
-  // turned on — the actor's raw head rows on s and on s' [Bmax][2A] each | the wide states [Bmax][S] and actions [Bmax][A] |
-  // the log-densities and the seed rows [nc][Bmax] | k_cql_seed's own per-slice sums [nc][slices at Bmax][4]; the test
-  // hook's noise arrays (null: Philox) and the row count of the last update with the mode on
-  double cql_alpha = 0.0;
-  int cql_n = 0, cql_B = 0, cql_last_n = 0;
-  float* cql_base = nullptr;
-  float *cql_raw_s = nullptr, *cql_raw_s2 = nullptr, *cql_ws = nullptr, *cql_wa = nullptr, *cql_logd = nullptr, *cql_seed = nullptr;
-  float* cql_part = nullptr;
-  const float *cql_eps = nullptr, *cql_uni = nullptr;
-  // the calibrated form of that mode (oprl_learner_set_calql, Cal-QL): on only while cql_n > 0; one
-  // allocation of its own, made when it is first turned on — step_n's slots (episode | step, int32) and returns-to-go,
-  // [Bmax] each; whether the last update with the CQL mode on was a calibrated one (read_cql's out[7])
-  bool calql_on = false, cql_last_cal = false;
-  int *calql_ep = nullptr, *calql_step = nullptr;
-  float* calql_g = nullptr;
+  // the modes (learner_modes.h): prioritized weights, D4PG, TD3 + BC, implicit Q-learning, (calibrated) conservative Q-learning
+  PerMode per;
+  C51Mode c51;
+  BcMode bc;
+  IqlMode iql;
+  CqlMode cql;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
-  MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (critic_phase step 1) ...
+  MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (generic_critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)
   bool fin16 = false;
   bool fin_l2_done = false;    // ... and the second hidden layer's forward rode on the target pass's heads behind the tail (r06-12); step 3 skips it too
-  bool fin_done = false;       // TQC: the online critics' first hidden launch rode on the actor's forward on s' (critic_phase step 1); step 3 skips it
+  bool fin_done = false;       // TQC: the online critics' first hidden launch rode on the actor's forward on s' (generic_critic_phase step 1); step 3 skips it
   LwPairBuf lw_pairs = {nullptr, 0, 1u, 1 << 20, nullptr, 3, 0};   // k_lw_mid_pair: flags (own allocation), tags; OPRL_AMD_LW_PAIR: bit 0 forward, bit 1 backward pairs (default 3)
   float* lw_scratch = nullptr; // [critics][layers 1 .. L-1][Bmax x 512]: activations of forward-only layer-by-layer launches (the target pass) — not the nets' dW exchange buffers, which the early first launch has already filled
-  MlpArgs rider;               // TQC: the actor's forward on s, prepared in critic_phase to ride on the critic step's head launch ...
-  bool rider_pending = false;  // ... offered to the next round (launch_layerwise_round); taken: rider_done, and actor_phase skips its step 5
+  MlpArgs rider;               // TQC: the actor's forward on s, prepared in generic_critic_phase to ride on the critic step's head launch ...
+  bool rider_pending = false;  // ... offered to the next round (launch_layerwise_round); taken: rider_done, and generic_actor_phase skips its step 5
   bool rider_done = false;
-  MlpArgs bwd_rider;           // TQC: the actor's backward, prepared in actor_phase to ride on the k_lw_dact launch whose rows it consumes (r06-16) ...
+  MlpArgs bwd_rider;           // TQC: the actor's backward, prepared in generic_actor_phase to ride on the k_lw_dact launch whose rows it consumes (r06-16) ...
   bool bwd_rider_pending = false;   // ... offered to the round with the action gradients; taken: bwd_rider_done, and step 8 is skipped
   bool bwd_rider_done = false;
   DwKArgs bwd_tiles;           // ... and its dW + Adam tiles (the actor's step 9) behind it (r06-18): offered with the rider; taken: bwd_tiles_done
@@ -443,7 +409,7 @@ struct oprl_learner {
   // Measured (profiles/r01g_batch_sweep.txt): worth it for the lean clusters of 4 (B = 512: 76 -> 51 us
   // per DDPG update); the generic passes on smaller clusters do better fully co-resident.
   int nc_cluster(int B) const {
-    const int slices = (B + kR - 1) / kR;
+    const int slices = n_slices(B);
     if (ncl == 4 && 4 * slices <= n_cus) return 4;
     const int roles = 2 + nc;
     int c = ncl;
@@ -502,7 +468,7 @@ struct oprl_learner {
   int rp_n[3] = {0, 0, 0}, rp_blocks[3] = {0, 0, 0};
 };
 
-// ---- internals of learner.hip the other host units call
+// ---- internals of learner.hip, learner_generic.hip and learner_modes.hip that cross units
 namespace oprl_host {
 const double* alpha_ptr(const oprl_learner* h);
 void dev_free(void* p);
@@ -525,9 +491,38 @@ void set_adam(AdamScalars& ad, double lr, double beta1, double beta2, double eps
 int next_tp_tag(unsigned* counter, unsigned long long* xbuf, size_t xbuf_bytes, hipStream_t st, unsigned* out);
 const oprl_net& eff(const oprl_learner* h, const oprl_net& n);
 int check_device_error(const oprl_learner* h);
-int cql_rows_fit(const oprl_learner* h, const char* who, int B);
-unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id);      // Philox key of a noise stream (1 .. 3: learner.hip; 4, 5: the CQL mode's)
+unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id);      // Philox key of a noise stream (1 .. 3: the update's and REDQ's; 4, 5: the CQL mode's)
+inline unsigned long long noise_key(const oprl_learner* h, uint64_t stream_id) { return noise_key(h->noise_seed, h->noise_rank, stream_id); }
+void redq_subset(uint64_t seed, int rank, uint64_t counter, int n, int m, int* out);
+bool tp_generic(const oprl_learner* h, const oprl_net& n, int B);
+AdamScalars adam_scalars(const oprl_learner* h, double lr, int step, bool polyak, float grad_scale);
+int dw_step(oprl_learner* h, bool critic, int B, hipStream_t st, const PrefetchJob* prefetch = nullptr);
+int temperature_step(oprl_learner* h, int B, hipStream_t st);
+// learner_generic.hip: the generic (per-net) launch sequence of an update, and the launch builders it shares with the modes
+int generic_critic_phase(oprl_learner* h, StepRows& rows, int B, const float* noise0, hipStream_t st);
+int generic_actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hipStream_t st);
+MlpArgs base_args(oprl_learner* h, const oprl_net& n, bool target, int B);
 void with_store(MlpArgs& a, const NetWs& ws, bool x, bool dy);
+MlpArgs critic_sa_args(oprl_learner* h, int j, const float* s, const float* a, int B, bool bwd);
+SeedArgs mse_td_seed(const oprl_learner* h, const float* r, const float* d, int B, int n_min);
+// net n forward only on the rows (x0 | x1; x1 null: x0 alone) with the activations kept in ws (store_dy: its dY rows
+// bound as well), the output to out [B][ldo]; and its counterpart, backward only from those activations with the seed rows
+// read from memory (SEED_PTR, ld0)
+MlpArgs forward_args(oprl_learner* h, const oprl_net& n, const NetWs& ws, bool store_dy, const float* x0, const float* x1, int B,
+                     float* out, int ldo);
+MlpArgs backward_args(oprl_learner* h, const oprl_net& n, const NetWs& ws, bool store_dy, int B, const float* seed, int ld0);
+void dact_to(MlpArgs& f, const oprl_learner* h, int j);      // the action columns' gradient of critic j's backward -> da[j]
+// learner_modes.hip: the modes' allocations, their steps of the generic sequence, and the wide rows' fit
+int per_alloc(oprl_learner* h);
+void free_modes(oprl_learner* h);
+int cql_rows_fit(const oprl_learner* h, const char* who, int B);
+int weighted_critic_step(oprl_learner* h, const StepRows& rows, int B, int n_min, hipStream_t st);
+int c51_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
+int cql_critic_step(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
+int iql_critic_phase(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
+int c51_action_grads(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
+int iql_action_grads(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
+int bc_action_grads(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
 hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st);
 void fill_items(const oprl_net& n, const NetWs& ws, std::vector<DwItem>& v, int* tiles, bool small_partial_tiles = false,
                 float* pk16 = nullptr, float* pk16_t = nullptr, int pl = 1);
@@ -541,6 +536,15 @@ int fresh32_tables(oprl_learner* h, int which /* bit 0 critics, bit 1 actor */, 
 // round of them — the n equal nets of one pass — from their finished arguments (tags and borrowed buffers are written into a[])
 int launch(const MlpArgs& a, int width, hipStream_t st);
 int launch_round(oprl_learner* h, MlpArgs* a, int n, int width, hipStream_t st);
+// One round of the generic launch sequence: make_j(j) builds the arguments of net j in [0, n), and launch_round decides
+// from the list how they go out.
+template <class F>
+int for_each_net(oprl_learner* h, int n, int width, hipStream_t st, F&& make_j) {
+  MlpArgs a[OPRL_MAX_CRITICS];
+  if (n > OPRL_MAX_CRITICS) { set_err("internal: a round of %d nets", n); return OPRL_ERR_STATE; }
+  for (int j = 0; j < n; ++j) a[j] = make_j(j);
+  return launch_round(h, a, n, width, st);
+}
 // learners with lazily maintained fp32 packs (fresh32)
 extern std::mutex g_lazy_mu;
 extern std::vector<oprl_learner*> g_lazy;

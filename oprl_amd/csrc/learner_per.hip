@@ -1,7 +1,7 @@
 // learner_per.hip — training from prioritized replay ("Training from it"): the entry points
-// oprl_learner_update_weighted and oprl_learner_step_n_prio.  Host code only.  The update itself is learner.hip's: the
-// weights travel down in the update's StepRows and critic_phase's step 3 becomes forward | k_td_weighted_seed | backward
-// (weighted_critic_step); everything else of the update is untouched.
+// oprl_learner_update_weighted and oprl_learner_step_n_prio.  Host code only.  The update itself is the generic sequence's: the
+// weights travel down in the update's StepRows and its step 3 becomes forward | k_td_weighted_seed | backward
+// (learner_modes.hip weighted_critic_step, which also holds per_alloc); everything else of the update is untouched.
 #include "learner_internal.h"
 #include "replay_internal.h"
 
@@ -26,11 +26,11 @@ int per_check(const oprl_learner* h, const char* who) {
     return OPRL_ERR_STATE;
   }
   if (h->group_member) { set_err("%s: the learner is a member of a group (packed learners gather their own rows)", who); return OPRL_ERR_STATE; }
-  if (h->iql_on) {
+  if (h->iql.on) {
     set_err("%s: the learner's implicit-Q-learning mode is on (oprl_learner_set_iql), whose value and actor steps take no importance weights", who);
     return OPRL_ERR_STATE;
   }
-  if (h->cql_n > 0) {
+  if (h->cql.n > 0) {
     set_err("%s: the learner's conservative-Q-learning mode is on (oprl_learner_set_cql), whose penalty takes no importance weights", who);
     return OPRL_ERR_STATE;
   }
@@ -38,20 +38,6 @@ int per_check(const oprl_learner* h, const char* who) {
     set_err("%s: the learner's fused launch form is on, which applies no importance weights; create it with no_fuse", who);
     return OPRL_ERR_STATE;
   }
-  return OPRL_OK;
-}
-
-// the weighted seeds [nc][Bmax] | step_n_prio's weights [Bmax] | |TD| [Bmax] | slots [Bmax]: one allocation, on first use
-int per_alloc(oprl_learner* h) {
-  if (h->per_seed != nullptr) return OPRL_OK;
-  const size_t Bm = (size_t)h->Bmax, n = ((size_t)h->nc + 3) * Bm;
-  float* p = nullptr;
-  if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) { set_err("hipMalloc(%zu) failed (prioritized training rows)", n * sizeof(float)); return OPRL_ERR_NOMEM; }
-  HIPC(hipMemset(p, 0, n * sizeof(float)));
-  h->per_seed = p;
-  h->per_w = p + (size_t)h->nc * Bm;
-  h->per_td = h->per_w + Bm;
-  h->per_slots = reinterpret_cast<int*>(h->per_td + Bm);
   return OPRL_OK;
 }
 
@@ -98,9 +84,9 @@ extern "C" int oprl_learner_step_n_prio(oprl_learner* h, oprl_replay* replay, in
   for (int k = 0; k < K; ++k) {
     const uint64_t u = (uint64_t)h->update_count;
     const double beta = std::min(1.0, beta0 + (1.0 - beta0) * (double)u / beta_steps);
-    RC(oprl_replay_prio_sample(replay, B, seed, u, beta, h->bs, h->ba, h->br, h->bd, h->bs2, h->per_slots, h->per_w, stream));
-    RC(weighted_update(h, h->bs, h->ba, h->br, h->bd, h->bs2, h->per_w, B, nullptr, nullptr, h->per_td, stream));
-    RC(oprl_replay_prio_update(replay, B, h->per_slots, h->per_td, stream));
+    RC(oprl_replay_prio_sample(replay, B, seed, u, beta, h->bs, h->ba, h->br, h->bd, h->bs2, h->per.slots, h->per.w, stream));
+    RC(weighted_update(h, h->bs, h->ba, h->br, h->bd, h->bs2, h->per.w, B, nullptr, nullptr, h->per.td, stream));
+    RC(oprl_replay_prio_update(replay, B, h->per.slots, h->per.td, stream));
   }
   return OPRL_OK;
 }

@@ -1,5 +1,5 @@
 // net_rounds.hip — how the net passes of the generic (per-net) launch sequence go out.  Host code only.
-// learner.hip builds the arguments of a round — the n equal nets of one pass: twin critics, TQC's quantile critics, REDQ's
+// learner_generic.hip builds the arguments of a round — the n equal nets of one pass: twin critics, TQC's quantile critics, REDQ's
 // ensemble or its target subset — and launch_round decides the launches from that list.  No state of an earlier call is
 // read, except the offers TQC's riders make to the layer-by-layer round (learner_internal.h: *_pending / *_done).
 #include "learner_internal.h"
@@ -38,17 +38,11 @@ int launch_pair(oprl_learner* h, MlpArgs* a, int width, hipStream_t st) {
     }
   }
   if (n_tp == 2 && tp[0]->B == tp[1]->B) {
-    prof_begin(0, st);
-    hipError_t e = launch_mlp_slice_tp2(*tp[0], *tp[1], h->n_cus, st);
-    prof_end(st);
-    HIPC(e);
+    RC(profiled(0, st, [&] { return launch_mlp_slice_tp2(*tp[0], *tp[1], h->n_cus, st); }));
     return OPRL_OK;
   }
   for (int k = 0; k < n_tp; ++k) {
-    prof_begin(0, st);
-    hipError_t e = launch_mlp_slice_tp(*tp[k], st);
-    prof_end(st);
-    HIPC(e);
+    RC(profiled(0, st, [&] { return launch_mlp_slice_tp(*tp[k], st); }));
   }
   return OPRL_OK;
 }
@@ -66,13 +60,13 @@ int launch_layerwise_round(oprl_learner* h, MlpArgs* a, int n, int width, hipStr
     for (int k = 0; k < n; ++k)
       for (int l = 1; l + 1 < a[k].net.n_layers; ++l) { a[k].net.pf[l] = a[k].pf16[l]; if (a[k].pb16[l]) a[k].net.pb[l] = a[k].pb16[l]; }
   prof_begin(0, st);
-  // a pending TD-target job (critic_phase) rides on this launch's heads when it is the target critics' forward
+  // a pending TD-target job (generic_critic_phase) rides on this launch's heads when it is the target critics' forward
   const TqcJob* job = nullptr;
   if (h->tqc_job_pending && !a[0].do_bwd && a[0].do_fwd && n == h->tqc_job.n_nets && a[0].out == h->tqc_job.z) {
     job = &h->tqc_job;
     h->tqc_job_pending = false;
   }
-  // a pending rider (critic_phase: the actor's forward on s) goes with the storing launch's heads
+  // a pending rider (generic_critic_phase: the actor's forward on s) goes with the storing launch's heads
   const MlpArgs* rider = nullptr;
   if (h->rider_pending && a[0].do_bwd && a[0].do_fwd && mlp_layerwise_rider_ok(a, n, h->rider, h->n_cus)) {
     rider = &h->rider;
@@ -88,7 +82,7 @@ int launch_layerwise_round(oprl_learner* h, MlpArgs* a, int n, int width, hipStr
   const MlpArgs* tail = nullptr;
   int tail0 = 0;
   if (h->fin_tail0 >= 0 && !a[0].do_bwd && a[0].do_fwd) {
-    const int slices = (a[0].B + kR - 1) / kR;
+    const int slices = n_slices(a[0].B);
     const int rest = h->nc - h->fin_tail0;
     if (mlp_layerwise_fin_fit(h->fin_args, h->nc, slices * n, h->n_cus) >= rest) {   // all resident at once
       tail = h->fin_args; tail0 = h->fin_tail0;
@@ -155,10 +149,7 @@ int launch_few(oprl_learner* h, MlpArgs* a, int n, int width, hipStream_t st) {
     for (int k = 0; k < m; ++k) RC(launch(a[k], width, st));
     return OPRL_OK;
   }
-  prof_begin(0, st);
-  hipError_t e = launch_mlp_slice_multi(a, m, width, st);
-  prof_end(st);
-  HIPC(e);
+  RC(profiled(0, st, [&] { return launch_mlp_slice_multi(a, m, width, st); }));
   return OPRL_OK;
 }
 
@@ -168,10 +159,7 @@ int launch(const MlpArgs& a0, int width, hipStream_t st) {
   MlpArgs a = a0;
   const bool tp = takes_cluster(a, width);
   if (tp) RC(draw_tag(a, st));
-  prof_begin(0, st);
-  hipError_t e = tp ? launch_mlp_slice_tp(a, st) : launch_mlp_slice(a, width, st);
-  prof_end(st);
-  HIPC(e);
+  RC(profiled(0, st, [&] { return tp ? launch_mlp_slice_tp(a, st) : launch_mlp_slice(a, width, st); }));
   return OPRL_OK;
 }
 

@@ -44,15 +44,25 @@ CASES = [
     # the weighted critic step: forward | seed kernel | backward per grouping
     ("ddpg-prioritized", "ddpg", dict(prioritized=True), {}, "weighted"),
     ("td3-prioritized", "td3", dict(prioritized=True), {}, "weighted"),
+    # the learner's modes, all on the generic sequence: a seed kernel between a forward-only and a backward-only launch
+    ("d4pg", "d4pg", {}, {}, "update"),                                               # critic and actor step
+    ("td3bc", "td3bc", {}, {}, "update"),                                             # the actor step, with k_bc_mix behind it
+    ("iql", "iql", {}, {}, "update"),                                                 # V's step and dW launch, k_iql_actor_seed
+    ("cql", "cql", dict(cql_n_actions=2, batch_size=B), {}, "update"),                # the critic step on B (1 + 3 N) = 448 rows
+    ("calql", "calql", dict(cql_n_actions=2, batch_size=B), {}, "returns"),           # ... with returns-to-go to update()
 ]
+# algorithms whose module and class are not `name` and `name.upper()`
+CLASSES = {"td3bc": ("td3_bc", "TD3BC"), "calql": ("calql", "CalQL")}
 
 
 def make_algo(name, kw):
-    """(the environment switches are read once, at create: the caller sets them around this call)"""
+    """(the environment switches are read once, at create: the caller sets them around this call; CQL.create raises
+    max_batch to its wide rows itself)"""
     import importlib
     from oprl_amd.logging import NullLogger
-    cls = getattr(importlib.import_module(f"oprl_amd.algos.{name}"), name.upper())
-    extra = {} if name == "ddpg" else dict(log_every=10 ** 9)
+    module, cls_name = CLASSES.get(name, (name, name.upper()))
+    cls = getattr(importlib.import_module(f"oprl_amd.algos.{module}"), cls_name)
+    extra = {} if name in ("ddpg", "d4pg") else dict(log_every=10 ** 9)
     t.manual_seed(0)
     algo = cls(logger=NullLogger(), state_dim=S, action_dim=A, device="cuda", max_batch=B, **extra, **kw).create()
     algo.set_seed(7, 0)
@@ -87,7 +97,8 @@ def run_case(case):
     for k in range(K):
         g = t.Generator().manual_seed(500 + k)
         rows = [x.cuda() for x in fx.make_batch(100 + k, B, S, A)]
-        batches.append((rows, (0.05 + 0.95 * t.rand(B, 1, generator=g)).cuda()))
+        w = (0.05 + 0.95 * t.rand(B, 1, generator=g)).cuda()
+        batches.append((rows, w, (20.0 * t.rand(B, 1, generator=g) - 10.0).cuda()))
     t.cuda.synchronize()
     cnt, ms = (C.c_int64 * KINDS)(), (C.c_double * KINDS)()
     lib.oprl_profile_enable(1)
@@ -96,8 +107,8 @@ def run_case(case):
         if how == "step_n":
             algo.learner.step_n(replay.handle, K, B, seed=5)
         else:
-            for rows, w in batches:
-                algo.update(*rows, **(dict(weights=w) if how == "weighted" else {}))
+            for rows, w, ret in batches:
+                algo.update(*rows, **(dict(weights=w) if how == "weighted" else dict(returns=ret) if how == "returns" else {}))
         assert lib.oprl_profile_read(cnt, ms, 1) == 0
     finally:
         lib.oprl_profile_enable(0)
