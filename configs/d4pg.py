@@ -1,4 +1,4 @@
-"""D4PG on the MI355X learner — DDPG with a categorical critic (Barth-Maron et al. 2018); written like configs/ddpg.py.
+"""D4PG on the MI355X learner — DDPG with a categorical critic (Barth-Maron et al. 2018); its body is configs/_common.py's ``TrainingScript``.
 Defaults: 41 atoms from -150 to 150.  ``--n-step 3`` gives the paper's multi-step targets, ``--num-envs N`` its many
 actors (``--open-episodes``: one open replay episode per environment); ``--per`` is refused.
 

@@ -21,6 +21,7 @@ from oprl_amd.algos.nn_models import MLP, flatten_module_, is_flat
 
 class OffPolicyAlgorithm(ABC):
     _created: bool = False
+    updates_per_request = 1      # updates update_from_buffer runs per update asked of it (REDQ: its update-to-data ratio)
 
     def check_created(self) -> None:
         if not self._created:
@@ -31,8 +32,23 @@ class OffPolicyAlgorithm(ABC):
     def get_policy_state_dict(self) -> dict[str, Any]:
         return self.actor.state_dict()
 
+    @property
+    def update_step(self) -> int:
+        return self.learner.update_count if self._created else 0
+
     def _log_update(self, step: int) -> None:
         """Scalar logging at the algorithm's cadence (the only host sync of an update)."""
+
+    def _dispatch_update(self, state, action, reward, done, next_state, weights, noise0, noise1) -> None:
+        """One logged update, weighted when ``weights`` ([B] or [B, 1], a prioritized batch's) are given: the rows' |TD|
+        is then left in ``last_td_abs`` (device tensor)."""
+        step = self.update_step
+        if weights is not None:
+            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights,
+                                                            noise0=noise0, noise1=noise1)
+        else:
+            self.learner.update(state, action, reward, done, next_state, noise0=noise0, noise1=noise1)
+        self._log_update(step)
 
     def update_from_buffer(self, replay_buffer, batch_size: int, act_next=None, n_updates: int = 1) -> None:
         """``update(*replay_buffer.sample(batch_size))`` as ONE C call (oprl_learner_step_n with
@@ -51,12 +67,15 @@ class OffPolicyAlgorithm(ABC):
         ``actor.explore_rows(act_next)`` collects them.  ``n_updates`` > 1 without ``act_next``: one ``step_n(K)``.
 
         A ``prioritized`` algorithm over a prioritized buffer: one ``step_n_prio`` call instead (draw by priority,
-        weighted update, new priorities); ``act_next`` is accepted but rides nowhere, ``explore`` runs its own forward."""
+        weighted update, new priorities); ``act_next`` is accepted but rides nowhere, ``explore`` runs its own forward.
+
+        Everywhere above K is ``n_updates x updates_per_request``."""
         refuse_prioritized(self, replay_buffer)
         check_nstep_gamma(self, replay_buffer)
         K = int(n_updates)
         if K < 1:
             raise ValueError(f"n_updates={n_updates!r}: at least one update")
+        K *= self.updates_per_request
         if trains_prioritized(self, replay_buffer):
             step = self.update_step
             step_prioritized(self, replay_buffer, K, batch_size)
@@ -138,6 +157,30 @@ def check_prioritized_config(algo) -> None:
                          "prioritized training)")
 
 
+def check_mode_config(algo, name: str, f32_only: str, uniform_only: str | None = None) -> None:
+    """What the learner refuses of an algorithm that runs as a mode of another's learner, or on the generic launch
+    sequence alone, said before anything touches the GPU: a precision other than f32 (``f32_only`` says what needs it),
+    gradient export and, where ``uniform_only`` says why, prioritized replay."""
+    if algo.precision != "f32":
+        if algo.precision not in _capi.PRECISION:
+            raise ValueError(f"precision={algo.precision!r}: expected one of {sorted(_capi.PRECISION)}")
+        raise ValueError(f"{name}: precision={algo.precision!r} unsupported (f32 only: {f32_only})")
+    if algo.export_grads:
+        raise ValueError(f"{name}: export_grads (data-parallel learners) unsupported")
+    if uniform_only is not None and algo.prioritized:
+        raise ValueError(f"{name}(prioritized=True): prioritized replay through {name} is not built ({uniform_only})")
+
+
+class Temperature:
+    """``alpha`` of the algorithms with an entropy temperature (SAC, REDQ and what derives from them)."""
+
+    @property
+    def alpha(self) -> float:
+        if self.log_alpha is not None:
+            return float(self.log_alpha.exp().item())
+        return self.alpha_init
+
+
 def trains_prioritized(algo, replay_buffer) -> bool:
     """A prioritized algorithm over a prioritized buffer with its tree on the device: the weighted path.  (A prioritized
     algorithm over a plain buffer trains uniformly through the plain path.)"""
@@ -182,6 +225,23 @@ def require_gpu(device: str) -> t.device:
         raise RuntimeError("no GPU visible to torch; the oprl_amd learner has no CPU path")
     _capi.load()
     return dev if dev.index is not None else t.device("cuda", t.cuda.current_device())
+
+
+def _fill_net(dst: _capi.OprlNet, mlp: MLP, target: MLP | None, arena: t.Tensor, m: t.Tensor, v: t.Tensor,
+              g: t.Tensor | None = None) -> None:
+    """The descriptor of ``mlp``, whose parameters lie inside ``arena``; ``m``, ``v`` and ``g`` (Adam's moments, the
+    exported gradient) are laid out like the arena."""
+    o = mlp.theta_ptr() - arena.data_ptr()
+    dst.n_layers = len(mlp.dims) - 1
+    for i, x in enumerate(mlp.dims):
+        dst.dims[i] = x
+    dst.theta = mlp.theta_ptr()
+    dst.theta_target = target.theta_ptr() if target is not None else None
+    dst.pack = mlp.pack_tensor().data_ptr()
+    dst.pack_target = target.pack_tensor().data_ptr() if target is not None else None
+    dst.adam_m = m.data_ptr() + o
+    dst.adam_v = v.data_ptr() + o
+    dst.grad = (g.data_ptr() + o) if g is not None else None
 
 
 class HipLearner:
@@ -235,26 +295,9 @@ class HipLearner:
         cfg.export_grads = int(export_grads)
         cfg.no_fuse = int(no_fuse)
 
-        def off(arena: t.Tensor, mlp: MLP) -> int:
-            return mlp.theta_ptr() - arena.data_ptr()
-
-        def fill(dst: _capi.OprlNet, mlp: MLP, target: MLP | None, arena, m, v, g):
-            o = off(arena, mlp)
-            dst.n_layers = len(mlp.dims) - 1
-            for i, x in enumerate(mlp.dims):
-                dst.dims[i] = x
-            dst.theta = mlp.theta_ptr()
-            dst.theta_target = target.theta_ptr() if target is not None else None
-            dst.pack = mlp.pack_tensor().data_ptr()
-            dst.pack_target = target.pack_tensor().data_ptr() if target is not None else None
-            dst.adam_m = m.data_ptr() + o
-            dst.adam_v = v.data_ptr() + o
-            dst.grad = (g.data_ptr() + o) if g is not None else None
-
-        fill(cfg.actor, actor_mlp, actor_target_mlp, self.actor_arena, self.actor_m, self.actor_v,
-             self.actor_grad)
+        _fill_net(cfg.actor, actor_mlp, actor_target_mlp, self.actor_arena, self.actor_m, self.actor_v, self.actor_grad)
         for j, (c, ct) in enumerate(zip(critic_mlps, critic_target_mlps)):
-            fill(cfg.critics[j], c, ct, self.critic_arena, self.critic_m, self.critic_v, self.critic_grad)
+            _fill_net(cfg.critics[j], c, ct, self.critic_arena, self.critic_m, self.critic_v, self.critic_grad)
         if log_alpha is not None:
             cfg.log_alpha = log_alpha.data_ptr()
             cfg.log_alpha_m = self.log_alpha_m.data_ptr()
@@ -404,11 +447,21 @@ class HipLearner:
 
         return B, f(state, self.S), f(action, self.A), f(reward, 1), f(done, 1), f(next_state, self.S)
 
+    def _noise(self, x, B):
+        """An injected normal draw as the kernels read it: float32 [B, A] on the device (``None``: Philox)."""
+        return None if x is None else x.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+
+    def _per_row(self, x, B, noun: str) -> t.Tensor:
+        """One number per row of the batch (``noun``: weights, returns), [B] or [B, 1], as float32 [B] on the device."""
+        x = t.as_tensor(x).to(device=self.device, dtype=t.float32).reshape(-1).contiguous()
+        if x.numel() != B:
+            raise ValueError(f"{x.numel()} {noun} for a batch of {B}")
+        return x
+
     def update(self, state, action, reward, done, next_state, noise0=None, noise1=None) -> None:
         self.check_bound()
         B, s, a, r, d, s2 = self._prep(state, action, reward, done, next_state)
-        n0 = None if noise0 is None else noise0.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
-        n1 = None if noise1 is None else noise1.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        n0, n1 = self._noise(noise0, B), self._noise(noise1, B)
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_update(
                 self.handle, _capi.ptr(s), _capi.ptr(a), _capi.ptr(r), _capi.ptr(d), _capi.ptr(s2), B,
@@ -419,11 +472,8 @@ class HipLearner:
         |TD| (mean over the critics) as a device tensor [B] (oprl_learner_update_weighted)."""
         self.check_bound()
         B, s, a, r, d, s2 = self._prep(state, action, reward, done, next_state)
-        w = t.as_tensor(weights).to(device=self.device, dtype=t.float32).reshape(-1).contiguous()
-        if w.numel() != B:
-            raise ValueError(f"{w.numel()} weights for a batch of {B}")
-        n0 = None if noise0 is None else noise0.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
-        n1 = None if noise1 is None else noise1.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        w = self._per_row(weights, B, "weights")
+        n0, n1 = self._noise(noise0, B), self._noise(noise1, B)
         td = t.empty(B, dtype=t.float32, device=self.device)
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_update_weighted(
@@ -434,8 +484,7 @@ class HipLearner:
     def update_phase(self, phase, state, action, reward, done, next_state, noise0=None, noise1=None):
         self.check_bound()
         B, s, a, r, d, s2 = self._prep(state, action, reward, done, next_state)
-        n0 = None if noise0 is None else noise0.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
-        n1 = None if noise1 is None else noise1.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        n0, n1 = self._noise(noise0, B), self._noise(noise1, B)
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_update_phase(
                 self.handle, phase, _capi.ptr(s), _capi.ptr(a), _capi.ptr(r), _capi.ptr(d), _capi.ptr(s2),
@@ -530,14 +579,17 @@ class HipLearner:
         _capi.check(self.lib.oprl_learner_set_seed(self.handle, int(seed) & (2 ** 64 - 1), int(rank)),
                     "oprl_learner_set_seed")
 
-    def read_scalars(self) -> dict[str, float]:
-        buf = (C.c_float * 10)()
+    def _read(self, fn_name: str, n: int, keys, *size) -> dict[str, float]:
+        """``keys`` over the first floats of the ``n`` that the library's ``fn_name`` writes (``size``: its count
+        argument, where it takes one)."""
+        buf = (C.c_float * n)()
         with _capi.on_device(self.device):
-            _capi.check(self.lib.oprl_learner_read_scalars(self.handle, buf, 10, _capi.current_stream()),
-                        "oprl_learner_read_scalars")
-        keys = ("critic_loss", "actor_loss", "q_mean", "q_target_mean", "alpha", "update_step",
-                "q1_mean", "log_pi_mean", "gauss_actor_loss", "alpha_loss")
+            _capi.check(getattr(self.lib, fn_name)(self.handle, buf, *size, _capi.current_stream()), fn_name)
         return dict(zip(keys, (float(x) for x in buf)))
+
+    def read_scalars(self) -> dict[str, float]:
+        return self._read("oprl_learner_read_scalars", 10, ("critic_loss", "actor_loss", "q_mean", "q_target_mean", "alpha",
+                          "update_step", "q1_mean", "log_pi_mean", "gauss_actor_loss", "alpha_loss"), 10)
 
     def set_bc(self, alpha: float) -> None:
         """The behaviour-cloning mode of a TD3 learner's actor step (oprl_learner_set_bc; TD3+BC):
@@ -548,10 +600,7 @@ class HipLearner:
     def read_bc(self) -> dict[str, float]:
         """lambda, mean |Q1(s, pi(s))| and the mean squared pi(s) - a of the last actor step with the mode on
         (oprl_learner_read_bc)."""
-        buf = (C.c_float * 4)()
-        with _capi.on_device(self.device):
-            _capi.check(self.lib.oprl_learner_read_bc(self.handle, buf, _capi.current_stream()), "oprl_learner_read_bc")
-        return {"bc_lambda": float(buf[0]), "q_abs_mean": float(buf[1]), "bc_mse": float(buf[2])}
+        return self._read("oprl_learner_read_bc", 4, ("bc_lambda", "q_abs_mean", "bc_mse"))
 
     def set_cql(self, cql_alpha: float, n_actions: int) -> None:
         """The conservative-Q-learning mode of a SAC learner's critic step (oprl_learner_set_cql; CQL, DESIGN.md section
@@ -562,11 +611,8 @@ class HipLearner:
     def read_cql(self) -> dict[str, float]:
         """Of the last update with the mode on, per critic: the mean of logsumexp - Q(s, a), the mean Q on the uniform
         actions and on the actions drawn from pi(.|s); and the penalty term of the loss (oprl_learner_read_cql)."""
-        buf = (C.c_float * 8)()
-        with _capi.on_device(self.device):
-            _capi.check(self.lib.oprl_learner_read_cql(self.handle, buf, _capi.current_stream()), "oprl_learner_read_cql")
-        keys = ("gap1", "gap2", "q_rand1", "q_rand2", "q_pi1", "q_pi2", "penalty", "bound_rate")
-        return dict(zip(keys, (float(x) for x in buf)))
+        return self._read("oprl_learner_read_cql", 8, ("gap1", "gap2", "q_rand1", "q_rand2", "q_pi1", "q_pi2", "penalty",
+                                                       "bound_rate"))
 
     def set_cql_noise(self, eps: t.Tensor | None, uni: t.Tensor | None) -> None:
         """Test hook (oprl_learner_set_cql_noise): device arrays standing in for the mode's normal draws [B, 2N, A] and
@@ -587,11 +633,8 @@ class HipLearner:
         """One update with the rows' returns-to-go ``returns`` ([B] or [B, 1]; oprl_learner_update_calql)."""
         self.check_bound()
         B, s, a, r, d, s2 = self._prep(state, action, reward, done, next_state)
-        g = t.as_tensor(returns).to(device=self.device, dtype=t.float32).reshape(-1).contiguous()
-        if g.numel() != B:
-            raise ValueError(f"{g.numel()} returns for a batch of {B}")
-        n0 = None if noise0 is None else noise0.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
-        n1 = None if noise1 is None else noise1.to(device=self.device, dtype=t.float32).reshape(B, self.A).contiguous()
+        g = self._per_row(returns, B, "returns")
+        n0, n1 = self._noise(noise0, B), self._noise(noise1, B)
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_update_calql(
                 self.handle, _capi.ptr(s), _capi.ptr(a), _capi.ptr(r), _capi.ptr(d), _capi.ptr(s2), _capi.ptr(g), B,
@@ -615,12 +658,7 @@ class HipLearner:
         m = self.value_m if same else t.zeros_like(arena)
         v = self.value_v if same else t.zeros_like(arena)
         desc = _capi.OprlNet()
-        desc.n_layers = len(value_mlp.dims) - 1
-        for i, x in enumerate(value_mlp.dims):
-            desc.dims[i] = x
-        desc.theta = value_mlp.theta_ptr()
-        desc.pack = value_mlp.pack_tensor().data_ptr()
-        desc.adam_m, desc.adam_v = m.data_ptr(), v.data_ptr()
+        _fill_net(desc, value_mlp, None, arena, m, v)
         with _capi.on_device(self.device):
             _capi.check(self.lib.oprl_learner_set_iql(self.handle, C.byref(desc), float(expectile), float(beta),
                                                       float(adv_clip), float(lr_value)), "oprl_learner_set_iql")
@@ -635,11 +673,7 @@ class HipLearner:
     def read_iql(self) -> dict[str, float]:
         """Of the last update with the mode on: the V loss, mean V(s), mean advantage u, mean weight w, the share of rows
         at the clip and the weighted cloning loss (oprl_learner_read_iql)."""
-        buf = (C.c_float * 8)()
-        with _capi.on_device(self.device):
-            _capi.check(self.lib.oprl_learner_read_iql(self.handle, buf, _capi.current_stream()), "oprl_learner_read_iql")
-        keys = ("v_loss", "v_mean", "adv_mean", "w_mean", "clip_frac", "actor_loss")
-        return dict(zip(keys, (float(x) for x in buf)))
+        return self._read("oprl_learner_read_iql", 8, ("v_loss", "v_mean", "adv_mean", "w_mean", "clip_frac", "actor_loss"))
 
     @property
     def value_step(self) -> int:

@@ -15,7 +15,7 @@ from __future__ import annotations
 import math
 from dataclasses import dataclass
 
-from oprl_amd import _capi
+from oprl_amd.algos.base_algorithm import check_mode_config
 from oprl_amd.algos.sac import SAC
 
 MAX_ACTIONS = 16       # kCqlMaxActions (csrc/cql_seed.h): 3 N <= 48 entries per row
@@ -55,16 +55,8 @@ def wide_rows(batch_size: int, n_actions: int) -> int:
 
 def check_config(algo: CQL) -> None:
     """What the learner would refuse, said before anything touches the GPU."""
-    if algo.precision != "f32":
-        if algo.precision not in _capi.PRECISION:
-            raise ValueError(f"precision={algo.precision!r}: expected one of {sorted(_capi.PRECISION)}")
-        raise ValueError(f"CQL: precision={algo.precision!r} unsupported (f32 only: the mode runs the generic launch "
-                         "sequence)")
-    if algo.export_grads:
-        raise ValueError("CQL: export_grads (data-parallel learners) unsupported")
-    if algo.prioritized:
-        raise ValueError("CQL(prioritized=True): prioritized replay through CQL is not built (no importance weights "
-                         "in the penalty; a fixed dataset is sampled uniformly)")
+    check_mode_config(algo, "CQL", "the mode runs the generic launch sequence",
+                      "no importance weights in the penalty; a fixed dataset is sampled uniformly")
     try:
         ca = float(algo.cql_alpha)
     except (TypeError, ValueError):

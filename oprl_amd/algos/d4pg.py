@@ -17,9 +17,8 @@ from dataclasses import dataclass, field
 import torch as t
 from torch import nn
 
-from oprl_amd import _capi
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, require_gpu
-from oprl_amd.algos.nn_functions import disable_gradient
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_mode_config, require_gpu
+from oprl_amd.algos.nn_functions import make_target_
 from oprl_amd.algos.nn_models import CategoricalCritic, DeterministicPolicy, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
 from oprl_amd.logging import LoggerProtocol
@@ -76,12 +75,8 @@ class D4PG(OffPolicyAlgorithm):
         self.critic, self.critic_target = critic(), critic()
         for m in (self.actor, self.actor_target, self.critic, self.critic_target):
             flatten_module_(m)
-        for src, dst in ((self.actor, self.actor_target), (self.critic, self.critic_target)):
-            dst._oprl_arena.copy_(src._oprl_arena)
-            for m in dst.modules():
-                if hasattr(m, "mark_dirty"):
-                    m.mark_dirty()
-            disable_gradient(dst)
+        make_target_(self.actor_target, self.actor)
+        make_target_(self.critic_target, self.critic)
         hp = dict(gamma=self.gamma, tau=self.tau, lr_actor=self.lr_actor, lr_critic=self.lr_critic,
                   beta1=0.9, beta2=0.999, adam_eps=1e-8, max_action=self.max_action, policy_freq=1,
                   v_min=float(self.v_min), v_max=float(self.v_max))
@@ -94,10 +89,6 @@ class D4PG(OffPolicyAlgorithm):
             hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, no_fuse=True, precision=self.precision)
         self._created = True
         return self
-
-    @property
-    def update_step(self) -> int:
-        return self.learner.update_count if self._created else 0
 
     def update(self, state: t.Tensor, action: t.Tensor, reward: t.Tensor, done: t.Tensor, next_state: t.Tensor) -> None:
         self.learner.update(state, action, reward, done, next_state)
@@ -113,9 +104,4 @@ def check_config(algo: D4PG) -> None:
                          f"engine's narrow outputs, at most {MAX_ATOMS} columns)")
     if not float(algo.v_max) > float(algo.v_min):
         raise ValueError(f"D4PG: v_max={algo.v_max} is not above v_min={algo.v_min}")
-    if algo.precision != "f32":
-        if algo.precision not in _capi.PRECISION:
-            raise ValueError(f"precision={algo.precision!r}: expected one of {sorted(_capi.PRECISION)}")
-        raise ValueError(f"D4PG: precision={algo.precision!r} unsupported (f32 only: the generic launch sequence)")
-    if algo.export_grads:
-        raise ValueError("D4PG: export_grads (data-parallel learners) unsupported")
+    check_mode_config(algo, "D4PG", "the generic launch sequence")

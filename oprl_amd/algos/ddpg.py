@@ -13,7 +13,7 @@ import torch as t
 from torch import nn
 
 from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_prioritized_config, require_gpu
-from oprl_amd.algos.nn_functions import disable_gradient
+from oprl_amd.algos.nn_functions import make_target_
 from oprl_amd.algos.nn_models import Critic, DeterministicPolicy, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
 from oprl_amd.logging import LoggerProtocol
@@ -61,16 +61,8 @@ class DDPG(OffPolicyAlgorithm):
         self.critic_target = Critic(self.state_dim, self.action_dim).to(dev)
         for m in (self.actor, self.actor_target, self.critic, self.critic_target):
             flatten_module_(m)
-        self.actor_target._oprl_arena.copy_(self.actor._oprl_arena)
-        for m in self.actor_target.modules():
-            if hasattr(m, "mark_dirty"):
-                m.mark_dirty()
-        self.critic_target._oprl_arena.copy_(self.critic._oprl_arena)
-        for m in self.critic_target.modules():
-            if hasattr(m, "mark_dirty"):
-                m.mark_dirty()
-        disable_gradient(self.actor_target)
-        disable_gradient(self.critic_target)
+        make_target_(self.actor_target, self.actor)
+        make_target_(self.critic_target, self.critic)
         hp = dict(gamma=self.gamma, tau=self.tau, lr_actor=self.lr_actor, lr_critic=self.lr_critic,
                   beta1=0.9, beta2=0.999, adam_eps=1e-8, max_action=self.max_action, policy_freq=1)
         self.learner = HipLearner(
@@ -82,10 +74,6 @@ class DDPG(OffPolicyAlgorithm):
             hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
         self._created = True
         return self
-
-    @property
-    def update_step(self) -> int:
-        return self.learner.update_count if self._created else 0
 
     def update(
         self,

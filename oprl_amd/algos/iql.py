@@ -18,7 +18,7 @@ from dataclasses import dataclass, field
 
 from torch import nn
 
-from oprl_amd import _capi
+from oprl_amd.algos.base_algorithm import check_mode_config
 from oprl_amd.algos.nn_models import MLP, flatten_module_
 from oprl_amd.algos.td3 import TD3
 
@@ -60,16 +60,8 @@ class IQL(TD3):
 
 def check_config(algo: IQL) -> None:
     """What the learner would refuse, said before anything touches the GPU."""
-    if algo.precision != "f32":
-        if algo.precision not in _capi.PRECISION:
-            raise ValueError(f"precision={algo.precision!r}: expected one of {sorted(_capi.PRECISION)}")
-        raise ValueError(f"IQL: precision={algo.precision!r} unsupported (f32 only: the mode runs the generic launch "
-                         "sequence)")
-    if algo.export_grads:
-        raise ValueError("IQL: export_grads (data-parallel learners) unsupported")
-    if algo.prioritized:
-        raise ValueError("IQL(prioritized=True): prioritized replay through IQL is not built (no importance weights "
-                         "in the value and actor steps; a fixed dataset is sampled uniformly)")
+    check_mode_config(algo, "IQL", "the mode runs the generic launch sequence",
+                      "no importance weights in the value and actor steps; a fixed dataset is sampled uniformly")
     if int(algo.policy_freq) != 1:
         raise ValueError(f"IQL: policy_freq={algo.policy_freq!r}; the actor steps on every update (policy_freq=1)")
     tau, beta, clip, lr = (float(x) for x in (algo.expectile, algo.beta, algo.adv_clip, algo.lr_value))

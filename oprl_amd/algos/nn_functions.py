@@ -34,3 +34,14 @@ def soft_update(target: nn.Module, source: nn.Module, tau: float) -> None:
 def disable_gradient(network: nn.Module) -> None:
     for param in network.parameters():
         param.requires_grad = False
+
+
+def make_target_(target: nn.Module, source: nn.Module, freeze: bool = True) -> None:
+    """Make the flat ``target`` the target twin of the flat ``source``: the same parameter values, and no gradient
+    when ``freeze``.  (Train or eval mode stays the caller's choice.)"""
+    target._oprl_arena.copy_(source._oprl_arena)
+    for m in target.modules():       # the master changed behind torch's back
+        if hasattr(m, "mark_dirty"):
+            m.mark_dirty()
+    if freeze:
+        disable_gradient(target)

@@ -16,14 +16,12 @@ from __future__ import annotations
 import math
 from dataclasses import dataclass, field
 
-import numpy as np
 import torch as t
 from torch import nn
 
 from oprl_amd import _capi
-from oprl_amd.algos.base_algorithm import (HipLearner, OffPolicyAlgorithm, check_nstep_gamma, check_prioritized_config,
-                                            refuse_prioritized, require_gpu, step_prioritized, trains_prioritized)
-from oprl_amd.algos.nn_functions import disable_gradient
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, Temperature, check_prioritized_config, require_gpu
+from oprl_amd.algos.nn_functions import make_target_
 from oprl_amd.algos.nn_models import MLP, GaussianActor, _forward_sa, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
 from oprl_amd.logging import LoggerProtocol
@@ -46,7 +44,7 @@ class EnsembleCritic(nn.Module):
 
 
 @dataclass
-class REDQ(OffPolicyAlgorithm):
+class REDQ(Temperature, OffPolicyAlgorithm):
     logger: LoggerProtocol
     state_dim: int
     action_dim: int
@@ -89,11 +87,7 @@ class REDQ(OffPolicyAlgorithm):
         self.critic, self.critic_target = critic(), critic().eval()
         for m in (self.actor, self.critic, self.critic_target):
             flatten_module_(m)
-        self.critic_target._oprl_arena.copy_(self.critic._oprl_arena)
-        for m in self.critic_target.modules():
-            if hasattr(m, "mark_dirty"):
-                m.mark_dirty()
-        disable_gradient(self.critic_target)
+        make_target_(self.critic_target, self.critic)
         self.target_entropy = -float(self.action_dim)
         self.log_alpha = None
         if self.tune_alpha:
@@ -113,14 +107,11 @@ class REDQ(OffPolicyAlgorithm):
         return self
 
     @property
-    def alpha(self) -> float:
-        if self.log_alpha is not None:
-            return float(self.log_alpha.exp().item())
-        return self.alpha_init
-
-    @property
-    def update_step(self) -> int:
-        return self.learner.update_count if self._created else 0
+    def updates_per_request(self) -> int:
+        """``update_from_buffer`` runs ``utd_ratio`` updates per update asked of it, K = ``n_updates x utd_ratio`` in
+        all: one ``step_n(K)`` call; with ``act_next`` the actor's forward rides behind the last (``step_n(K - 1)`` +
+        ``step_act``, the same updates bit for bit), a 2-D ``act_next`` [N, S] as rows behind all K (``step_act_rows``)."""
+        return int(self.utd_ratio)
 
     def update(
         self,
@@ -138,53 +129,7 @@ class REDQ(OffPolicyAlgorithm):
         ``weights``: importance weights [B] or [B, 1] of a prioritized batch (critic loss only); the rows' |TD|, the
         mean over the ensemble, is left in ``last_td_abs`` (device tensor)."""
         n0, n1 = noise if noise is not None else (None, None)
-        step = self.update_step
-        if weights is not None:
-            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights, noise0=n0, noise1=n1)
-        else:
-            self.learner.update(state, action, reward, done, next_state, noise0=n0, noise1=n1)
-        self._log_update(step)
-
-    def update_from_buffer(self, replay_buffer, batch_size: int, act_next=None, n_updates: int = 1) -> None:
-        """``utd_ratio`` times ``update(*replay_buffer.sample(batch_size))`` as one ``step_n(K=utd_ratio)`` call.
-        ``act_next``: the actor's forward of it rides behind the last update (``step_n(K - 1)`` + ``step_act``, the
-        same updates bit for bit).  ``n_updates``: that many environment steps' worth, K = ``n_updates x utd_ratio``;
-        a 2-D ``act_next`` [N, S] rides as rows behind all K (one ``step_act_rows`` call)."""
-        refuse_prioritized(self, replay_buffer)
-        check_nstep_gamma(self, replay_buffer)
-        if int(n_updates) < 1:
-            raise ValueError(f"n_updates={n_updates!r}: at least one update")
-        K = int(n_updates) * int(self.utd_ratio)
-        if trains_prioritized(self, replay_buffer):      # (one step_n_prio call; act_next rides nowhere)
-            step = self.update_step
-            step_prioritized(self, replay_buffer, K, batch_size)
-            for u in range(step, step + K):
-                if u % self.log_every == 0:
-                    self._log_update(u)
-                    break
-            return
-        handle = getattr(replay_buffer, "handle", None)
-        if handle is None:
-            for _ in range(K):
-                self.update(*replay_buffer.sample(batch_size))
-            return
-        step = self.update_step
-        seed = int(getattr(replay_buffer, "seed", 0))
-        mlp = self._actor_mlp() if act_next is not None else None
-        if mlp is not None and np.ndim(act_next) == 2:
-            self.learner.step_act_rows(handle, K, int(batch_size), seed, act_next)
-            mlp.set_pending_rows(act_next, self.learner)
-        elif mlp is not None:
-            if K > 1:
-                self.learner.step_n(handle, K - 1, int(batch_size), seed=seed)
-            self.learner.step_act(handle, int(batch_size), seed, act_next)
-            mlp.set_pending(act_next, self.learner)
-        else:
-            self.learner.step_n(handle, K, int(batch_size), seed=seed)
-        for u in range(step, step + K):
-            if u % self.log_every == 0:
-                self._log_update(u)
-                break
+        self._dispatch_update(state, action, reward, done, next_state, weights, n0, n1)
 
     def _log_update(self, step: int) -> None:
         if step % self.log_every == 0:

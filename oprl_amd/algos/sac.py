@@ -10,15 +10,15 @@ from dataclasses import dataclass, field
 import torch as t
 from torch import nn
 
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_prioritized_config, require_gpu
-from oprl_amd.algos.nn_functions import disable_gradient
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, Temperature, check_prioritized_config, require_gpu
+from oprl_amd.algos.nn_functions import make_target_
 from oprl_amd.algos.nn_models import DoubleCritic, GaussianActor, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
 from oprl_amd.logging import LoggerProtocol
 
 
 @dataclass
-class SAC(OffPolicyAlgorithm):
+class SAC(Temperature, OffPolicyAlgorithm):
     logger: LoggerProtocol
     state_dim: int
     action_dim: int
@@ -56,11 +56,7 @@ class SAC(OffPolicyAlgorithm):
         self.critic, self.critic_target = critic(), critic().eval()
         for m in (self.actor, self.critic, self.critic_target):
             flatten_module_(m)
-        self.critic_target._oprl_arena.copy_(self.critic._oprl_arena)
-        for m in self.critic_target.modules():
-            if hasattr(m, "mark_dirty"):
-                m.mark_dirty()
-        disable_gradient(self.critic_target)
+        make_target_(self.critic_target, self.critic)
         self.log_alpha = None
         if self.tune_alpha:
             self.log_alpha = t.tensor(math.log(self.alpha_init), dtype=t.float64, device=dev)
@@ -80,16 +76,6 @@ class SAC(OffPolicyAlgorithm):
         self._created = True
         return self
 
-    @property
-    def alpha(self) -> float:
-        if self.log_alpha is not None:
-            return float(self.log_alpha.exp().item())
-        return self.alpha_init
-
-    @property
-    def update_step(self) -> int:
-        return self.learner.update_count if self._created else 0
-
     def update(
         self,
         state: t.Tensor,
@@ -106,12 +92,7 @@ class SAC(OffPolicyAlgorithm):
         ``weights``: importance weights [B] or [B, 1] of a prioritized batch (critic loss only); the rows' |TD| is
         left in ``last_td_abs`` (device tensor)."""
         n0, n1 = noise if noise is not None else (None, None)
-        step = self.update_step
-        if weights is not None:
-            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights, noise0=n0, noise1=n1)
-        else:
-            self.learner.update(state, action, reward, done, next_state, noise0=n0, noise1=n1)
-        self._log_update(step)
+        self._dispatch_update(state, action, reward, done, next_state, weights, n0, n1)
 
     def _log_update(self, step: int) -> None:
         if step % self.log_every == 0:

@@ -10,7 +10,7 @@ import torch as t
 from torch import nn
 
 from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, check_prioritized_config, require_gpu
-from oprl_amd.algos.nn_functions import disable_gradient
+from oprl_amd.algos.nn_functions import make_target_
 from oprl_amd.algos.nn_models import DeterministicPolicy, DoubleCritic, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
 from oprl_amd.logging import LoggerProtocol
@@ -64,16 +64,8 @@ class TD3(OffPolicyAlgorithm):
         self.critic, self.critic_target = critic(), critic().eval()
         for m in (self.actor, self.actor_target, self.critic, self.critic_target):
             flatten_module_(m)
-        self.actor_target._oprl_arena.copy_(self.actor._oprl_arena)
-        for m in self.actor_target.modules():
-            if hasattr(m, "mark_dirty"):
-                m.mark_dirty()
-        self.critic_target._oprl_arena.copy_(self.critic._oprl_arena)
-        for m in self.critic_target.modules():
-            if hasattr(m, "mark_dirty"):
-                m.mark_dirty()
-        disable_gradient(self.actor_target)
-        disable_gradient(self.critic_target)
+        make_target_(self.actor_target, self.actor)
+        make_target_(self.critic_target, self.critic)
         hp = dict(gamma=self.gamma, tau=self.tau, lr_actor=self.lr_actor, lr_critic=self.lr_critic,
                   beta1=0.9, beta2=0.999, adam_eps=1e-8, policy_noise=self.policy_noise,
                   noise_clip=self.noise_clip, max_action=self.max_action, policy_freq=self.policy_freq)
@@ -87,10 +79,6 @@ class TD3(OffPolicyAlgorithm):
             hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
         self._created = True
         return self
-
-    @property
-    def update_step(self) -> int:
-        return self.learner.update_count if self._created else 0
 
     def update(
         self,
@@ -107,12 +95,7 @@ class TD3(OffPolicyAlgorithm):
         ``randn_like(action)`` (td3.py:98); None draws it on device (Philox).
         ``weights``: importance weights [B] or [B, 1] of a prioritized batch; the rows' |TD| is left in
         ``last_td_abs`` (device tensor)."""
-        step = self.update_step
-        if weights is not None:
-            self.last_td_abs = self.learner.update_weighted(state, action, reward, done, next_state, weights, noise0=noise)
-        else:
-            self.learner.update(state, action, reward, done, next_state, noise0=noise)
-        self._log_update(step)
+        self._dispatch_update(state, action, reward, done, next_state, weights, noise, None)
 
     def _log_update(self, step: int) -> None:
         if step % self.log_every == 0:

@@ -14,7 +14,7 @@ from __future__ import annotations
 import math
 from dataclasses import dataclass
 
-from oprl_amd import _capi
+from oprl_amd.algos.base_algorithm import check_mode_config
 from oprl_amd.algos.td3 import TD3
 
 
@@ -42,16 +42,7 @@ class TD3BC(TD3):
 
 def check_config(algo: TD3BC) -> None:
     """What the learner would refuse, said before anything touches the GPU."""
-    if algo.precision != "f32":
-        if algo.precision not in _capi.PRECISION:
-            raise ValueError(f"precision={algo.precision!r}: expected one of {sorted(_capi.PRECISION)}")
-        raise ValueError(f"TD3BC: precision={algo.precision!r} unsupported (f32 only: the BC step runs the generic "
-                         "launch sequence)")
-    if algo.export_grads:
-        raise ValueError("TD3BC: export_grads (data-parallel learners) unsupported")
-    if algo.prioritized:
-        raise ValueError("TD3BC(prioritized=True): prioritized replay through TD3BC is not built (a fixed dataset is "
-                         "sampled uniformly)")
+    check_mode_config(algo, "TD3BC", "the BC step runs the generic launch sequence", "a fixed dataset is sampled uniformly")
     alpha = float(algo.bc_alpha)
     if not (math.isfinite(alpha) and alpha > 0.0):
         raise ValueError(f"TD3BC: bc_alpha={algo.bc_alpha!r} is not a finite number above 0")

@@ -6,8 +6,6 @@ built or a file is looked at."""
 from __future__ import annotations
 
 import ctypes as C
-import importlib
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -20,6 +18,7 @@ from oprl_amd.algos.cql import CQL
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import calql_oracle as cal
+from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_replay_returns": 7, "oprl_cql_seed_cal": 19, "oprl_learner_set_calql": 2, "oprl_learner_update_calql": 11}
@@ -208,29 +207,17 @@ def test_the_bound_at_its_ends_and_at_equality():
 
 
 # ---- configs/calql.py -------------------------------------------------------------------------------------------------------
-def _load_config(monkeypatch, argv):
-    monkeypatch.setattr(sys, "argv", ["calql.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", "calql"):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module("calql")
-    finally:
-        for m in ("_common", "calql"):
-            sys.modules.pop(m, None)
-
-
 def test_the_config_script_parses_its_flags(monkeypatch):
-    mod = _load_config(monkeypatch, ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--cql-alpha", "1.5", "--cql-actions", "4",
-                                     "--tune-alpha", "--updates", "300", "--batch", "64", "--updates-per-call", "20",
-                                     "--no-normalize", "--finetune-steps", "40", "--prior-share", "0.25"])
+    mod = load_config(monkeypatch, "calql", ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--cql-alpha", "1.5", "--cql-actions", "4",
+                                             "--tune-alpha", "--updates", "300", "--batch", "64", "--updates-per-call", "20",
+                                             "--no-normalize", "--finetune-steps", "40", "--prior-share", "0.25"])
     a = mod.script.args
     assert (a.dataset, a.cql_alpha, a.cql_actions, a.tune_alpha, a.updates, a.batch, a.updates_per_call, a.no_normalize) == \
         ("d.npz", 1.5, 4, True, 300, 64, 20, True)
     assert (mod.finetune_steps, a.prior_share) == (40, 0.25)
     assert mod.hparams_of(a) == dict(cql_alpha=1.5, cql_n_actions=4, tune_alpha=True, batch_size=64)
     assert mod.script.algo_cls is CalQL and not mod.script.takes_per
-    mod = _load_config(monkeypatch, ["--env", "synthetic:cheetah-run", "--n-step", "3"])
+    mod = load_config(monkeypatch, "calql", ["--env", "synthetic:cheetah-run", "--n-step", "3"])
     assert mod.finetune_steps == 0 and mod.script.args.n_step == 3
     with pytest.raises(ValueError, match="--dataset"):
         mod.run()
@@ -253,4 +240,4 @@ def test_the_config_script_refuses(monkeypatch, argv, msg):
     monkeypatch.setattr(env, "make_env", lambda *a, **k: pytest.fail("an environment was built"))
     monkeypatch.setattr(ds, "load_dataset", lambda *a, **k: pytest.fail("a dataset was opened"))
     with pytest.raises(ValueError, match=msg):
-        _load_config(monkeypatch, ["--env", "synthetic:walker-walk", "--dataset", "none.npz", *argv])
+        load_config(monkeypatch, "calql", ["--env", "synthetic:walker-walk", "--dataset", "none.npz", *argv])

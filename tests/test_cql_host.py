@@ -5,7 +5,6 @@ critics at the GPU comparison's own shapes."""
 from __future__ import annotations
 
 import ctypes as C
-import importlib
 import sys
 from pathlib import Path
 
@@ -18,6 +17,7 @@ from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import cql_oracle as co
 from tests import scenarios as sc
+from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_learner_set_cql": 3, "oprl_learner_read_cql": 3, "oprl_learner_set_cql_noise": 3, "oprl_cql_rows": 16,
@@ -64,29 +64,17 @@ def test_exports_and_the_workspace_the_class_asks_for():
     assert wide_rows(256, 10) == 7936 and wide_rows(100, 2) == 700 and wide_rows(16, 16) == 784
 
 
-def _load_config(monkeypatch, argv):
-    monkeypatch.setattr(sys, "argv", ["cql.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", "cql"):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module("cql")
-    finally:
-        for m in ("_common", "cql"):
-            sys.modules.pop(m, None)
-
-
 def test_the_config_script_parses_its_flags(monkeypatch):
-    mod = _load_config(monkeypatch, ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--cql-alpha", "1.5", "--cql-actions", "4",
-                                     "--tune-alpha", "--updates", "300", "--batch", "64", "--updates-per-call", "20",
-                                     "--no-normalize", "--n-step", "3"])
+    mod = load_config(monkeypatch, "cql", ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--cql-alpha", "1.5", "--cql-actions", "4",
+                                           "--tune-alpha", "--updates", "300", "--batch", "64", "--updates-per-call", "20",
+                                           "--no-normalize", "--n-step", "3"])
     a = mod.script.args
     assert (a.dataset, a.cql_alpha, a.cql_actions, a.tune_alpha, a.updates, a.batch, a.updates_per_call, a.no_normalize, a.n_step) == \
         ("d.npz", 1.5, 4, True, 300, 64, 20, True, 3)
     assert mod.hparams_of(a) == dict(cql_alpha=1.5, cql_n_actions=4, tune_alpha=True, batch_size=64)
     assert mod.config.state_dim == 24 and mod.config.action_dim == 6
     assert mod.script.algo_cls is CQL and not mod.script.takes_per
-    mod = _load_config(monkeypatch, ["--env", "synthetic:cheetah-run"])
+    mod = load_config(monkeypatch, "cql", ["--env", "synthetic:cheetah-run"])
     a = mod.script.args
     assert (a.dataset, a.cql_alpha, a.cql_actions, a.tune_alpha, a.batch, a.no_normalize, a.n_step) == (None, 5.0, 10, False, 256, False, 1)
     with pytest.raises(ValueError, match="--dataset"):
@@ -105,8 +93,13 @@ def test_the_config_script_parses_its_flags(monkeypatch):
     (["--seeds", "2"], "--seeds"),
 ], ids=["per", "num-envs", "num-envs-open", "open-episodes", "seeds"])
 def test_the_config_script_refuses(monkeypatch, argv, msg):
+    """... before an environment is built or a file is opened."""
+    import oprl_amd.buffers.offline_dataset as ds
+    import oprl_amd.environment as env
+    monkeypatch.setattr(env, "make_env", lambda *a, **k: pytest.fail("an environment was built"))
+    monkeypatch.setattr(ds, "load_dataset", lambda *a, **k: pytest.fail("a dataset was opened"))
     with pytest.raises(ValueError, match=msg):
-        _load_config(monkeypatch, ["--env", "synthetic:walker-walk", *argv])
+        load_config(monkeypatch, "cql", ["--env", "synthetic:walker-walk", *argv])
 
 
 @pytest.mark.parametrize("kw,msg", [

@@ -4,7 +4,6 @@ scatter projection is the kernel's gather formula."""
 from __future__ import annotations
 
 import ctypes as C
-import importlib
 import sys
 from pathlib import Path
 
@@ -16,6 +15,7 @@ from oprl_amd import _capi
 from oprl_amd.algos.d4pg import D4PG
 from oprl_amd.logging import NullLogger
 from tests import d4pg_oracle as do
+from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
 
@@ -59,30 +59,18 @@ def test_exports():
     assert t.allclose(q[:, 0], (t.softmax(logits, 1) * t.linspace(-1, 1, 5)).sum(1))
 
 
-def _load_config(monkeypatch, argv):
-    monkeypatch.setattr(sys, "argv", ["d4pg.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", "d4pg"):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module("d4pg")
-    finally:
-        for m in ("_common", "d4pg"):
-            sys.modules.pop(m, None)
-
-
 def test_the_config_script_parses_its_flags(monkeypatch):
-    mod = _load_config(monkeypatch, ["--env", "walker-walk"])
+    mod = load_config(monkeypatch, "d4pg", ["--env", "walker-walk"])
     assert (mod.script.args.atoms, mod.script.args.v_min, mod.script.args.v_max) == (41, -150.0, 150.0)
     assert mod.atoms_of(mod.script.args) == dict(n_atoms=41, v_min=-150.0, v_max=150.0)
-    mod = _load_config(monkeypatch, ["--env", "walker-walk", "--atoms", "31", "--v-min", "-10", "--v-max", "90",
-                                      "--n-step", "3", "--num-envs", "4", "--open-episodes"])
+    mod = load_config(monkeypatch, "d4pg", ["--env", "walker-walk", "--atoms", "31", "--v-min", "-10", "--v-max", "90",
+                                            "--n-step", "3", "--num-envs", "4", "--open-episodes"])
     args = mod.script.args
     assert (args.atoms, args.v_min, args.v_max, args.n_step, args.num_envs, args.open_episodes) == (31, -10.0, 90.0, 3, 4, True)
     assert mod.config.state_dim == 24 and mod.config.action_dim == 6
     assert mod.script.algo_cls is D4PG and not mod.script.takes_per
     with pytest.raises(ValueError, match="--per"):
-        _load_config(monkeypatch, ["--env", "walker-walk", "--per"])
+        load_config(monkeypatch, "d4pg", ["--env", "walker-walk", "--per"])
     # the other scripts still parse as before
     from oprl_amd.parse_args import parse_args
     monkeypatch.setattr(sys, "argv", ["ddpg.py"])

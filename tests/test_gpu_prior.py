@@ -7,9 +7,6 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import importlib
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -17,9 +14,9 @@ import torch as t
 
 from oprl_amd import _capi
 from tests import prior_oracle as po
+from tests.config_scripts import load_config
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parents[1]
 KEYS = ("s", "a", "r", "d", "s2")
 INTS = ("ep", "step", "src")
 SENT_F, SENT_I = 12345.0, -777
@@ -592,18 +589,6 @@ def test_iql_pretrained_offline_is_finetuned_online_on_mixed_batches(data):
     assert np.isfinite(ret) and 0.0 < ret <= STEPS
 
 
-def _load_config(monkeypatch, script, argv):
-    monkeypatch.setattr(sys, "argv", [f"{script}.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", script):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module(script)
-    finally:
-        for m in ("_common", script):
-            sys.modules.pop(m, None)
-
-
 def test_sac_from_scratch_through_the_prior_data_flag(data, tmp_path, monkeypatch):
     """configs/sac.py --prior-data: the script's own factories through run_training for 120 environment steps."""
     from oprl_amd.buffers.prior_buffer import PriorDataReplayBuffer
@@ -612,7 +597,7 @@ def test_sac_from_scratch_through_the_prior_data_flag(data, tmp_path, monkeypatc
     path = tmp_path / "cheetah.npz"
     np.savez(path, observations=data.observations, actions=data.actions, rewards=data.rewards, terminals=data.terminals,
              timeouts=data.timeouts, next_observations=data.next_observations)
-    mod = _load_config(monkeypatch, "sac", ["--env", f"synthetic:{ENV}", "--prior-data", str(path), "--prior-share", "0.5"])
+    mod = load_config(monkeypatch, "sac", ["--env", f"synthetic:{ENV}", "--prior-data", str(path), "--prior-share", "0.5"])
     made, log = {}, []
 
     def make_algo(logger):

@@ -3,7 +3,6 @@ list, the alias, the Python buffer's validation, the command-line flags and what
 goal-conditioned synthetic environment, and the statistics of tests/her_oracle.py's draws (no GPU needed)."""
 from __future__ import annotations
 
-import importlib
 import math
 import sys
 from pathlib import Path
@@ -13,6 +12,7 @@ import pytest
 
 from oprl_amd import _capi
 from tests import her_oracle as ho
+from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
 HER_FUNCS = {"oprl_replay_set_her": 8, "oprl_replay_sample_her": 14}
@@ -131,44 +131,32 @@ def test_her_flags(monkeypatch):
         parse_args()
 
 
-def _load_config(monkeypatch, script, argv):
-    monkeypatch.setattr(sys, "argv", [f"{script}.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", script):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module(script)
-    finally:
-        for m in ("_common", script):
-            sys.modules.pop(m, None)
-
-
 GOAL_ENV = ["--env", "synthetic:goal-reach-2d"]
 
 
 def test_config_refuses_her_with_per(monkeypatch):
     with pytest.raises(ValueError, match="--per"):
-        _load_config(monkeypatch, "ddpg", [*GOAL_ENV, "--her", "--per"])
+        load_config(monkeypatch, "ddpg", [*GOAL_ENV, "--her", "--per"])
 
 
 def test_config_refuses_her_with_n_step(monkeypatch):
     with pytest.raises(ValueError, match="--n-step 3"):
-        _load_config(monkeypatch, "td3", [*GOAL_ENV, "--her", "--n-step", "3"])
+        load_config(monkeypatch, "td3", [*GOAL_ENV, "--her", "--n-step", "3"])
 
 
 def test_config_refuses_her_without_a_goal_layout(monkeypatch):
     with pytest.raises(ValueError, match="goal layout"):
-        _load_config(monkeypatch, "sac", ["--env", "synthetic:walker-walk", "--her"])
+        load_config(monkeypatch, "sac", ["--env", "synthetic:walker-walk", "--her"])
 
 
 def test_config_refuses_her_in_the_offline_scripts(monkeypatch):
     with pytest.raises(ValueError, match="--her"):
-        _load_config(monkeypatch, "iql", [*GOAL_ENV, "--her"])
+        load_config(monkeypatch, "iql", [*GOAL_ENV, "--her"])
 
 
 def test_config_builds_the_hindsight_buffer_from_the_environments_layout(monkeypatch):
     from oprl_amd.buffers.hindsight_buffer import HindsightEpisodicReplayBuffer
-    mod = _load_config(monkeypatch, "ddpg", [*GOAL_ENV, "--her", "--her-ratio", "0.5", "--device", "cpu"])
+    mod = load_config(monkeypatch, "ddpg", [*GOAL_ENV, "--her", "--her-ratio", "0.5", "--device", "cpu"])
     assert mod.script.her and (mod.config.state_dim, mod.config.action_dim) == (8, 2)
     buf = mod.make_replay_buffer()
     assert type(buf) is HindsightEpisodicReplayBuffer
@@ -177,7 +165,7 @@ def test_config_builds_the_hindsight_buffer_from_the_environments_layout(monkeyp
     assert buf.threshold == mod.make_env(seed=0).goal_layout["threshold"]
     # without the flag the same script builds what it built before
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
-    plain = _load_config(monkeypatch, "ddpg", [*GOAL_ENV, "--device", "cpu"])
+    plain = load_config(monkeypatch, "ddpg", [*GOAL_ENV, "--device", "cpu"])
     assert not plain.script.her and type(plain.make_replay_buffer()) is EpisodicReplayBuffer
 
 

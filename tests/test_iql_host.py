@@ -5,7 +5,6 @@ the actor or V."""
 from __future__ import annotations
 
 import ctypes as C
-import importlib
 import sys
 from pathlib import Path
 
@@ -17,6 +16,7 @@ from oprl_amd.algos.iql import IQL
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests.iql_oracle import IQLOracle
+from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_learner_set_iql": 6, "oprl_learner_read_iql": 3, "oprl_learner_get_iql_step": 2,
@@ -61,29 +61,17 @@ def test_exports():
     assert (algo.expectile, algo.beta, algo.adv_clip, algo.lr_value, algo.policy_freq) == (0.7, 3.0, 100.0, 3e-4, 1)
 
 
-def _load_config(monkeypatch, argv):
-    monkeypatch.setattr(sys, "argv", ["iql.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", "iql"):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module("iql")
-    finally:
-        for m in ("_common", "iql"):
-            sys.modules.pop(m, None)
-
-
 def test_the_config_script_parses_its_flags(monkeypatch):
-    mod = _load_config(monkeypatch, ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--expectile", "0.9", "--beta", "10",
-                                     "--adv-clip", "50", "--updates", "300", "--batch", "64", "--updates-per-call", "20",
-                                     "--no-normalize", "--n-step", "3"])
+    mod = load_config(monkeypatch, "iql", ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--expectile", "0.9", "--beta", "10",
+                                           "--adv-clip", "50", "--updates", "300", "--batch", "64", "--updates-per-call", "20",
+                                           "--no-normalize", "--n-step", "3"])
     a = mod.script.args
     assert (a.dataset, a.expectile, a.beta, a.adv_clip, a.updates, a.batch, a.updates_per_call, a.no_normalize, a.n_step) == \
         ("d.npz", 0.9, 10.0, 50.0, 300, 64, 20, True, 3)
     assert mod.hparams_of(a) == dict(expectile=0.9, beta=10.0, adv_clip=50.0, batch_size=64)
     assert mod.config.state_dim == 24 and mod.config.action_dim == 6
     assert mod.script.algo_cls is IQL and not mod.script.takes_per
-    mod = _load_config(monkeypatch, ["--env", "synthetic:cheetah-run"])
+    mod = load_config(monkeypatch, "iql", ["--env", "synthetic:cheetah-run"])
     a = mod.script.args
     assert (a.dataset, a.expectile, a.beta, a.adv_clip, a.batch, a.no_normalize, a.n_step) == (None, 0.7, 3.0, 100.0, 256, False, 1)
     with pytest.raises(ValueError, match="--dataset"):
@@ -102,8 +90,13 @@ def test_the_config_script_parses_its_flags(monkeypatch):
     (["--seeds", "2"], "--seeds"),
 ], ids=["per", "num-envs", "num-envs-open", "open-episodes", "seeds"])
 def test_the_config_script_refuses(monkeypatch, argv, msg):
+    """... before an environment is built or a file is opened."""
+    import oprl_amd.buffers.offline_dataset as ds
+    import oprl_amd.environment as env
+    monkeypatch.setattr(env, "make_env", lambda *a, **k: pytest.fail("an environment was built"))
+    monkeypatch.setattr(ds, "load_dataset", lambda *a, **k: pytest.fail("a dataset was opened"))
     with pytest.raises(ValueError, match=msg):
-        _load_config(monkeypatch, ["--env", "synthetic:walker-walk", *argv])
+        load_config(monkeypatch, "iql", ["--env", "synthetic:walker-walk", *argv])
 
 
 @pytest.mark.parametrize("kw,msg", [

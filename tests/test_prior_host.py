@@ -4,7 +4,6 @@ the numpy oracle on hand-written storage, and every flag refusal of the online a
 needed)."""
 from __future__ import annotations
 
-import importlib
 import math
 import sys
 from fractions import Fraction
@@ -15,6 +14,7 @@ import pytest
 
 from oprl_amd import _capi
 from tests import prior_oracle as po
+from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
 PRIOR_FUNCS = {"oprl_replay_set_prior": 3, "oprl_replay_sample_mix": 14}
@@ -230,18 +230,6 @@ def test_check_prior_refuses(monkeypatch, extra, word):
         check_prior(parse_args())
 
 
-def _load_config(monkeypatch, script, argv):
-    monkeypatch.setattr(sys, "argv", [f"{script}.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", script):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module(script)
-    finally:
-        for m in ("_common", script):
-            sys.modules.pop(m, None)
-
-
 NO_FILE = ["--prior-data", "/nonexistent/never_read.npz"]       # refused before the file is looked at
 NO_ENV = ["--env", "no-such-environment"]                       # ... and before an environment is built
 
@@ -252,26 +240,26 @@ NO_ENV = ["--env", "no-such-environment"]                       # ... and before
                                                ("d4pg", ["--prior-share", "2"], "--prior-share")])
 def test_online_scripts_refuse_before_anything_is_built(monkeypatch, script, extra, word):
     with pytest.raises(ValueError, match=word):
-        _load_config(monkeypatch, script, [*NO_ENV, *NO_FILE, *extra])
+        load_config(monkeypatch, script, [*NO_ENV, *NO_FILE, *extra])
     with pytest.raises(ValueError, match="no-such-environment"):      # (what is refused next, once the flags agree)
-        _load_config(monkeypatch, script, [*NO_ENV, *NO_FILE])
+        load_config(monkeypatch, script, [*NO_ENV, *NO_FILE])
 
 
 @pytest.mark.parametrize("script", ["td3_bc", "iql", "cql"])
 def test_offline_scripts_refuse(monkeypatch, script):
     env = ["--env", "synthetic:reacher-easy", "--device", "cpu"]
     with pytest.raises(ValueError, match="--finetune-steps with --n-step 3"):
-        _load_config(monkeypatch, script, [*env, "--finetune-steps", "100", "--n-step", "3"])
+        load_config(monkeypatch, script, [*env, "--finetune-steps", "100", "--n-step", "3"])
     with pytest.raises(ValueError, match="--finetune-steps -1"):
-        _load_config(monkeypatch, script, [*env, "--finetune-steps", "-1"])
+        load_config(monkeypatch, script, [*env, "--finetune-steps", "-1"])
     with pytest.raises(ValueError, match="--prior-share"):
-        _load_config(monkeypatch, script, [*env, "--finetune-steps", "100", "--prior-share", "1.01"])
+        load_config(monkeypatch, script, [*env, "--finetune-steps", "100", "--prior-share", "1.01"])
     with pytest.raises(ValueError, match="--prior-data"):
-        _load_config(monkeypatch, script, [*env, "--prior-data", "d.npz"])
+        load_config(monkeypatch, script, [*env, "--prior-data", "d.npz"])
     # the default is today's behaviour: no fine-tuning, and --n-step alone is still accepted
-    mod = _load_config(monkeypatch, script, [*env, "--n-step", "3"])
+    mod = load_config(monkeypatch, script, [*env, "--n-step", "3"])
     assert mod.finetune_steps == 0
-    mod = _load_config(monkeypatch, script, [*env, "--finetune-steps", "100", "--prior-share", "0.25"])
+    mod = load_config(monkeypatch, script, [*env, "--finetune-steps", "100", "--prior-share", "0.25"])
     assert mod.finetune_steps == 100 and mod.script.args.prior_share == 0.25
 
 
@@ -291,7 +279,7 @@ def test_online_script_builds_the_prior_buffer_from_the_dataset(monkeypatch, tmp
     np.savez(path, observations=obs, actions=rs.uniform(-1, 1, (N, A)).astype(np.float32), rewards=rs.rand(N).astype(np.float32),
              terminals=term, timeouts=tout, next_observations=obs + 1)
     env = ["--env", "synthetic:reacher-easy", "--device", "cpu"]
-    mod = _load_config(monkeypatch, "sac", [*env, "--prior-data", str(path), "--prior-share", "0.25"])
+    mod = load_config(monkeypatch, "sac", [*env, "--prior-data", str(path), "--prior-share", "0.25"])
     assert mod.script.prior
     buf = mod.make_replay_buffer()
     assert type(buf) is PriorDataReplayBuffer and type(buf.prior) is EpisodicReplayBuffer and buf.prior_share == 0.25
@@ -303,7 +291,7 @@ def test_online_script_builds_the_prior_buffer_from_the_dataset(monkeypatch, tmp
     np.savez(tmp_path / "bad.npz", observations=obs[:, :5], actions=rs.rand(N, A).astype(np.float32), rewards=rs.rand(N).astype(np.float32),
              terminals=term)
     with pytest.raises(ValueError, match="dims"):
-        _load_config(monkeypatch, "sac", [*env, "--prior-data", str(tmp_path / "bad.npz")]).make_replay_buffer()
+        load_config(monkeypatch, "sac", [*env, "--prior-data", str(tmp_path / "bad.npz")]).make_replay_buffer()
     # without the flag the same script builds what it built before
-    plain = _load_config(monkeypatch, "sac", env)
+    plain = load_config(monkeypatch, "sac", env)
     assert not plain.script.prior and type(plain.make_replay_buffer()) is EpisodicReplayBuffer

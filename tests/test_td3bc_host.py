@@ -4,7 +4,6 @@ refuses it refuses before the GPU is touched, and the oracle's hand-written grad
 from __future__ import annotations
 
 import ctypes as C
-import importlib
 import sys
 from pathlib import Path
 
@@ -16,6 +15,7 @@ from oprl_amd.algos.td3_bc import TD3BC
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests.td3bc_oracle import TD3BCOracle
+from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_learner_set_bc": 2, "oprl_learner_read_bc": 3, "oprl_bc_seed": 12}
@@ -61,27 +61,15 @@ def test_exports():
     assert algo.bc_alpha == 2.5 and algo.policy_freq == 2
 
 
-def _load_config(monkeypatch, argv):
-    monkeypatch.setattr(sys, "argv", ["td3_bc.py", *argv])
-    monkeypatch.syspath_prepend(str(ROOT / "configs"))
-    for m in ("_common", "td3_bc"):
-        sys.modules.pop(m, None)
-    try:
-        return importlib.import_module("td3_bc")
-    finally:
-        for m in ("_common", "td3_bc"):
-            sys.modules.pop(m, None)
-
-
 def test_the_config_script_parses_its_flags(monkeypatch):
-    mod = _load_config(monkeypatch, ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--bc-alpha", "1.5",
-                                     "--updates", "300", "--batch", "64", "--no-normalize", "--n-step", "3"])
+    mod = load_config(monkeypatch, "td3_bc", ["--env", "synthetic:walker-walk", "--dataset", "d.npz", "--bc-alpha", "1.5",
+                                              "--updates", "300", "--batch", "64", "--no-normalize", "--n-step", "3"])
     a = mod.script.args
     assert (a.dataset, a.bc_alpha, a.updates, a.batch, a.no_normalize, a.n_step) == ("d.npz", 1.5, 300, 64, True, 3)
     assert mod.alpha_of(a) == dict(bc_alpha=1.5, batch_size=64)
     assert mod.config.state_dim == 24 and mod.config.action_dim == 6
     assert mod.script.algo_cls is TD3BC and not mod.script.takes_per
-    mod = _load_config(monkeypatch, ["--env", "synthetic:cheetah-run"])
+    mod = load_config(monkeypatch, "td3_bc", ["--env", "synthetic:cheetah-run"])
     a = mod.script.args
     assert (a.dataset, a.bc_alpha, a.batch, a.no_normalize, a.n_step) == (None, 2.5, 256, False, 1)
     with pytest.raises(ValueError, match="--dataset"):
@@ -99,8 +87,13 @@ def test_the_config_script_parses_its_flags(monkeypatch):
     (["--open-episodes"], "--open-episodes"),
 ], ids=["per", "num-envs", "num-envs-open", "open-episodes"])
 def test_the_config_script_refuses(monkeypatch, argv, msg):
+    """... before an environment is built or a file is opened."""
+    import oprl_amd.buffers.offline_dataset as ds
+    import oprl_amd.environment as env
+    monkeypatch.setattr(env, "make_env", lambda *a, **k: pytest.fail("an environment was built"))
+    monkeypatch.setattr(ds, "load_dataset", lambda *a, **k: pytest.fail("a dataset was opened"))
     with pytest.raises(ValueError, match=msg):
-        _load_config(monkeypatch, ["--env", "synthetic:walker-walk", *argv])
+        load_config(monkeypatch, "td3_bc", ["--env", "synthetic:walker-walk", *argv])
 
 
 @pytest.mark.parametrize("kw,msg", [
