@@ -119,6 +119,33 @@ class TrainingScript:
                      open_episodes=self.args.open_episodes)
 
 
+LAYER_NORM_FLAG = ("--layer-norm", bool, False,
+                   "LayerNorm in the critics' hidden layers (Linear -> LayerNorm -> ReLU; RLPD / DroQ): generic launch "
+                   "sequence, f32, one learner; not with --per")
+
+
+def layer_norm_kwargs(args: Namespace) -> dict:
+    return dict(layer_norm=bool(args.layer_norm))
+
+
+@dataclass
+class LayerNormScript(TrainingScript):
+    """configs/sac.py and configs/redq.py: ``--layer-norm`` sets the algorithm's ``layer_norm`` field."""
+
+    extra_flags: tuple = (LAYER_NORM_FLAG,)
+    algo_kwargs: Callable[[Namespace], dict] | None = layer_norm_kwargs
+
+    def refuse(self) -> None:
+        super().refuse()
+        if not self.args.layer_norm:
+            return
+        if self.per:
+            raise ValueError("--layer-norm with --per: the LayerNorm critics' kernels take no importance weights")
+        if self.args.seeds != 1:
+            raise ValueError("--layer-norm with --seeds > 1: LayerNorm critics are built and measured for one learner per "
+                             "GPU; one run per invocation (--start_seed picks its seed)")
+
+
 OFFLINE_FLAGS = (       # of every offline script: --dataset before the script's own flags, the others behind them
     ("--dataset", str, None, "the dataset: an .npz with observations, actions, rewards, terminals [, timeouts, next_observations]"),
     ("--updates", int, 1_000_000, "updates to run"),

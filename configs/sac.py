@@ -2,6 +2,7 @@
 this repo unchanged through the ``oprl`` alias package).
 
     python configs/sac.py --env walker-walk --device cuda [--seeds N]
+    python configs/sac.py --env walker-walk --layer-norm        # LayerNorm critics
 """
 import sys
 from pathlib import Path
@@ -9,10 +10,10 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
-from _common import TrainingScript  # noqa: E402
+from _common import LayerNormScript  # noqa: E402
 from oprl.algos.sac import SAC  # noqa: E402
 
-script = TrainingScript(SAC, "SAC", estimate_q_every=5000, log_every=1000)
+script = LayerNormScript(SAC, "SAC", estimate_q_every=5000, log_every=1000)
 # the names a reference-style script defines at module level
 make_env, make_algo, make_replay_buffer, make_logger, config = (
     script.make_env, script.make_algo, script.make_replay_buffer, script.make_logger, script.config)

@@ -14,7 +14,9 @@
  *                    (Kumar et al. 2020, CQL(H)) as a mode of a SAC learner
  *   oprl_learner_set_calql / update_calql, oprl_replay_returns, oprl_cql_seed_cal   no counterpart: calibrated Q-learning
  *                    (Nakamoto et al. 2023, Cal-QL), the calibrated form of that mode
- *   oprl_replay_*    ReplayBufferProtocol                 buffers/protocols.py:6-26
+ *   oprl_learner_set_layernorm, oprl_mlp_ln   no counterpart: layer normalisation in the critics of a SAC / REDQ learner
+ *                    (the RLPD / DroQ critic block)
+ *   oprl_replay_*    ReplayBufferProtocol              buffers/protocols.py:6-26
  *                    EpisodicReplayBuffer.{add_transition,sample}  buffers/episodic_buffer.py:81-133
  *   oprl_mlp_*       MLP / Critic / policies forward      algos/nn_models.py:27-194
  *   oprl_adam_* / oprl_polyak   torch.optim.Adam.step / soft_update  algos/nn_functions.py:5-10
@@ -741,6 +743,42 @@ int oprl_learner_set_calql(oprl_learner* h, int32_t on);
  * null g; OPRL_ERR_STATE: the calibrated form is off. */
 int oprl_learner_update_calql(oprl_learner* h, const float* s, const float* a, const float* r, const float* d, const float* s2,
                               const float* g, int32_t B, const float* noise0, const float* noise1, void* stream);
+
+/* ---- LayerNorm critics (Ball et al. 2023, RLPD; Hiraoka et al. 2022, DroQ): Linear -> LayerNorm -> ReLU in
+ * both hidden layers of every critic of a SAC or REDQ learner; the output layer stays plain.  Per hidden layer and row, over
+ * the 256 columns: mu = mean z, var = mean (z - mu)^2 (biased, two passes), zh = (z - mu) / sqrt(var + eps),
+ * x = relu(gamma zh + beta).  The four arrays are the CALLER's device arrays [n_critics][2 hidden layers][gamma | beta][256]
+ * fp32 (gamma starts at 1, beta at 0; the target copy equal; m and v zero), outside the nets' arenas and packs, whose
+ * layouts do not change.  They belong to the critic optimiser: every update steps them with lr_critic, the learner's betas
+ * and eps and the step count of that update's critic dW launch, and the target copy takes its Polyak step when the
+ * critics' targets do.  Target forwards read the target copy; the actor step propagates through LN and steps nothing.
+ * Called once, before the first update.  OPRL_ERR_INVALID: an algorithm other than SAC / REDQ, a precision other than f32,
+ * critics that are not three layers of hidden width 256 with one output, a null array, an eps that is not finite and
+ * positive.  OPRL_ERR_STATE: the fused launch form is on (create the learner with no_fuse), a group member, export_grads /
+ * data-parallel, the CQL mode on, a second call, a learner that has updated.  While the mode is on oprl_learner_set_cql /
+ * set_calql, oprl_group_create, oprl_learner_update_weighted and oprl_learner_step_n_prio return OPRL_ERR_STATE.  A refused
+ * call changes nothing. */
+typedef struct oprl_layernorm {
+  float* theta;             /* [n_critics][2][2][256] gamma | beta per hidden layer */
+  float* theta_target;      /* the target critics' copy */
+  float* adam_m;            /* Adam's first and second moments */
+  float* adam_v;
+  float eps;                /* 1e-5f: torch's default */
+} oprl_layernorm;
+int oprl_learner_set_layernorm(oprl_learner* h, const oprl_layernorm* ln);
+/* One packed three-layer net of hidden width 256 with LN parameters ln_theta [2][gamma | beta][256] on caller rows
+ * [x0 | x1] (x1 may be null): forward, and — given the seed rows dout [B][n_out] — backward.  split = 0: one launch;
+ * 1: a forward-only launch that keeps the rows, then a backward-only launch that reloads them (the same bits).  The row
+ * arrays hold `rows` >= B rows per hidden layer, of which rows >= B are not touched: x_rows / dz_rows / zh_rows
+ * [2][rows][256] (the layer's output, the gradient wrt its pre-normalisation z, the normalised z), rstd_rows [2][rows];
+ * out [B][n_out]; dx1 [B][k1] (or null) the gradient wrt the x1 columns; dln [2][2][256] dgamma | dbeta summed over the
+ * batch in slice order.  dout null: forward only (dz_rows, dx1, dln unused).  With dout the call allocates its per-slice sums,
+ * SYNCHRONISES the stream and frees them before it returns.  OPRL_ERR_INVALID: null arguments, a net that is not three layers
+ * of hidden width 256, B < 1, rows < B or rows > 2^22, k0 + k1 != the net's input dim, an eps that is not finite and positive.
+ * The kernel tests' entry point. */
+int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1, int32_t k1,
+                int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows, float* dz_rows,
+                float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream);
 
 #ifdef __cplusplus
 }

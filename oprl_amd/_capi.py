@@ -71,6 +71,16 @@ class OprlLearnerConfig(C.Structure):
     ]
 
 
+class OprlLayerNorm(C.Structure):
+    _fields_ = [
+        ("theta", C.c_void_p),
+        ("theta_target", C.c_void_p),
+        ("adam_m", C.c_void_p),
+        ("adam_v", C.c_void_p),
+        ("eps", C.c_float),
+    ]
+
+
 # every symbol the header declares: name -> (restype, argtypes)
 _P, _I32, _I64, _U64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 SIGNATURES = {
@@ -167,6 +177,8 @@ SIGNATURES = {
     "oprl_cql_seed_cal": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "oprl_learner_set_calql": (C.c_int, [_P, _I32]),
     "oprl_learner_update_calql": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P]),
+    "oprl_learner_set_layernorm": (C.c_int, [_P, C.POINTER(OprlLayerNorm)]),
+    "oprl_mlp_ln": (C.c_int, [C.POINTER(OprlNet), _P, _F, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -157,6 +157,21 @@ def check_prioritized_config(algo) -> None:
                          "prioritized training)")
 
 
+def check_layer_norm_config(algo) -> None:
+    """``layer_norm=True`` puts LayerNorm into the critics of SAC and REDQ on the exact-fp32 generic launch sequence of one
+    GPU: called by ``create()`` before anything touches the GPU."""
+    if not getattr(algo, "layer_norm", False):
+        return
+    name = type(algo).__name__
+    if algo.prioritized:
+        raise ValueError(f"{name}(layer_norm=True, prioritized=True): the LN kernels take no importance weights "
+                         "(prioritized replay with LayerNorm critics is not built)")
+    if algo.export_grads:
+        raise ValueError(f"{name}(layer_norm=True) does not export gradients (no data-parallel LayerNorm critics)")
+    if algo.precision != "f32":
+        raise ValueError(f"{name}(layer_norm=True) needs precision='f32', got {algo.precision!r}: the LN kernels run exact fp32")
+
+
 def check_mode_config(algo, name: str, f32_only: str, uniform_only: str | None = None) -> None:
     """What the learner refuses of an algorithm that runs as a mode of another's learner, or on the generic launch
     sequence alone, said before anything touches the GPU: a precision other than f32 (``f32_only`` says what needs it),
@@ -205,6 +220,7 @@ def check_nstep_gamma(algo, replay_buffer) -> None:
 
 
 IQL_STATE_KEYS = ("value", "value_m", "value_v", "value_step")
+LN_STATE_KEYS = ("critic_ln", "critic_ln_target", "critic_ln_m", "critic_ln_v")
 
 
 def _rows_f32(obs) -> np.ndarray:
@@ -312,6 +328,7 @@ class HipLearner:
         self._mlps = (actor_mlp, actor_target_mlp, list(critic_mlps), list(critic_target_mlps))
         self._value_mlp = None         # the value net of the implicit-Q-learning mode (set_iql) ...
         self._iql_on = False           # ... and whether the mode is on (the net and its moments are kept while it is off)
+        self._ln = None                # the critics' LayerNorm holder (set_layernorm), or None
         self._ptrs = self._snapshot_ptrs()
         h = C.c_void_p()
         with _capi.on_device(device):
@@ -344,7 +361,9 @@ class HipLearner:
         return c
 
     def _snapshot_ptrs(self):
-        return tuple(p.data_ptr() for p in self._param_cache()[0])
+        # (the LayerNorm holder's four tensors too: the library keeps their raw pointers, set_layernorm)
+        ln = () if self._ln is None else tuple(x.data_ptr() for x in self._ln.tensors())
+        return tuple(p.data_ptr() for p in self._param_cache()[0]) + ln
 
     def _snapshot_versions(self):
         return tuple(p._version for p in self._param_cache()[1])
@@ -384,6 +403,8 @@ class HipLearner:
             _capi.check(self.lib.oprl_learner_get_iql_step(self.handle, C.byref(n)), "oprl_learner_get_iql_step")
             sd.update(value=self.value_arena.detach().cpu().clone(), value_m=self.value_m.cpu().clone(),
                       value_v=self.value_v.cpu().clone(), value_step=int(n.value))
+        if self._ln is not None:      # LayerNorm critics: the parameters, their target copy and both Adam moments
+            sd.update({k: x.detach().cpu().clone() for k, x in zip(LN_STATE_KEYS, self._ln.tensors())})
         return sd
 
     def load_state_dict(self, sd: dict[str, Any]) -> None:
@@ -400,6 +421,16 @@ class HipLearner:
                 raise ValueError(f"checkpoint has no {', '.join(missing)}: this learner's implicit-Q-learning mode is on "
                                  "and resumes its value net, both Adam moments and its step count with the rest")
             pairs += [(self.value_arena, sd["value"]), (self.value_m, sd["value_m"]), (self.value_v, sd["value_v"])]
+        have_ln = [k for k in LN_STATE_KEYS if k in sd]
+        if self._ln is None and have_ln:
+            raise ValueError(f"checkpoint carries {', '.join(have_ln)} but this learner's critics have no layer normalisation "
+                             "(layer_norm=False)")
+        if self._ln is not None:
+            missing = [k for k in LN_STATE_KEYS if k not in sd]
+            if missing:
+                raise ValueError(f"checkpoint has no {', '.join(missing)}: this learner's critics carry layer normalisation "
+                                 "(layer_norm=True) and resume its parameters, target copy and Adam moments with the rest")
+            pairs += [(x, sd[k]) for k, x in zip(LN_STATE_KEYS, self._ln.tensors())]
         for dst, src in pairs:
             if dst.shape != src.shape:
                 raise ValueError(f"checkpoint tensor shape {tuple(src.shape)} != {tuple(dst.shape)}")
@@ -621,6 +652,19 @@ class HipLearner:
         self._cql_noise = (prep(eps), prep(uni))
         _capi.check(self.lib.oprl_learner_set_cql_noise(self.handle, _capi.ptr(self._cql_noise[0]), _capi.ptr(self._cql_noise[1])),
                     "oprl_learner_set_cql_noise")
+
+    def set_layernorm(self, holder) -> None:
+        """Layer normalisation in the critics of a SAC / REDQ learner (oprl_learner_set_layernorm):
+        ``holder`` is the ``CriticLayerNorm`` whose four device tensors [n_critics, 2, 2, 256] the library reads and steps
+        in place.  Once, before the first update; a refused call leaves the learner as it was.  The four tensors must stay
+        where they are (write into them in place): ``check_bound`` refuses to run once one of them was replaced or moved."""
+        d = _capi.OprlLayerNorm()
+        d.theta, d.theta_target, d.adam_m, d.adam_v = (x.data_ptr() for x in holder.tensors())
+        d.eps = float(holder.eps)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_set_layernorm(self.handle, C.byref(d)), "oprl_learner_set_layernorm")
+        self._ln = holder
+        self._ptrs = self._snapshot_ptrs()      # the holder's tensors join the pointers check_bound() watches
 
     def set_calql(self, on: bool) -> None:
         """The calibrated form of the CQL mode (oprl_learner_set_calql; Cal-QL): the penalty's

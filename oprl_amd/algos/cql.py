@@ -57,6 +57,8 @@ def check_config(algo: CQL) -> None:
     """What the learner would refuse, said before anything touches the GPU."""
     check_mode_config(algo, "CQL", "the mode runs the generic launch sequence",
                       "no importance weights in the penalty; a fixed dataset is sampled uniformly")
+    if getattr(algo, "layer_norm", False):
+        raise ValueError(f"{type(algo).__name__}(layer_norm=True): the conservative penalty's wide critic step has no LayerNorm form")
     try:
         ca = float(algo.cql_alpha)
     except (TypeError, ValueError):

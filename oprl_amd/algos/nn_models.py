@@ -310,6 +310,61 @@ def _forward_sa(mlp: MLP, states: t.Tensor, actions: t.Tensor) -> t.Tensor:
     return mlp.nn(t.cat([states, actions], dim=-1))
 
 
+LN_WIDTH = 256      # the hidden width the LN slice kernels are built for (csrc/ln_slice.h)
+
+
+class CriticLayerNorm(nn.Module):
+    """The LayerNorm parameters of ``n_critics`` critics MLP(S + A -> 256 -> 256 -> 1) whose hidden layers are
+    Linear -> LayerNorm -> ReLU: ONE tensor ``theta`` [n_critics, 2 hidden layers, 2, 256] —
+    [..., 0, :] gamma (starts at 1), [..., 1, :] beta (starts at 0) — and, made by ``make_state``, its target twin and
+    Adam's two moments, the four arrays oprl_learner_set_layernorm takes.  It is NOT a submodule of any ``MLP``:
+    ``flatten_module_`` would fold it into the net's arena and break the layout the library reads.  The critic modules
+    hold it in their ``__dict__`` (``attach_layer_norm``) and apply it in ``forward``."""
+
+    def __init__(self, n_critics: int, eps: float = 1e-5) -> None:
+        super().__init__()
+        theta = t.zeros(n_critics, 2, 2, LN_WIDTH, dtype=t.float32)
+        theta[:, :, 0, :] = 1.0
+        self.theta = nn.Parameter(theta, requires_grad=False)
+        self.eps = float(eps)
+        self.target: t.Tensor | None = None
+        self.m: t.Tensor | None = None
+        self.v: t.Tensor | None = None
+
+    def make_state(self) -> "CriticLayerNorm":
+        """The target twin (a copy) and zero moments, on the parameters' device."""
+        self.target = self.theta.detach().clone()
+        self.m = t.zeros_like(self.target)
+        self.v = t.zeros_like(self.target)
+        return self
+
+    def tensors(self) -> tuple[t.Tensor, t.Tensor, t.Tensor, t.Tensor]:
+        if self.target is None:
+            self.make_state()
+        return self.theta.data, self.target, self.m, self.v
+
+    def gamma_beta(self, net: int, layer: int, target: bool = False) -> tuple[t.Tensor, t.Tensor]:
+        th = self.target if target else self.theta.data
+        return th[net, layer, 0], th[net, layer, 1]
+
+
+def attach_layer_norm(critic: nn.Module, holder: CriticLayerNorm, target: bool) -> None:
+    """``critic.forward`` applies ``holder``'s LayerNorm from now on (``target``: the target twin's parameters)."""
+    critic.__dict__["_ln"] = (holder, bool(target))
+
+
+def _forward_sa_ln(mlp: "MLP", states: t.Tensor, actions: t.Tensor, ln, net: int) -> t.Tensor:
+    """``mlp`` on [s | a] with LayerNorm between every hidden Linear and its ReLU, in torch on the tensors' device: what
+    the LN slice kernels compute (the critic modules' forward when LN is on; not a hot path)."""
+    holder, target = ln
+    x = t.cat([states, actions], dim=-1)
+    linears = [m for m in mlp.nn if isinstance(m, nn.Linear)]
+    for l, lin in enumerate(linears[:-1]):
+        g, b = holder.gamma_beta(net, l, target)
+        x = t.relu(t.nn.functional.layer_norm(t.nn.functional.linear(x, lin.weight, lin.bias), (lin.out_features,), g, b, holder.eps))
+    return t.nn.functional.linear(x, linears[-1].weight, linears[-1].bias)
+
+
 class Critic(nn.Module):
     def __init__(
         self,
@@ -371,9 +426,15 @@ class DoubleCritic(nn.Module):
         self.q2 = MLP(state_dim + action_dim, 1, hidden_units, hidden_activation)
 
     def forward(self, states: t.Tensor, actions: t.Tensor) -> tuple[t.Tensor, t.Tensor]:
+        ln = self.__dict__.get("_ln")
+        if ln is not None:
+            return _forward_sa_ln(self.q1, states, actions, ln, 0), _forward_sa_ln(self.q2, states, actions, ln, 1)
         return _forward_sa(self.q1, states, actions), _forward_sa(self.q2, states, actions)
 
     def Q1(self, states: t.Tensor, actions: t.Tensor) -> t.Tensor:
+        ln = self.__dict__.get("_ln")
+        if ln is not None:
+            return _forward_sa_ln(self.q1, states, actions, ln, 0)
         return _forward_sa(self.q1, states, actions)
 
 

@@ -20,9 +20,9 @@ import torch as t
 from torch import nn
 
 from oprl_amd import _capi
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, Temperature, check_prioritized_config, require_gpu
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, Temperature, check_layer_norm_config, check_prioritized_config, require_gpu
 from oprl_amd.algos.nn_functions import make_target_
-from oprl_amd.algos.nn_models import MLP, GaussianActor, _forward_sa, flatten_module_
+from oprl_amd.algos.nn_models import MLP, CriticLayerNorm, GaussianActor, _forward_sa, _forward_sa_ln, attach_layer_norm, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
 from oprl_amd.logging import LoggerProtocol
 
@@ -40,6 +40,9 @@ class EnsembleCritic(nn.Module):
             self.nets.append(net)
 
     def forward(self, state: t.Tensor, action: t.Tensor) -> t.Tensor:
+        ln = self.__dict__.get("_ln")
+        if ln is not None:
+            return t.cat(tuple(_forward_sa_ln(net, state, action, ln, i) for i, net in enumerate(self.nets)), dim=1)
         return t.cat(tuple(_forward_sa(net, state, action) for net in self.nets), dim=1)
 
 
@@ -66,6 +69,7 @@ class REDQ(Temperature, OffPolicyAlgorithm):
     no_fuse: bool = False         # (REDQ has no fused form: no effect)
     prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # f32 only: the learner refuses the others
+    layer_norm: bool = False      # Linear -> LayerNorm -> ReLU in the critics' hidden layers (RLPD / DroQ)
 
     actor: PolicyProtocol = field(init=False)
     critic: EnsembleCritic = field(init=False)
@@ -75,6 +79,7 @@ class REDQ(Temperature, OffPolicyAlgorithm):
 
     def create(self) -> "REDQ":
         check_prioritized_config(self)
+        check_layer_norm_config(self)
         dev = require_gpu(self.device)
         if not 1 <= self.n_critics <= _capi.OPRL_MAX_CRITICS:
             raise ValueError(f"REDQ: n_critics={self.n_critics} outside [1, {_capi.OPRL_MAX_CRITICS}]")
@@ -102,7 +107,12 @@ class REDQ(Temperature, OffPolicyAlgorithm):
             critic_group=self.critic, critic_mlps=self.critic.nets,
             critic_target_group=self.critic_target, critic_target_mlps=self.critic_target.nets,
             hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, log_alpha=self.log_alpha,
-            no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
+            no_fuse=self.no_fuse or self.prioritized or self.layer_norm, precision=self.precision)
+        if self.layer_norm:
+            self.critic_ln = CriticLayerNorm(self.n_critics).to(dev).make_state()
+            attach_layer_norm(self.critic, self.critic_ln, False)
+            attach_layer_norm(self.critic_target, self.critic_ln, True)
+            self.learner.set_layernorm(self.critic_ln)
         self._created = True
         return self
 

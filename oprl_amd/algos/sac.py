@@ -10,9 +10,9 @@ from dataclasses import dataclass, field
 import torch as t
 from torch import nn
 
-from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, Temperature, check_prioritized_config, require_gpu
+from oprl_amd.algos.base_algorithm import HipLearner, OffPolicyAlgorithm, Temperature, check_layer_norm_config, check_prioritized_config, require_gpu
 from oprl_amd.algos.nn_functions import make_target_
-from oprl_amd.algos.nn_models import DoubleCritic, GaussianActor, flatten_module_
+from oprl_amd.algos.nn_models import CriticLayerNorm, DoubleCritic, GaussianActor, attach_layer_norm, flatten_module_
 from oprl_amd.algos.protocols import PolicyProtocol
 from oprl_amd.logging import LoggerProtocol
 
@@ -37,6 +37,7 @@ class SAC(Temperature, OffPolicyAlgorithm):
     no_fuse: bool = False     # True: the generic per-net launch sequence instead of the fused kernels
     prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # "f32": exact-fp32 MFMA (parity mode); "bf16": bf16 MFMA inputs, fp32 accumulate / master / Adam (include/oprl_amd.h)
+    layer_norm: bool = False      # Linear -> LayerNorm -> ReLU in the critics' hidden layers (RLPD / DroQ): generic launch sequence, f32
 
     actor: PolicyProtocol = field(init=False)
     critic: nn.Module = field(init=False)
@@ -46,6 +47,7 @@ class SAC(Temperature, OffPolicyAlgorithm):
 
     def create(self) -> "SAC":
         check_prioritized_config(self)
+        check_layer_norm_config(self)
         dev = require_gpu(self.device)
         self.actor = GaussianActor(self.state_dim, self.action_dim, (256, 256),
                                    nn.ReLU(inplace=True), device=self.device).to(dev)
@@ -72,7 +74,12 @@ class SAC(Temperature, OffPolicyAlgorithm):
             critic_target_group=self.critic_target,
             critic_target_mlps=[self.critic_target.q1, self.critic_target.q2],
             hp=hp, max_batch=self.max_batch, export_grads=self.export_grads, log_alpha=self.log_alpha,
-            no_fuse=self.no_fuse or self.prioritized, precision=self.precision)
+            no_fuse=self.no_fuse or self.prioritized or self.layer_norm, precision=self.precision)
+        if self.layer_norm:
+            self.critic_ln = CriticLayerNorm(2).to(dev).make_state()
+            attach_layer_norm(self.critic, self.critic_ln, False)
+            attach_layer_norm(self.critic_target, self.critic_ln, True)
+            self.learner.set_layernorm(self.critic_ln)
         self._created = True
         return self
 

@@ -21,7 +21,7 @@ OBJ = HERE / "lib" / "obj"
 # without them).  OPRL_AMD_TRACE=1 makes _capi load this one.
 OUT_TRACE = HERE / "lib" / "liboprl_amd_trace.so"
 OBJ_TRACE = HERE / "lib" / "obj_trace"
-SOURCES = ["kernels.hip", "fused_ddpg.hip", "slice_tp.hip", "layerwise.hip", "dw_wide.hip", "p2p.hip", "replay.hip", "replay_prio.hip", "replay_nstep.hip", "replay_her.hip", "replay_mix.hip", "replay_returns.hip", "replay_rows.hip", "policy_act.hip", "policy_act_rows.hip", "per_seed.hip", "c51_seed.hip", "bc_seed.hip", "iql_seed.hip", "cql_seed.hip", "learner.hip",
+SOURCES = ["kernels.hip", "fused_ddpg.hip", "slice_tp.hip", "layerwise.hip", "dw_wide.hip", "p2p.hip", "replay.hip", "replay_prio.hip", "replay_nstep.hip", "replay_her.hip", "replay_mix.hip", "replay_returns.hip", "replay_rows.hip", "policy_act.hip", "policy_act_rows.hip", "per_seed.hip", "c51_seed.hip", "bc_seed.hip", "iql_seed.hip", "cql_seed.hip", "ln_slice.hip", "learner.hip",
            "learner_create.hip", "learner_dp.hip", "learner_generic.hip", "learner_group.hip", "learner_misc.hip", "learner_modes.hip", "learner_per.hip",
            "net_rounds.hip"]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]

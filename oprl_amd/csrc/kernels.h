@@ -84,7 +84,7 @@ struct MlpArgs {
   // host-side only (ignored by the kernels): where launch() draws the tag from, the exchange
   // area's size for the wrap-around reset
   unsigned* tp_tag_counter; size_t tp_xbuf_bytes;
-  void* reserved;                    // always null: padding in the place of a former host-side member, kept so that the layout the kernels take by value is unchanged
+  void* reserved;                    // host-side only: null, or the launch's LnView (ln_slice.h: a critic with layer normalisation — net_rounds.hip sends the pass to the LN kernels); in the place of a former host-side member, so that the layout the kernels take by value is unchanged
   // host-side only: this net's bf16 fragment packs per layer (bf16 learners; null otherwise) — a launcher
   // whose kernels run PrecBF16 moves them into net.pf / net.pb
   const float* pf16[kMaxLayers]; const float* pb16[kMaxLayers];

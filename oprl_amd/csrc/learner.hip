@@ -287,6 +287,7 @@ AdamScalars adam_scalars(const oprl_learner* h, double lr, int step, bool polyak
 // predicate for the launch and for the dW kernel that has to sum the dz1 partials it leaves.
 bool tp_generic(const oprl_learner* h, const oprl_net& n, int B) {
   if (!h->tp_generic_on || h->xbuf == nullptr) return false;
+  if (h->ln.on && &n != &h->cfg.actor) return false;            // (critics with LN run the single-CU LN kernels, ln_slice.hip)
   if (n.n_layers != 3 || n.dims[1] != 256 || n.dims[2] != 256) return false;
   if (n.dims[0] > 96 || n.dims[3] > kNarrowMax) return false;
   if (((h->S & 15) + h->A - 1) / 16 >= 4) return false;          // input-gradient column span

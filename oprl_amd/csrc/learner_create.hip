@@ -118,6 +118,7 @@ extern "C" int oprl_learner_create(const oprl_learner_config* cfg, oprl_learner*
   if (e == hipSuccess) e = init_fused_attrs();
   if (e == hipSuccess) e = init_slice_tp_attrs();
   if (e == hipSuccess) e = init_layerwise_attrs();
+  if (e == hipSuccess) e = init_ln_attrs();
   if (e != hipSuccess) { set_err("hipFuncSetAttribute: %s", hipGetErrorString(e)); delete h; return OPRL_ERR_HIP; }
   if (h->nc > 2) {
     bool ok = hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;

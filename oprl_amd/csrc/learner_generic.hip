@@ -27,6 +27,8 @@ MlpArgs base_args(oprl_learner* h, const oprl_net& n, bool target, int B) {
       a.pb16[l] = target ? nullptr : pk16 + pack16_off_bwd(n, l, h->planes);
     }
   }
+  if (h->ln.on)                      // (a critic of a learner with LN: its view goes with the launch, net_rounds.hip)
+    for (int j = 0; j < h->nc; ++j) if (&n == &h->cfg.critics[j]) a.reserved = target ? &h->ln.target[j] : &h->ln.online[j];
   a.B = B;
   a.action_dim = h->A;
   a.policy_noise = (float)h->cfg.hp.policy_noise;
@@ -268,7 +270,10 @@ int generic_critic_phase(oprl_learner* h, StepRows& rows, int B, const float* no
   else if (rows.w != nullptr) RC(weighted_critic_step(h, rows, B, n_min, st));
   else if (algo == OPRL_D4PG) RC(c51_critic_step(h, rows, B, st));
   else RC(plain_critic_step(h, rows, B, n_min, st));
-  // 4. dW + Adam (+ Polyak where the reference does it every step)
+  // 4. dW + Adam (+ Polyak where the reference does it every step); the LN parameters' step beside it, at the same step count
+  // (in front of dw_step, whose dw_commit moves the count once BOTH launches are out.  Should the dW launch itself fail — a hard
+  // error, the update is lost — gamma / beta have taken a step the weights and the count have not)
+  if (h->ln.on) RC(ln_adam_step(h, B, st));
   return dw_step(h, true, rows_dw, st);
 }
 

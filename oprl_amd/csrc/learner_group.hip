@@ -44,6 +44,10 @@ extern "C" int oprl_group_create(oprl_learner** learners, int32_t n, oprl_group*
       set_err("oprl_group_create: member %d has the behaviour-cloning mode on (oprl_learner_set_bc); packed learners run the fused launches, which have no BC step", i);
       return OPRL_ERR_STATE;
     }
+    if (h && h->ln.on) {
+      set_err("oprl_group_create: member %d has layer normalisation in its critics (oprl_learner_set_layernorm); packed learners run the fused launches, which have none", i);
+      return OPRL_ERR_STATE;
+    }
     if (h && h->iql.on) {
       set_err("oprl_group_create: member %d has the implicit-Q-learning mode on (oprl_learner_set_iql); packed learners run the fused launches, which have no value net", i);
       return OPRL_ERR_STATE;

@@ -20,6 +20,7 @@
 #include "../../include/oprl_amd.h"
 #include "host_err.h"
 #include "kernels.h"
+#include "ln_slice.h"
 #include "p2p.h"
 
 namespace oprl {
@@ -349,12 +350,13 @@ struct oprl_learner {
   DwXchg dw_xchg;
   PrefetchJob prefetch;        // step_n on the generic path (TQC): the next update's rows as riders of this update's k_lw_dact launch
   bool prefetch_pending = false, prefetch_done = false;
-  // the modes (learner_modes.h): prioritized weights, D4PG, TD3 + BC, implicit Q-learning, (calibrated) conservative Q-learning
+  // the modes (learner_modes.h): prioritized weights, D4PG, TD3 + BC, implicit Q-learning, (calibrated) conservative Q-learning, LayerNorm critics
   PerMode per;
   C51Mode c51;
   BcMode bc;
   IqlMode iql;
   CqlMode cql;
+  LnMode ln;
   float* batch_alt = nullptr;  // the second set of batch rows [Bmax x (2 S + A + 2)] the riders fill while an update reads the first
   MlpArgs fin_args[OPRL_MAX_CRITICS];   // TQC: the online critics' first-launch arguments of this update (generic_critic_phase step 1) ...
   int fin_tail0 = -1;          // ... of which [fin_tail0, nc) did not fit beside the actor's forward: offered to the target pass's head launch (-1: none pending)
@@ -523,6 +525,7 @@ int iql_critic_phase(oprl_learner* h, const StepRows& rows, int B, hipStream_t s
 int c51_action_grads(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
 int iql_action_grads(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
 int bc_action_grads(oprl_learner* h, const StepRows& rows, int B, hipStream_t st);
+int ln_adam_step(oprl_learner* h, int B, hipStream_t st);      // the LN parameters' step of the critic optimiser (k_ln_adam), at the step count of the dW launch beside it
 hipError_t launch_dw_prof(const oprl_learner* h, DwArgs a, hipStream_t st);
 void fill_items(const oprl_net& n, const NetWs& ws, std::vector<DwItem>& v, int* tiles, bool small_partial_tiles = false,
                 float* pk16 = nullptr, float* pk16_t = nullptr, int pl = 1);

@@ -60,3 +60,18 @@ struct CqlMode {
   int *ep = nullptr, *step = nullptr;
   float* g = nullptr;
 };
+
+// layer normalisation in the critics of a SAC / REDQ learner (oprl_learner_set_layernorm, ln_slice.hip):
+// the caller's four arrays [nc][2 hidden layers][gamma | beta][256] (parameters, target copy, Adam m and v), eps, and one
+// allocation of its own, made when the mode is turned on — the zh rows [nc][2][Bmax][256] and rstd [nc][2][Bmax] a
+// forward-only launch leaves for the backward-only one | the per-slice dgamma / dbeta sums [nc][2][slices at Bmax][2][256].
+// online[j] / target[j]: critic j's views as MlpArgs::reserved carries them to the launchers (net_rounds.hip)
+struct LnMode {
+  bool on = false;
+  float *theta = nullptr, *theta_target = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+  float eps = 0.f;
+  float* base = nullptr;
+  float* sums = nullptr;
+  int slices = 0;
+  oprl::LnView online[OPRL_MAX_CRITICS], target[OPRL_MAX_CRITICS];
+};

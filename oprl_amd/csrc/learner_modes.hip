@@ -24,7 +24,7 @@ static int mode_block(const char* what, size_t bytes, void** out) {
 }
 
 void oprl_host::free_modes(oprl_learner* h) {
-  void* const blocks[5] = {h->per.seed, h->bc.seed, h->iql.base, h->cql.base, h->cql.ep};
+  void* const blocks[6] = {h->per.seed, h->bc.seed, h->iql.base, h->cql.base, h->cql.ep, h->ln.base};
   for (void* p : blocks)
     if (p != nullptr) (void)hipFree(p);
 }
@@ -505,6 +505,7 @@ extern "C" int oprl_learner_set_cql(oprl_learner* h, double cql_alpha, int32_t n
   if (h->bf16 || h->x2) { set_err("oprl_learner_set_cql: the mode runs the exact-fp32 generic launch sequence only (precision f32)"); return OPRL_ERR_INVALID; }
   if (!cql_alpha_ok("oprl_learner_set_cql", cql_alpha)) return OPRL_ERR_INVALID;
   RC(refuse_fused_or_dp(h, "oprl_learner_set_cql", "wide critic step", "conservative-Q-learning step"));
+  if (h->ln.on) { set_err("oprl_learner_set_cql: the learner's critics carry layer normalisation (oprl_learner_set_layernorm), which the wide critic step does not run"); return OPRL_ERR_STATE; }
   if (m.base == nullptr) {
     const size_t Bm = (size_t)h->Bmax, slices = (size_t)n_slices(h->Bmax), A = (size_t)h->A, S = (size_t)h->S, nc = (size_t)h->nc;
     // (Pool::take rounds every block up to 256 bytes: 64 floats of slack for each of the 7 blocks)
@@ -534,6 +535,7 @@ extern "C" int oprl_learner_set_calql(oprl_learner* h, int32_t on) {
   if (!h) { set_err("oprl_learner_set_calql: null learner handle"); return OPRL_ERR_INVALID; }
   CqlMode& m = h->cql;
   if (!on) { m.cal_on = false; return OPRL_OK; }
+  if (h->ln.on) { set_err("oprl_learner_set_calql: the learner's critics carry layer normalisation (oprl_learner_set_layernorm), which the conservative penalty's step does not run"); return OPRL_ERR_STATE; }
   if (m.n == 0) {
     set_err("oprl_learner_set_calql: the conservative-Q-learning mode is off (oprl_learner_set_cql first): the calibrated bound is a form of its penalty");
     return OPRL_ERR_STATE;
@@ -705,4 +707,155 @@ int oprl_host::cql_critic_step(oprl_learner* h, const StepRows& rows, int B, hip
   return for_each_net(h, nc, h->w_critic, st, [&](int j) {
     return backward_args(h, c.critics[j], h->ws_critic[j], true, Bw, m.seed + (size_t)j * h->Bmax, 1);
   });
+}
+
+// ---------------------------------------------------------------- LayerNorm critics (ln_slice.hip)
+// Linear -> LayerNorm -> ReLU in both hidden layers of every critic of a SAC / REDQ learner (the RLPD / DroQ block).  The
+// parameters are the caller's, outside the nets' arenas; the critics' passes go to the LN slice kernels (net_rounds.hip),
+// and the parameters step with the critic optimiser (ln_adam_step, beside step 4 of the generic critic phase).
+extern "C" int oprl_learner_set_layernorm(oprl_learner* h, const oprl_layernorm* ln) {
+  const char* who = "oprl_learner_set_layernorm";
+  if (!h) { set_err("%s: null learner handle", who); return OPRL_ERR_INVALID; }
+  if (!ln) { set_err("%s: null oprl_layernorm", who); return OPRL_ERR_INVALID; }
+  const oprl_learner_config& c = h->cfg;
+  if (c.algo != OPRL_SAC && c.algo != OPRL_REDQ) {
+    set_err("%s: layer normalisation is built for the critics of SAC and REDQ learners (algo %d)", who, c.algo);
+    return OPRL_ERR_INVALID;
+  }
+  if (h->bf16 || h->x2) { set_err("%s: the LN slice kernels run exact fp32 only (precision f32)", who); return OPRL_ERR_INVALID; }
+  for (int j = 0; j < h->nc; ++j) {
+    const oprl_net& n = c.critics[j];
+    if (n.n_layers != kLnHidden + 1 || n.dims[1] != kLnWidth || n.dims[2] != kLnWidth || n.dims[3] != 1) {
+      set_err("%s: critic %d is not a three-layer net of hidden width %d with one output", who, j, kLnWidth);
+      return OPRL_ERR_INVALID;
+    }
+  }
+  if (!ln->theta || !ln->theta_target || !ln->adam_m || !ln->adam_v) { set_err("%s: null parameter array (theta, theta_target, adam_m, adam_v)", who); return OPRL_ERR_INVALID; }
+  if (!std::isfinite(ln->eps) || !(ln->eps > 0.f)) { set_err("%s: eps=%g must be finite and positive", who, (double)ln->eps); return OPRL_ERR_INVALID; }
+  RC(refuse_fused_or_dp(h, who, "LN kernels", "LN step"));
+  if (h->cql.n > 0) { set_err("%s: the learner's conservative-Q-learning mode is on (oprl_learner_set_cql), whose wide critic step has no LN form", who); return OPRL_ERR_STATE; }
+  LnMode& m = h->ln;
+  if (m.on) { set_err("%s: the mode is already on (it is set once, before the first update)", who); return OPRL_ERR_STATE; }
+  if (h->update_count > 0) { set_err("%s: the learner has run %lld updates; the mode is set before the first", who, (long long)h->update_count); return OPRL_ERR_STATE; }
+  const size_t Bm = (size_t)h->Bmax, slices = (size_t)n_slices(h->Bmax), nc = (size_t)h->nc;
+  const size_t n_zh = nc * kLnHidden * Bm * kLnWidth, n_rstd = nc * kLnHidden * Bm, n_sums = nc * kLnHidden * slices * 2 * kLnWidth;
+  float* p = nullptr;
+  RC(mode_block("layer-normalisation", (n_zh + n_rstd + n_sums + 3 * 64) * sizeof(float), (void**)&p));
+  Pool pool;
+  pool.base = reinterpret_cast<char*>(p); pool.cap = (n_zh + n_rstd + n_sums + 3 * 64) * sizeof(float);
+  float* zh = pool.take<float>(n_zh);
+  float* rstd = pool.take<float>(n_rstd);
+  m.sums = pool.take<float>(n_sums);
+  if (pool.used > pool.cap) { (void)hipFree(p); m.sums = nullptr; set_err("internal: the layer-normalisation rows overran their allocation"); return OPRL_ERR_STATE; }
+  m.base = p;
+  m.slices = (int)slices;
+  m.theta = ln->theta; m.theta_target = ln->theta_target; m.adam_m = ln->adam_m; m.adam_v = ln->adam_v;
+  m.eps = ln->eps;
+  for (int j = 0; j < h->nc; ++j) {
+    LnView v;
+    memset((void*)&v, 0, sizeof v);
+    v.eps = m.eps;
+    v.gb = m.theta_target + (size_t)j * kLnNetFloats;
+    m.target[j] = v;
+    v.gb = m.theta + (size_t)j * kLnNetFloats;
+    for (int l = 0; l < kLnHidden; ++l) {
+      v.zh[l] = zh + ((size_t)j * kLnHidden + l) * Bm * kLnWidth;
+      v.rstd[l] = rstd + ((size_t)j * kLnHidden + l) * Bm;
+    }
+    v.sums = m.sums + (size_t)j * kLnHidden * slices * 2 * kLnWidth;
+    v.sum_slices = (int)slices;
+    m.online[j] = v;
+  }
+  m.on = true;
+  return OPRL_OK;
+}
+
+// k_ln_adam: every critic's per-slice dgamma / dbeta sums of this update's critic step, added in slice order, and the
+// Adam (+ Polyak when critic_targets_due) step with lr_critic at the step count of the critics' dW launch — which the
+// caller makes next and which commits the count (dw_commit)
+int oprl_host::ln_adam_step(oprl_learner* h, int B, hipStream_t st) {
+  const LnMode& m = h->ln;
+  LnAdamArgs a;
+  memset((void*)&a, 0, sizeof a);
+  a.theta = m.theta; a.target = m.theta_target; a.m = m.adam_m; a.v = m.adam_v;
+  a.sums = m.sums;
+  a.n_nets = h->nc; a.n_slices = n_slices(B); a.sum_slices = m.slices;
+  a.ad = adam_scalars(h, h->cfg.hp.lr_critic, h->opt_step_critic + 1, critic_targets_due(h), 1.0f);
+  RC(profiled(1, st, [&] { return launch_ln_adam(a, st); }));
+  return OPRL_OK;
+}
+
+// One packed three-layer net of width 256 with LN parameters ln_theta [2][gamma | beta][256] on caller rows [x0 | x1]:
+// forward, and — given dout [B][n_out] — backward from those seed rows (SEED_PTR).  split = 0: one launch; 1: a
+// forward-only launch that keeps x, zh and rstd, then a backward-only launch that reloads them.  Row arrays hold `rows`
+// (>= B) rows per hidden layer: x / dz / zh [2][rows][256], rstd [2][rows]; dx1 [B][k1] the gradient over the x1 columns;
+// dln [2][2][256] the reduced dgamma | dbeta.  The kernel tests' entry point (tests/test_gpu_ln_slice.py).
+extern "C" int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1, int32_t k1,
+                           int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows, float* dz_rows,
+                           float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream) {
+  const char* who = "oprl_mlp_ln";
+  if (!net || !ln_theta || !x0 || !out || !x_rows || !zh_rows || !rstd_rows) { set_err("%s: null argument", who); return OPRL_ERR_INVALID; }
+  if (dout != nullptr && (!dz_rows || !dln)) { set_err("%s: a backward (dout) needs dz_rows and dln", who); return OPRL_ERR_INVALID; }
+  int width = 0;
+  RC(check_net(*net, "net", &width));
+  if (net->n_layers != kLnHidden + 1 || width != kLnWidth) { set_err("%s: the LN kernels take a three-layer net of hidden width %d", who, kLnWidth); return OPRL_ERR_INVALID; }
+  if (B < 1 || rows < B || rows > (1 << 22)) { set_err("%s: need 1 <= B (%d) <= rows (%d) <= 2^22", who, B, rows); return OPRL_ERR_INVALID; }
+  if (k0 < 1 || k0 + (x1 ? k1 : 0) != net->dims[0] || (x1 && k1 < 1)) { set_err("%s: k0+k1=%d != input dim %d", who, k0 + (x1 ? k1 : 0), net->dims[0]); return OPRL_ERR_INVALID; }
+  if (dx1 != nullptr && (!x1 || !dout || k1 > kNarrowMax)) { set_err("%s: dx1 needs x1 (k1 <= %d) and dout", who, kNarrowMax); return OPRL_ERR_INVALID; }
+  if (!std::isfinite(eps) || !(eps > 0.f)) { set_err("%s: eps=%g must be finite and positive", who, (double)eps); return OPRL_ERR_INVALID; }
+  hipStream_t st = (hipStream_t)stream;
+  HIPC(init_ln_attrs());
+  RC(fresh32(net, st));
+  const int slices = n_slices(B), nout = net->dims[net->n_layers];
+  float* sums = nullptr;
+  if (dout != nullptr) RC(mode_block("oprl_mlp_ln", (size_t)kLnHidden * slices * 2 * kLnWidth * sizeof(float), (void**)&sums));
+  MlpArgs a;
+  memset(&a, 0, sizeof a);
+  a.net = net_view(*net, false);
+  a.B = B;
+  a.x0 = x0; a.k0 = k0; a.x1 = x1; a.k1 = x1 ? k1 : 0;
+  a.out = out; a.ldo = nout;
+  LnView v;
+  memset((void*)&v, 0, sizeof v);
+  v.gb = ln_theta; v.eps = eps;
+  for (int l = 0; l < kLnHidden; ++l) {
+    a.Xg[l + 1] = x_rows + (size_t)l * rows * kLnWidth;
+    if (dout != nullptr) a.dYg[l] = dz_rows + (size_t)l * rows * kLnWidth;
+    v.zh[l] = zh_rows + (size_t)l * rows * kLnWidth;
+    v.rstd[l] = rstd_rows + (size_t)l * rows;
+  }
+  a.seed_mode = SEED_PTR;
+  a.seed.p0 = dout; a.seed.ld0 = nout;
+  if (dx1 != nullptr) { a.dact_col0 = k0; a.dact_cols = k1; a.dact = dx1; a.lddact = k1; }
+  hipError_t e = hipSuccess;
+  if (dout == nullptr || split) {
+    MlpArgs f = a;
+    f.do_fwd = 1;
+    e = launch_mlp_slice_ln(f, v, st);
+  }
+  if (e == hipSuccess && dout != nullptr) {
+    MlpArgs b = a;
+    b.do_fwd = split ? 0 : 1; b.do_bwd = 1;
+    if (split) b.out = nullptr;
+    LnView vb = v;
+    vb.sums = sums; vb.sum_slices = slices;
+    e = launch_mlp_slice_ln(b, vb, st);
+    if (e == hipSuccess) {
+      LnAdamArgs r;
+      memset((void*)&r, 0, sizeof r);
+      r.theta = dln; r.m = dln; r.v = dln;          // (do_adam 0: only the reduced gradient is written, to gout)
+      r.sums = sums; r.gout = dln;
+      r.n_nets = 1; r.n_slices = slices; r.sum_slices = slices;
+      set_adam(r.ad, 0.0, 0.9, 0.999, 1e-8, 0.0);
+      set_step(r.ad, 1); r.ad.grad_scale = 1.0f; r.ad.do_adam = 0;
+      e = launch_ln_adam(r, st);
+    }
+  }
+  if (sums != nullptr) {
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(sums);
+    if (e == hipSuccess) e = e2;
+  }
+  HIPC(e);
+  return OPRL_OK;
 }

@@ -34,6 +34,10 @@ int per_check(const oprl_learner* h, const char* who) {
     set_err("%s: the learner's conservative-Q-learning mode is on (oprl_learner_set_cql), whose penalty takes no importance weights", who);
     return OPRL_ERR_STATE;
   }
+  if (h->ln.on) {
+    set_err("%s: the learner's critics carry layer normalisation (oprl_learner_set_layernorm), whose kernels take no importance weights", who);
+    return OPRL_ERR_STATE;
+  }
   if (h->fused) {
     set_err("%s: the learner's fused launch form is on, which applies no importance weights; create it with no_fuse", who);
     return OPRL_ERR_STATE;

@@ -153,9 +153,43 @@ int launch_few(oprl_learner* h, MlpArgs* a, int n, int width, hipStream_t st) {
   return OPRL_OK;
 }
 
+// A net pass that carries an LN view (MlpArgs::reserved: a critic of a learner with layer normalisation)
+// goes to the LN kernels (ln_slice.hip).  What of the view this launch uses: the per-slice dgamma / dbeta sums only where
+// the dW launch follows (forward + backward with the dY rows stored: the critic step), the zh / rstd rows only where the
+// pass is split into a forward-only and a backward-only launch
+LnView ln_view_of(const MlpArgs& a) {
+  LnView v = *static_cast<const LnView*>(a.reserved);
+  const bool whole = a.do_fwd && a.do_bwd;
+  if (!whole || a.dYg[0] == nullptr) v.sums = nullptr;
+  if (whole || (a.do_fwd && a.Xg[1] == nullptr))
+    for (int l = 0; l < kLnHidden; ++l) { v.zh[l] = nullptr; v.rstd[l] = nullptr; }
+  return v;
+}
+
+// a round of n LN nets: ceil(n / kMaxMulti) k_mlp_slice_multi_ln launches, whatever n
+int launch_ln_round(MlpArgs* a, int n, int width, hipStream_t st) {
+  if (width != kLnWidth) { set_err("internal: an LN net pass at width %d", width); return OPRL_ERR_STATE; }
+  for (int j0 = 0; j0 < n; j0 += kMaxMulti) {
+    const int m = std::min(kMaxMulti, n - j0);
+    LnView v[kMaxMulti];
+    for (int k = 0; k < m; ++k) {
+      if (a[j0 + k].reserved == nullptr) { set_err("internal: a round of nets with and without LN"); return OPRL_ERR_STATE; }
+      v[k] = ln_view_of(a[j0 + k]);
+    }
+    RC(profiled(0, st, [&] { return launch_mlp_slice_multi_ln(a + j0, v, m, st); }));
+  }
+  return OPRL_OK;
+}
+
 }  // namespace
 
 int launch(const MlpArgs& a0, int width, hipStream_t st) {
+  if (a0.reserved != nullptr) {
+    if (width != kLnWidth) { set_err("internal: an LN net pass at width %d", width); return OPRL_ERR_STATE; }
+    const LnView v = ln_view_of(a0);
+    RC(profiled(0, st, [&] { return launch_mlp_slice_ln(a0, v, st); }));
+    return OPRL_OK;
+  }
   MlpArgs a = a0;
   const bool tp = takes_cluster(a, width);
   if (tp) RC(draw_tag(a, st));
@@ -166,6 +200,7 @@ int launch(const MlpArgs& a0, int width, hipStream_t st) {
 int launch_round(oprl_learner* h, MlpArgs* a, int n, int width, hipStream_t st) {
   // measured: the event fork/join costs more than it saves for 2 nets (TD3 8.8k -> 7.7k/s),
   // pays for the 5 quantile critics of TQC (673 -> 1206/s)
+  if (n > 0 && a[0].reserved != nullptr) return launch_ln_round(a, n, width, st);
   if (n == 2) return launch_pair(h, a, width, st);
   if (n > 2 && n <= kMaxMulti) return launch_few(h, a, n, width, st);
   if (n > kMaxMulti && h->tp_generic_on) {

@@ -1,5 +1,5 @@
 """update() throughput of the algorithms at the BASELINE.json configs
-(parity-test cases 2-4 + DDPG, REDQ, D4PG, TD3BC, IQL, CQL), fixed synthetic minibatch resident in HBM, noise
+(parity-test cases 2-4 + DDPG, REDQ, D4PG, TD3BC, IQL, CQL, LayerNorm critics), fixed synthetic minibatch resident in HBM, noise
 drawn on device — one Python call per update, so the fast paths are bound by the
 call rate — and, second column, oprl_learner_step_n (sampling from an HBM replay +
 update, K steps per call).  Not the headline bench (bench.py); numbers for DESIGN.md.
@@ -9,6 +9,7 @@ update, K steps per call).  Not the headline bench (bench.py); numbers for DESIG
     python tools/bench_algos.py 2000 TD3BC TD3                      
     python tools/bench_algos.py 2000 IQL TD3-walker TD3BC-walker    (all three at walker dims)
     python tools/bench_algos.py 2000 CQL SAC-walker                 (the penalty's cost over SAC)
+    python tools/bench_algos.py 2000 REDQ REDQ-LN SAC-walker SAC-LN (LayerNorm critics' cost)
 
 Two or more algorithm names: each names the first case that starts with it, created as a ``no_fuse`` learner so that
 all of them take the generic launch sequence (D4PG has no other), and the timed passes alternate
@@ -42,7 +43,9 @@ CASES = [("DDPG walker B=256", DDPG, 24, 6, 256, {}),
          ("TD3-walker pf=1 B=256", TD3, 24, 6, 256, dict(log_every=10 ** 9, policy_freq=1)),      # (an actor step on every update, as IQL)
          ("TD3BC-walker pf=1 B=256", TD3BC, 24, 6, 256, dict(log_every=10 ** 9, policy_freq=1)),
          ("CQL walker N=10 B=256", CQL, 24, 6, 256, dict(log_every=10 ** 9)),      # (7936 wide rows in the critic step)
-         ("SAC-walker B=256", SAC, 24, 6, 256, dict(log_every=10 ** 9))]           # (the fixed temperature, as CQL's default)
+         ("SAC-walker B=256", SAC, 24, 6, 256, dict(log_every=10 ** 9)),           # (the fixed temperature, as CQL's default)
+         ("SAC-LN walker B=256", SAC, 24, 6, 256, dict(log_every=10 ** 9, layer_norm=True)),      # (LayerNorm critics: the single-CU LN slice kernels)
+         ("REDQ-LN walker N=10 M=2 B=256", REDQ, 24, 6, 256, dict(log_every=10 ** 9, layer_norm=True))]
 PRECISIONS = ("f32", "bf16", "x2")
 
 
@@ -121,7 +124,7 @@ def main():
     for name, cls, S, A, B, kw in [(f"{c[0]} [{p}]", *c[1:5], dict(c[5], precision=p)) for c in CASES for p in precs]:
         if only and only not in name:
             continue
-        if cls in (D4PG, TD3BC, IQL, CQL) and kw["precision"] != "f32":
+        if (cls in (D4PG, TD3BC, IQL, CQL) or kw.get("layer_norm")) and kw["precision"] != "f32":
             continue                    # (f32 only)
         b = Bench(name, cls, S, A, B, kw)
         for _rep in range(2):           # best of two passes (the first one still sees clock ramp-up)
