@@ -5,7 +5,6 @@ tolerance, the calibrated oracle's seeds are autograd's, and configs/calql.py re
 built or a file is looked at."""
 from __future__ import annotations
 
-import ctypes as C
 from pathlib import Path
 
 import numpy as np
@@ -19,22 +18,14 @@ from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import calql_oracle as cal
 from tests.config_scripts import load_config
+from tests.support import assert_abi_bound, assert_class_refuses, assert_source_built, small_nets
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_replay_returns": 7, "oprl_cql_seed_cal": 19, "oprl_learner_set_calql": 2, "oprl_learner_update_calql": 11}
 
 
 def test_the_abi_additions_are_bound():
-    assert _capi.OPRL_ABI_VERSION == 4 and "calql" not in _capi.ALGO and len(_capi.ALGO) == 6      # a form of a mode
-    lib = _capi.load()
-    assert lib.oprl_abi_version() == 4
-    header = (ROOT / "include" / "oprl_amd.h").read_text()
-    assert "#define OPRL_ABI_VERSION 4" in header
-    for name, n_args in ENTRIES.items():
-        assert hasattr(lib, name)
-        res, args = _capi.SIGNATURES[name]
-        assert res is C.c_int and len(args) == n_args
-        assert f"int {name}(" in header
+    lib, _header = assert_abi_bound(ENTRIES, mode_name="calql")          # a form of a mode
     # oprl_cql_seed's signature and g
     assert len(_capi.SIGNATURES["oprl_cql_seed_cal"][1]) == len(_capi.SIGNATURES["oprl_cql_seed"][1]) + 1
     # null handles and pointers are refused without a GPU
@@ -45,9 +36,7 @@ def test_the_abi_additions_are_bound():
 
 
 def test_the_build_lists_the_new_source():
-    from oprl_amd import build
-    assert "replay_returns.hip" in build.SOURCES
-    assert (build.CSRC / "replay_returns.hip").exists()
+    assert_source_built("replay_returns", header=False)
 
 
 def test_exports():
@@ -69,14 +58,7 @@ def test_exports():
 ], ids=["x2", "bf16", "export_grads", "prioritized", "alpha-negative", "N-17"])
 def test_the_class_refuses_before_any_gpu_call(kw, msg, monkeypatch):
     import oprl_amd.algos.sac as mod
-    monkeypatch.setattr(mod, "require_gpu", lambda device: pytest.fail("the GPU was asked for"))
-    with pytest.raises(ValueError, match=msg):
-        CalQL(logger=NullLogger(), state_dim=4, action_dim=2, **kw)
-    algo = CalQL(logger=NullLogger(), state_dim=4, action_dim=2)
-    for k, v in kw.items():
-        setattr(algo, k, v)
-    with pytest.raises(ValueError, match=msg):
-        algo.create()
+    assert_class_refuses(CalQL, mod, kw, msg, monkeypatch)
 
 
 def test_update_needs_returns():
@@ -151,9 +133,8 @@ def test_mixed_returns_split_by_row_index():
 # ---- the calibrated oracle -------------------------------------------------------------------------------------------------
 def small_oracle(**kw):
     S, A = 5, 3
-    nets = [fx.make_net(11, [S, 16, 16, 2 * A]), fx.make_net(12, [S + A, 16, 16, 1]), fx.make_net(13, [S + A, 16, 16, 1])]
     kw.setdefault("n_actions", 4)
-    return cal.CalQLOracle(S, A, *nets, **kw), S, A
+    return cal.CalQLOracle(S, A, *small_nets(S, A, gaussian=True), **kw), S, A
 
 
 def draws(seed, B, A, N):

@@ -4,20 +4,19 @@ refuses before the GPU is touched, the oracle's hand-written seeds are autograd'
 critics at the GPU comparison's own shapes."""
 from __future__ import annotations
 
-import ctypes as C
 import sys
 from pathlib import Path
 
 import pytest
 import torch as t
 
-from oprl_amd import _capi
 from oprl_amd.algos.cql import CQL, wide_rows
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import cql_oracle as co
 from tests import scenarios as sc
 from tests.config_scripts import load_config
+from tests.support import assert_abi_bound, assert_class_refuses, assert_source_built, small_nets
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_learner_set_cql": 3, "oprl_learner_read_cql": 3, "oprl_learner_set_cql_noise": 3, "oprl_cql_rows": 16,
@@ -25,18 +24,7 @@ ENTRIES = {"oprl_learner_set_cql": 3, "oprl_learner_read_cql": 3, "oprl_learner_
 
 
 def test_the_abi_additions_are_bound():
-    assert _capi.OPRL_ABI_VERSION == 4 and "cql" not in _capi.ALGO and len(_capi.ALGO) == 6   # a mode, not an algorithm
-    lib = _capi.load()
-    assert lib.oprl_abi_version() == 4
-    header = (ROOT / "include" / "oprl_amd.h").read_text()
-    assert "#define OPRL_ABI_VERSION 4" in header
-    for name, n_args in ENTRIES.items():
-        assert hasattr(lib, name)
-        res, args = _capi.SIGNATURES[name]
-        assert res is C.c_int and len(args) == n_args
-        assert f"int {name}(" in header
-    # the hyper-parameter struct is where it was: CQL is no field of it
-    assert [f[0] for f in _capi.OprlHparams._fields_][-2:] == ["v_min", "v_max"]
+    lib, _header = assert_abi_bound(ENTRIES, mode_name="cql")            # a mode, not an algorithm: CQL is no field of the hparams
     # null arguments are refused without a GPU
     assert lib.oprl_learner_set_cql(None, 5.0, 10) == -1 and b"null" in lib.oprl_last_error()
     assert lib.oprl_learner_read_cql(None, None, None) == -1 and b"null" in lib.oprl_last_error()
@@ -46,9 +34,7 @@ def test_the_abi_additions_are_bound():
 
 
 def test_the_build_lists_the_new_source():
-    from oprl_amd import build
-    assert "cql_seed.hip" in build.SOURCES
-    assert (build.CSRC / "cql_seed.hip").exists() and (build.CSRC / "cql_seed.h").exists()
+    assert_source_built("cql_seed")
 
 
 def test_exports_and_the_workspace_the_class_asks_for():
@@ -118,14 +104,7 @@ def test_the_class_refuses_before_any_gpu_call(kw, msg, monkeypatch):
     """ValueError at construction; and again from create() for fields set afterwards — before require_gpu, which a
     machine without a GPU would fail with RuntimeError instead."""
     import oprl_amd.algos.sac as mod
-    monkeypatch.setattr(mod, "require_gpu", lambda device: pytest.fail("the GPU was asked for"))
-    with pytest.raises(ValueError, match=msg):
-        CQL(logger=NullLogger(), state_dim=4, action_dim=2, **kw)
-    algo = CQL(logger=NullLogger(), state_dim=4, action_dim=2)
-    for k, v in kw.items():
-        setattr(algo, k, v)
-    with pytest.raises(ValueError, match=msg):
-        algo.create()
+    assert_class_refuses(CQL, mod, kw, msg, monkeypatch)
 
 
 def test_a_prioritized_buffer_is_refused():
@@ -140,9 +119,8 @@ def test_a_prioritized_buffer_is_refused():
 # ---- the oracle ----------------------------------------------------------------------------------------------------------
 def small_oracle(**kw):
     S, A = 5, 3
-    nets = [fx.make_net(11, [S, 16, 16, 2 * A]), fx.make_net(12, [S + A, 16, 16, 1]), fx.make_net(13, [S + A, 16, 16, 1])]
     kw.setdefault("n_actions", 4)
-    return co.CQLOracle(S, A, *nets, **kw), S, A
+    return co.CQLOracle(S, A, *small_nets(S, A, gaussian=True), **kw), S, A
 
 
 def draws(seed, B, A, N):

@@ -3,7 +3,6 @@ configs/d4pg.py parses its flags, what the Python class refuses it refuses befor
 scatter projection is the kernel's gather formula."""
 from __future__ import annotations
 
-import ctypes as C
 import sys
 from pathlib import Path
 
@@ -16,19 +15,15 @@ from oprl_amd.algos.d4pg import D4PG
 from oprl_amd.logging import NullLogger
 from tests import d4pg_oracle as do
 from tests.config_scripts import load_config
+from tests.support import assert_abi_bound, assert_class_refuses, assert_source_built
 
 ROOT = Path(__file__).resolve().parents[1]
 
 
 def test_the_abi_additions_are_bound():
-    assert _capi.ALGO["d4pg"] == 5 and _capi.OPRL_ABI_VERSION == 4
-    lib = _capi.load()
-    assert lib.oprl_abi_version() == 4
-    assert hasattr(lib, "oprl_c51_seed")
-    res, args = _capi.SIGNATURES["oprl_c51_seed"]
-    assert res is C.c_int and len(args) == 14
-    header = (ROOT / "include" / "oprl_amd.h").read_text()
-    assert "OPRL_D4PG = 5" in header and "int oprl_c51_seed(" in header and "#define OPRL_ABI_VERSION 4" in header
+    assert _capi.ALGO["d4pg"] == 5
+    lib, header = assert_abi_bound({"oprl_c51_seed": 14})
+    assert "OPRL_D4PG = 5" in header
     names = [f[0] for f in _capi.OprlHparams._fields_]
     assert names[-2:] == ["v_min", "v_max"] and names[-3] == "n_min"          # appended: no earlier field moved
     assert _capi.OprlHparams.v_min.offset == _capi.OprlHparams.n_min.offset + 8   # (the int32 tail is padded to 8)
@@ -39,9 +34,7 @@ def test_the_abi_additions_are_bound():
 
 
 def test_the_build_lists_the_new_source():
-    from oprl_amd import build
-    assert "c51_seed.hip" in build.SOURCES
-    assert (build.CSRC / "c51_seed.hip").exists() and (build.CSRC / "c51_seed.h").exists()
+    assert_source_built("c51_seed")
 
 
 def test_exports():
@@ -91,14 +84,7 @@ def test_the_class_refuses_before_any_gpu_call(kw, msg, monkeypatch):
     """ValueError at construction; and again from create() for fields set afterwards — before require_gpu, which a
     machine without a GPU would fail with RuntimeError instead."""
     import oprl_amd.algos.d4pg as mod
-    monkeypatch.setattr(mod, "require_gpu", lambda device: pytest.fail("the GPU was asked for"))
-    with pytest.raises(ValueError, match=msg):
-        D4PG(logger=NullLogger(), state_dim=4, action_dim=2, **kw)
-    algo = D4PG(logger=NullLogger(), state_dim=4, action_dim=2)
-    for k, v in kw.items():
-        setattr(algo, k, v)
-    with pytest.raises(ValueError, match=msg):
-        algo.create()
+    assert_class_refuses(D4PG, mod, kw, msg, monkeypatch)
 
 
 def test_the_prioritized_refusal_names_the_follow_up():

@@ -29,11 +29,11 @@ from oracle import fixtures as fx
 from tests import calql_oracle as cal
 from tests import cql_oracle as co
 from tests import scenarios as sc
-from tests.test_gpu_cql import (ENV, GAMMA, TOL, assert_same_state, batches, counters, critic_gates, learner_state, make,
-                                oracle_state, plain_step, refused, replay)
+from tests.support import INVALID, STATE, check_resume, check_step_n_equals_loop, counters, refused
+from tests.test_gpu_cql import (ENV, GAMMA, TOL, assert_same_state, batches, critic_gates, learner_state, make, oracle_state,
+                                plain_step, replay)
 
 pytestmark = pytest.mark.gpu
-INVALID, STATE = -1, -3
 SHAPES = ((16, 2), (37, 2))
 NEG_INF = -float("inf")
 
@@ -170,19 +170,17 @@ def test_step_n_equals_sample_returns_update_bitwise(kind):
     """step_n(3) is bit for bit three rounds of sample(return_indices=True) + returns_to_go (the learner's gamma) +
     update(returns=) at the same counters, and the returns are not trivial."""
     buf = prior_replay() if kind == "prior-data" else replay(kind == "nstep3")
-    fused, loop = make_cal(RB, tune_alpha=True), make_cal(RB, tune_alpha=True)
-    loop.load_state_dict(fused.state_dict())
-    for seed in (3, 5):
-        fused.learner.step_n(buf.handle, 3, RB, seed=seed)
-        buf.seed = seed
-        for _ in range(3):
-            buf._sample_counter = loop.update_step
-            rows, (ep, step) = buf.sample(RB, return_indices=True)[:2]
-            g = buf.returns_to_go(ep, step, gamma=loop.gamma)
-            assert float(g.abs().max()) > 0 and bool(t.isfinite(g).all())
-            loop.update(*rows, returns=g)
-        assert_same_state(fused, loop)
-    assert fused.update_step == 6 and loop.gamma == GAMMA
+
+    def sample_returns_update(loop, buf, B):
+        rows, (ep, step) = buf.sample(B, return_indices=True)[:2]
+        g = buf.returns_to_go(ep, step, gamma=loop.gamma)
+        assert float(g.abs().max()) > 0 and bool(t.isfinite(g).all())
+        loop.update(*rows, returns=g)
+        return rows
+
+    fused, loop, _ = check_step_n_equals_loop(lambda: (make_cal(RB, tune_alpha=True), make_cal(RB, tune_alpha=True)), buf, RB,
+                                              one=sample_returns_update)
+    assert fused.update_step == 6 and loop.gamma == GAMMA and len(fused.state_dict()["targets"]) == 1
     a = fused.learner.read_cql()
     assert a == loop.learner.read_cql() and a["gap1"] != 0 and 0 < a["bound_rate"] < 1
     # update_from_buffer reaches step_n: one more round each
@@ -198,17 +196,8 @@ def test_resume():
     form has no state of its own, and create() turns it on."""
     B = 37
     data = batches(B, 4)
-    a = make_cal(B, tune_alpha=True)
-    for x in data[:2]:
-        cal_step(a, x)
-    sd = a.state_dict()
-    b = make_cal(B, tune_alpha=True)
-    b.load_state_dict(sd)
-    for x in data[2:]:
-        cal_step(a, x)
-        cal_step(b, x)
-    assert a.update_step == 4
-    assert_same_state(a, b)
+    a, b, sd = check_resume(lambda: make_cal(B, tune_alpha=True), cal_step, data, 2)
+    assert a.update_step == 4 and len(sd["targets"]) == 1
     assert not t.equal(a.state_dict()["critic"], sd["critic"])
     with pytest.raises(RuntimeError, match="returns"):
         b.learner.update(*(v.cuda() for v in data[0]))

@@ -26,14 +26,16 @@ from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import cql_oracle as co
 from tests import scenarios as sc
+from tests import support
 from tests.hip_adapters import cpu_params, hip_adam, load_params
+from tests.support import INVALID, STATE, check_resume, check_step_n_equals_loop, counters, random_replay, refused  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TOL = 2e-5                          # network outputs (tests/test_gpu_algos.py)
 GAMMA = 0.99
 ENV = co.ENV
-KEYS = ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v")
+NSTEP = 3
 
 
 def make(B, N=2, cls=CQL, fixture_nets=False, env=ENV, **kw):
@@ -134,18 +136,9 @@ def test_cql_matches_the_oracle(B, N, tune):
 
 
 # ---- bitwise links -----------------------------------------------------------------------------------------------------
-def assert_same_state(a, b):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
-    x, y = a.state_dict(), b.state_dict()
-    assert x["counters"] == y["counters"], (x["counters"], y["counters"])
-    for k in KEYS:
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    assert len(x["targets"]) == len(y["targets"]) == 1          # (SAC: the critics' targets; the actor has none)
-    assert t.equal(x["targets"][0], y["targets"][0]), "targets"
-    if "log_alpha" in x:
-        assert all(t.equal(p, q) for p, q in zip(x["log_alpha"], y["log_alpha"]))
+def assert_same_state(a, b, **kw):       # kept: the shared check plus SAC's "exactly one target list" at this call site
+    assert len(a.state_dict()["targets"]) == 1          # (SAC: the critics' targets; the actor has none)
+    support.assert_same_state(a, b, **kw)
 
 
 @pytest.mark.parametrize("tune", [False, True], ids=["alpha-fixed", "alpha-tuned"])
@@ -196,26 +189,11 @@ def test_a_fused_sac_learner_of_the_same_process_is_untouched():
     assert_same_state(straight, around)
 
 
-RB, E, LEP, NSTEP = 64, 40, 30, 3
+RB = 64
 
 
 def replay(nstep):
-    """E episodes of random length with 10 % done rows, every row random normal; n-step mode or plain."""
-    from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
-    from oprl_amd.buffers.nstep_buffer import NStepEpisodicReplayBuffer
-    S, A = fx.ENVS[ENV]
-    kw = dict(buffer_size_transitions=E * LEP, state_dim=S, action_dim=A, max_episode_lenth=LEP, device="cuda", seed=7)
-    buf = (NStepEpisodicReplayBuffer(n_step=NSTEP, gamma=GAMMA, **kw) if nstep else EpisodicReplayBuffer(**kw)).create()
-    gen = t.Generator(device="cuda").manual_seed(1000)
-    for v in buf._tensors.values():
-        v.copy_(t.randn(v.shape, device="cuda", generator=gen))
-    buf._tensors["dones"].copy_(t.as_tensor((np.random.RandomState(6).rand(E, LEP, 1) < 0.1).astype(np.float32)))
-    lens = [int(x) for x in np.random.RandomState(4).randint(1, LEP + 1, size=E)]
-    buf.ep_lens = lens + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = sum(lens)
-    buf._lens_dirty = True
-    return buf
+    return random_replay(ENV, NSTEP if nstep else None, GAMMA)
 
 
 @pytest.mark.parametrize("nstep", [False, True], ids=["plain", "nstep3"])
@@ -223,16 +201,8 @@ def test_step_n_equals_sample_then_update_bitwise(nstep):
     """step_n(3) is bit for bit three sample() + update() pairs (Philox draws at the same counters), over a plain replay
     and over an n-step replay (n = 3)."""
     buf = replay(nstep)
-    fused, loop = make(RB, tune_alpha=True), make(RB, tune_alpha=True)
-    loop.load_state_dict(fused.state_dict())
-    for seed in (3, 5):
-        fused.learner.step_n(buf.handle, 3, RB, seed=seed)
-        buf.seed = seed
-        for _ in range(3):
-            buf._sample_counter = loop.update_step
-            loop.update(*buf.sample(RB))
-        assert_same_state(fused, loop)
-    assert fused.update_step == 6
+    fused, loop, _ = check_step_n_equals_loop(lambda: (make(RB, tune_alpha=True), make(RB, tune_alpha=True)), buf, RB)
+    assert fused.update_step == 6 and len(fused.state_dict()["targets"]) == 1
     assert not t.equal(fused.learner.critic_arena.cpu(), make(RB, tune_alpha=True).state_dict()["critic"])
     assert fused.learner.read_cql() == loop.learner.read_cql() and fused.learner.read_cql()["gap1"] != 0
 
@@ -287,36 +257,12 @@ def test_resume():
     """A checkpoint taken after two updates, loaded into a fresh learner, gives bit-identical state after two more: the
     mode has no state of its own."""
     B = 100
-    data = batches(B, 4)
-    a = make(B, tune_alpha=True)
-    for x in data[:2]:
-        plain_step(a, x)
-    sd = a.state_dict()
-    b = make(B, tune_alpha=True)
-    b.load_state_dict(sd)
-    for x in data[2:]:
-        plain_step(a, x)
-        plain_step(b, x)
-    assert a.update_step == 4
-    assert_same_state(a, b)
+    a, _b, sd = check_resume(lambda: make(B, tune_alpha=True), plain_step, batches(B, 4), 2)
+    assert a.update_step == 4 and len(sd["targets"]) == 1
     assert not t.equal(a.state_dict()["critic"], sd["critic"])
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------
-INVALID, STATE = -1, -3
-
-
-def refused(rc, status, word):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert word in msg, (word, msg)
-
-
-def counters(algo):
-    t.cuda.synchronize()
-    return algo.learner.state_dict()["counters"]
-
-
 def test_refusals():
     """Every case DESIGN.md §19 lists as refused returns its status with a message that names the reason; the update
     count and all Adam step counts stay where they were, and a refused learner goes on as what it was."""

@@ -30,7 +30,9 @@ from oracle import fixtures as fx
 from tests import nstep_oracle as no
 from tests import scenarios as sc
 from tests.d4pg_oracle import D4PGOracle
-from tests.hip_adapters import cpu_params, hip_adam, load_params
+from tests.hip_adapters import cpu_params, load_params
+from tests.support import (INVALID, as_np, assert_same_state, check_resume, check_step_n_equals_loop, loop_updates, pair_adam,
+                           pair_nets, pair_q_y, random_replay, refused, run_pair, to_double, worst_ratio)
 
 pytestmark = pytest.mark.gpu
 
@@ -74,41 +76,18 @@ def assert_the_batches_reach_every_case(data, v_min, v_max):
         assert int((~low & ~high).sum()) >= 1
 
 
-def run_pair(algo, oracles, data):
-    for batch in data:
-        algo.update(*(x.cuda() for x in batch))
-        f = [x.double() for x in batch]
-        for o in oracles:
-            o.update(*f)
-    t.cuda.synchronize()
-    algo.learner.check()
+def step(algo, batch):
+    algo.update(*(x.cuda() for x in batch))
 
 
 def got_and_want(algo, o, B):
     got, want = {}, {}
-    for name, mod, ref in (("critic", algo.critic, o.critic), ("critic_target", algo.critic_target, o.critic_target),
-                           ("actor", algo.actor, o.actor), ("actor_target", algo.actor_target, o.actor_target)):
-        for l, (x, y) in enumerate(zip(cpu_params(mod), ref)):
-            got[f"u.{name}.{l}"], want[f"u.{name}.{l}"] = x, y
-    for which, opt in (("critic", o.opt_critic), ("actor", o.opt_actor)):
-        m, v = hip_adam(algo, which)
-        for l in range(len(m)):
-            got[f"u.m_{which}.{l}"], want[f"u.m_{which}.{l}"] = m[l], opt.m[l]
-            got[f"u.v_{which}.{l}"], want[f"u.v_{which}.{l}"] = v[l], opt.v[l]
-    q, y = algo.learner.debug_q_y(B)
-    got["u.q"], want["u.q"] = q.cpu(), o.last["q"].reshape(-1)
-    got["u.y"], want["u.y"] = y.cpu(), o.last["y"].reshape(-1)
-    as_np = lambda dct: {k: np.asarray(v.detach().cpu().double().numpy()) for k, v in dct.items()}   # noqa: E731
+    for name in ("critic", "critic_target", "actor", "actor_target"):
+        pair_nets(got, want, name, getattr(algo, name), getattr(o, name))
+    pair_adam(got, want, algo, "critic", o.opt_critic)
+    pair_adam(got, want, algo, "actor", o.opt_actor)
+    pair_q_y(got, want, algo, B, o.last["q"], o.last["y"])
     return as_np(got), as_np(want)
-
-
-def worst_ratio(got, want):
-    """max over keys of (deviation / the key's gate)"""
-    w = 0.0
-    for k, v in want.items():
-        lim = sc.PARAM_TOL if sc._is_param_key(k) else TOL
-        w = max(w, sc.rel_dev(got[k], v) / lim)
-    return w
 
 
 PARITY = [(256, 41), (256, 48), (100, 41), (100, 5)]
@@ -122,7 +101,7 @@ def test_d4pg_matches_the_oracle(B, N):
     assert_the_batches_reach_every_case(data, V_MIN, V_MAX)
     algo = make(B, N, fixture_nets=True)
     o = oracle_for(algo)
-    run_pair(algo, [o], data)
+    run_pair(algo, [o], data, step, to_double)
     assert algo.learner.update_count == 4
     got, want = got_and_want(algo, o, B)
     worst = sc.compare(got, want, TOL, param_tol=sc.PARAM_TOL)
@@ -141,65 +120,29 @@ def test_the_comparison_discriminates():
     algo = make(B, N, fixture_nets=True, tau=0.5)
     right = oracle_for(algo)
     wrong = {"no (1 - d)": oracle_for(algo, no_done=True), "no polyak": oracle_for(algo, skip_polyak=True)}
-    run_pair(algo, [right, *wrong.values()], batches(B, 4))
+    run_pair(algo, [right, *wrong.values()], batches(B, 4), step, to_double)
     got, want = got_and_want(algo, right, B)
     sc.compare(got, want, TOL, param_tol=sc.PARAM_TOL)
     for name, o in wrong.items():
-        r = worst_ratio(*got_and_want(algo, o, B))
+        r, _key = worst_ratio(*got_and_want(algo, o, B), TOL)
         assert r >= 10.0, f"{name}: the learner is only {r:.1f} gates away from the wrong oracle"
 
 
 # ---- step_n over replays ---------------------------------------------------------------------------------------------
 RB, RN, RV = 64, 41, 5.0            # batch, atoms and support [-5, 5] of the replay-driven tests
-E, LEP, NSTEP = 40, 30, 3
+NSTEP = 3
 
 
 def replay(nstep):
-    """E episodes of random length with 10 % done rows, every row random normal; n-step mode or plain."""
-    from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
-    from oprl_amd.buffers.nstep_buffer import NStepEpisodicReplayBuffer
-    kw = dict(buffer_size_transitions=E * LEP, state_dim=S, action_dim=A, max_episode_lenth=LEP, device="cuda", seed=7)
-    buf = (NStepEpisodicReplayBuffer(n_step=NSTEP, gamma=GAMMA, **kw) if nstep else EpisodicReplayBuffer(**kw)).create()
-    gen = t.Generator(device="cuda").manual_seed(1000)
-    for v in buf._tensors.values():
-        v.copy_(t.randn(v.shape, device="cuda", generator=gen))
-    buf._tensors["dones"].copy_(t.as_tensor((np.random.RandomState(6).rand(E, LEP, 1) < 0.1).astype(np.float32)))
-    lens = [int(x) for x in np.random.RandomState(4).randint(1, LEP + 1, size=E)]
-    buf.ep_lens = lens + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = sum(lens)
-    buf._lens_dirty = True
-    return buf
-
-
-def assert_same_state(a, b):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
-    x, y = a.state_dict(), b.state_dict()
-    assert x["counters"] == y["counters"], (x["counters"], y["counters"])
-    for k in ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"):
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), f"targets[{i}]"
+    return random_replay((S, A), NSTEP if nstep else None, GAMMA)
 
 
 @pytest.mark.parametrize("nstep", [False, True], ids=["plain", "nstep3"])
 def test_step_n_equals_sample_then_update_bitwise(nstep):
     """step_n(3) is bit for bit three sample() + update() pairs, over a plain replay and over an n-step replay (n = 3)."""
     buf = replay(nstep)
-    fused, loop = make(RB, RN, v_min=-RV, v_max=RV), make(RB, RN, v_min=-RV, v_max=RV)
-    loop.load_state_dict(fused.state_dict())
-    n_done = 0
-    for seed in (3, 5):
-        fused.learner.step_n(buf.handle, 3, RB, seed=seed)
-        buf.seed = seed
-        for _ in range(3):
-            buf._sample_counter = loop.update_step
-            batch = buf.sample(RB)
-            n_done += int((batch[3] != 0).sum().item())
-            loop.update(*batch)
-        assert_same_state(fused, loop)
+    pair = lambda: (make(RB, RN, v_min=-RV, v_max=RV), make(RB, RN, v_min=-RV, v_max=RV))       # noqa: E731
+    fused, _loop, n_done = check_step_n_equals_loop(pair, buf, RB)
     assert n_done > 0 and fused.update_step == 6
     assert not t.equal(fused.learner.actor_arena, make(RB, RN, v_min=-RV, v_max=RV).learner.actor_arena)   # (it trained)
 
@@ -244,40 +187,18 @@ def test_lanes_replay_trains():
     fused, loop = make(RB, RN, v_min=-RV, v_max=RV), make(RB, RN, v_min=-RV, v_max=RV)
     loop.load_state_dict(fused.state_dict())
     fused.learner.step_n(buf.handle, 2, RB, seed=9)
-    buf.seed = 9
-    for _ in range(2):
-        buf._sample_counter = loop.update_step
-        loop.update(*buf.sample(RB))
+    loop_updates(loop, buf, 2, 9, RB)
     assert_same_state(fused, loop)
 
 
 def test_resume():
     """A checkpoint taken after two updates, loaded into a fresh learner, gives bit-identical state after two more."""
     B, N = 100, 41
-    data = batches(B, 4)
-    a = make(B, N)
-    for x in data[:2]:
-        a.update(*(v.cuda() for v in x))
-    b = make(B, N)
-    b.load_state_dict(a.state_dict())
-    for x in data[2:]:
-        for algo in (a, b):
-            algo.update(*(v.cuda() for v in x))
+    a, _b, _sd = check_resume(lambda: make(B, N), step, batches(B, 4), 2)
     assert a.update_step == 4
-    assert_same_state(a, b)
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------
-INVALID, STATE = -1, -3
-
-
-def refused(rc, status):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert len(msg) > 0
-    return msg
-
-
 def test_refusals():
     """Every configuration and call DESIGN.md §15 lists as refused returns its status with a message; the update count
     and the Adam step counts stay where they were."""

@@ -12,6 +12,8 @@ import torch as t
 
 from oprl_amd import _capi
 from tests import her_oracle as ho
+from tests import support
+from tests.support import INVALID, STATE, assert_same_state, fill_random, live_lens, loop_updates, refused, set_table, storage
 
 pytestmark = pytest.mark.gpu
 KEYS = ("s", "a", "r", "d", "s2")
@@ -24,20 +26,7 @@ def make_buffer(E, L, S, A, seed=7, cls=None, **her):
     from oprl_amd.buffers.hindsight_buffer import HindsightEpisodicReplayBuffer
     buf = (cls or HindsightEpisodicReplayBuffer)(buffer_size_transitions=E * L, state_dim=S, action_dim=A,
                                                  max_episode_lenth=L, device="cuda", seed=seed, **her).create()
-    gen = t.Generator(device="cuda").manual_seed(1000 + E + L)
-    for k in ("actions", "rewards", "dones", "states"):     # every row random normal: the never-written ones too
-        v = buf._tensors[k]
-        v.copy_(t.randn(v.shape, device="cuda", generator=gen))
-    return buf
-
-
-def set_table(buf, lens):
-    """Write the episode table directly (the storage already holds data)."""
-    lens = [int(x) for x in lens]
-    buf.ep_lens = lens + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = sum(lens)
-    buf._lens_dirty = True
+    return fill_random(buf, ("actions", "rewards", "dones", "states"), gen_seed=1000 + E + L)
 
 
 def set_mode(buf, **kw):
@@ -45,14 +34,6 @@ def set_mode(buf, **kw):
         setattr(buf, k, v)
     buf._validate()
     buf._set_her()
-
-
-def storage(buf):
-    return [getattr(buf, k).cpu().numpy() for k in ("states", "actions", "rewards", "dones")]
-
-
-def live_lens(buf):
-    return buf.ep_lens[:buf.episodes_counter]
 
 
 def oracle(buf, B, counter, inds=None):
@@ -301,26 +282,12 @@ def test_lanes_replay_matches_the_oracle():
 
 
 # ---- refusals and round trips -----------------------------------------------------------------------------------------------
-def refused(rc, status):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert len(msg) > 20
-    return msg
-
-
+LONG = dict(min_len=21)             # these refusals explain themselves: more than 20 bytes of message
 LS, LA, LB = 12, 3, 32
 
 
 def make_algo(name, prec):
-    from oprl_amd.algos.ddpg import DDPG
-    from oprl_amd.algos.sac import SAC
-    from oprl_amd.algos.td3 import TD3
-    from oprl_amd.logging import NullLogger
-    cls = dict(ddpg=DDPG, td3=TD3, sac=SAC)[name]
-    kw = {} if name == "ddpg" else dict(log_every=10 ** 9)
-    t.manual_seed(0)
-    return cls(logger=NullLogger("/tmp/oprl_amd_test"), state_dim=LS, action_dim=LA, device="cuda", precision=prec,
-               **kw).create()
+    return support.make_algo(name, prec, LS, LA)
 
 
 @pytest.fixture(scope="module")
@@ -328,13 +295,7 @@ def learner_replays():
     """A hindsight replay at goal-reach-3d's dims and a plain replay over the same storage contents and table."""
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
     E, L = 20, 12
-    lens = np.random.RandomState(4).randint(1, L + 1, size=E)
-    bufs = [make_buffer(E, L, LS, LA, **TASK), make_buffer(E, L, LS, LA, cls=EpisodicReplayBuffer)]
-    for buf in bufs:
-        buf._tensors["dones"].copy_(t.as_tensor((np.random.RandomState(6).rand(E, L, 1) < 0.1).astype(np.float32)))
-        set_table(buf, lens)
-    assert all(t.equal(bufs[0]._tensors[k], bufs[1]._tensors[k]) for k in bufs[0]._tensors)
-    return bufs
+    return support.twin_replays(make_buffer(E, L, LS, LA, **TASK), make_buffer(E, L, LS, LA, cls=EpisodicReplayBuffer), E, L)
 
 
 def test_refusals(learner_replays):
@@ -342,7 +303,6 @@ def test_refusals(learner_replays):
     from oprl_amd.buffers.prioritized_buffer import PrioritizedEpisodicReplayBuffer
     from oprl_amd.group import LearnerGroup
     lib = _capi.load()
-    INVALID, STATE = -1, -3
     kw = dict(buffer_size_transitions=40, state_dim=12, action_dim=2, max_episode_lenth=10, device="cuda")
     plain = EpisodicReplayBuffer(**kw).create()
     h = plain._handle
@@ -355,36 +315,36 @@ def test_refusals(learner_replays):
                        ((6, 9, 3, 0.8, 0, 0, -1e-3), b"threshold"), ((6, 9, 3, 0.8, 0, 0, nan), b"threshold"),
                        ((6, 9, 3, 0.8, 0, 0, inf), b"threshold"), ((6, 9, 3, 0.8, 2, 0, 0.1), b"strategy"),
                        ((6, 9, 3, 0.8, -1, 0, 0.1), b"strategy"), ((6, 9, 3, 0.8, 0, 2, 0.1), b"reward")):
-        assert word in refused(lib.oprl_replay_set_her(h, *args), INVALID), args
+        refused(lib.oprl_replay_set_her(h, *args), INVALID, word, **LONG)
     # ... changing nothing: the mode is still off
     plain.add_transition(np.zeros(12), np.zeros(2), 0.0, False)
     out = [t.zeros((4, w), device="cuda") for w in (12, 2, 1, 1, 12)]
     ptrs = [_capi.ptr(x) for x in out]
-    assert b"goal layout" in refused(lib.oprl_replay_sample_her(plain.handle, 4, None, 0, 0, *ptrs, None, None, None,
-                                                                _capi.current_stream()), STATE)
+    refused(lib.oprl_replay_sample_her(plain.handle, 4, None, 0, 0, *ptrs, None, None, None, _capi.current_stream()), STATE,
+            b"goal layout", **LONG)
     # hindsight excludes n-step returns and the sum tree, either way round
     assert lib.oprl_replay_set_nstep(h, 3, 0.99) == 0
-    assert b"n-step" in refused(lib.oprl_replay_set_her(h, 6, 9, 3, 0.8, 0, 0, 0.1), STATE)
+    refused(lib.oprl_replay_set_her(h, 6, 9, 3, 0.8, 0, 0, 0.1), STATE, b"n-step", **LONG)
     assert lib.oprl_replay_set_nstep(h, 1, 0.99) == 0
     assert lib.oprl_replay_set_her(h, 6, 9, 3, 0.8, 0, 0, 0.1) == 0
     assert lib.oprl_replay_set_her(h, 0, 3, 3, 0.0, 1, 1, 0.0) == 0 and lib.oprl_replay_set_her(h, 11, 0, 1, 1.0, 0, 0, 1e30) == 0
-    assert b"hindsight" in refused(lib.oprl_replay_set_nstep(h, 3, 0.99), STATE)
+    refused(lib.oprl_replay_set_nstep(h, 3, 0.99), STATE, b"hindsight", **LONG)
     assert lib.oprl_replay_set_nstep(h, 1, 0.99) == 0                      # (n = 1 is the mode off: nothing to refuse)
-    assert b"hindsight" in refused(lib.oprl_replay_prio_enable(h, 0.6, 1e-6, None), STATE)
+    refused(lib.oprl_replay_prio_enable(h, 0.6, 1e-6, None), STATE, b"hindsight", **LONG)
     assert lib.oprl_replay_sample_her(plain.handle, 4, None, 0, 0, *ptrs, None, None, None, _capi.current_stream()) == 0
     assert lib.oprl_replay_set_her(h, 0, 0, 0, 0.0, 0, 0, 0.0) == 0        # G = 0 switches the mode off ...
     assert lib.oprl_replay_set_nstep(h, 3, 0.99) == 0 and lib.oprl_replay_set_nstep(h, 1, 0.99) == 0
     assert lib.oprl_replay_prio_enable(h, 0.6, 1e-6, None) == 0            # ... and both are allowed again
-    assert b"prioritized" in refused(lib.oprl_replay_set_her(h, 6, 9, 3, 0.8, 0, 0, 0.1), STATE)
+    refused(lib.oprl_replay_set_her(h, 6, 9, 3, 0.8, 0, 0, 0.1), STATE, b"prioritized", **LONG)
     prio = PrioritizedEpisodicReplayBuffer(**kw).create()
-    assert b"prioritized" in refused(lib.oprl_replay_set_her(prio._handle, 6, 9, 3, 0.8, 0, 0, 0.1), STATE)
+    refused(lib.oprl_replay_set_her(prio._handle, 6, 9, 3, 0.8, 0, 0, 0.1), STATE, b"prioritized", **LONG)
     t.cuda.synchronize()
     # the packed learners gather stored rows inside their launches
     hbuf, _ = learner_replays
     members = [make_algo("ddpg", "f32") for _ in range(2)]
     g = LearnerGroup(members)
     seeds = (C.c_uint64 * 2)(1, 2)
-    assert b"hindsight" in refused(lib.oprl_group_step_n(g.handle, hbuf.handle, 1, LB, seeds, _capi.current_stream()), STATE)
+    refused(lib.oprl_group_step_n(g.handle, hbuf.handle, 1, LB, seeds, _capi.current_stream()), STATE, b"hindsight", **LONG)
     assert members[0].update_step == 0 and members[1].update_step == 0
 
 
@@ -404,28 +364,6 @@ def test_checkpoint_round_trip(replay):
 
 
 # ---- learners ---------------------------------------------------------------------------------------------------------------
-def assert_same_state(a, b):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
-    x, y = a.state_dict(), b.state_dict()
-    for k in ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"):
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), f"targets[{i}]"
-    assert ("log_alpha" in x) == ("log_alpha" in y)
-    for p, q in zip(x.get("log_alpha", []), y.get("log_alpha", [])):
-        assert t.equal(p, q), "log_alpha"
-    assert x["counters"] == y["counters"]
-
-
-def loop_updates(algo, buf, K, seed):
-    buf.seed = seed
-    for _ in range(K):
-        buf._sample_counter = algo.update_step
-        algo.update(*buf.sample(LB))
-
-
 @pytest.mark.parametrize("name,prec", [("ddpg", "f32"), ("td3", "x2"), ("sac", "f32")])
 def test_step_n_over_a_hindsight_replay_equals_sample_then_update(learner_replays, name, prec):
     hbuf, pbuf = learner_replays
@@ -434,7 +372,7 @@ def test_step_n_over_a_hindsight_replay_equals_sample_then_update(learner_replay
     assert_same_state(fused, loop)
     print(name, prec, "launch form at B = 32:", fused.debug_form(LB))
     fused.learner.step_n(hbuf.handle, 3, LB, seed=11)
-    loop_updates(loop, hbuf, 3, 11)
+    loop_updates(loop, hbuf, 3, 11, LB)
     assert_same_state(fused, loop)
     assert fused.update_step == 3
     # the relabelled rows are not the stored rows (the comparison above is not vacuous)
@@ -444,12 +382,12 @@ def test_step_n_over_a_hindsight_replay_equals_sample_then_update(learner_replay
     assert not t.equal(a[0], b[0]) and not t.equal(a[2], b[2]) and t.equal(a[1], b[1])
     # update_from_buffer over the buffer class: one more update, alone and with the next observation's action riding
     fused.update_from_buffer(hbuf, LB)
-    loop_updates(loop, hbuf, 1, 11)
+    loop_updates(loop, hbuf, 1, 11, LB)
     assert_same_state(fused, loop)
     obs = np.linspace(-1, 1, LS).astype(np.float32)
     fused.update_from_buffer(hbuf, LB, act_next=obs)
     act = fused.actor.explore(obs)
-    loop_updates(loop, hbuf, 1, 11)
+    loop_updates(loop, hbuf, 1, 11, LB)
     assert_same_state(fused, loop)
     assert fused.update_step == 5 and np.all(np.isfinite(act)) and np.shape(act)[-1] == LA
     # no flag is left behind: step_n over a plain replay, against the twin whose learner never saw the hindsight handle

@@ -29,8 +29,11 @@ from oprl_amd.algos.td3_bc import TD3BC
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import scenarios as sc
-from tests.hip_adapters import cpu_params, hip_adam, load_params, split_like
+from tests import support
+from tests.hip_adapters import load_params, split_like
 from tests.iql_oracle import IQLOracle
+from tests.support import (INVALID, STATE, as_np, assert_same_state, check_resume, check_step_n_equals_loop, pair_adam, pair_nets,
+                           pair_q_y, random_replay, refused, worst_ratio)
 
 pytestmark = pytest.mark.gpu
 
@@ -81,33 +84,24 @@ def step(algo, x):
 def got_and_want(algo, o, B):
     """(everything but V, V's parameters and moments): the second pair falls under the parameter gate as a whole"""
     got, want, got_v, want_v = {}, {}, {}, {}
-    for name, mod, ref in (("critic", algo.critic, o.critic), ("critic_target", algo.critic_target, o.critic_target),
-                           ("actor", algo.actor, o.actor), ("actor_target", algo.actor_target, o.actor_target)):
-        for l, (x, y) in enumerate(zip(cpu_params(mod), ref)):
-            got[f"u.{name}.{l}"], want[f"u.{name}.{l}"] = x, y
-    for which, opt in (("critic", o.opt_critic), ("actor", o.opt_actor)):
-        m, v = hip_adam(algo, which)
-        for l in range(len(m)):
-            got[f"u.m_{which}.{l}"], want[f"u.m_{which}.{l}"] = m[l], opt.m[l]
-            got[f"u.v_{which}.{l}"], want[f"u.v_{which}.{l}"] = v[l], opt.v[l]
+    for name in ("critic", "critic_target", "actor", "actor_target"):
+        pair_nets(got, want, name, getattr(algo, name), getattr(o, name))
+    pair_adam(got, want, algo, "critic", o.opt_critic)
+    pair_adam(got, want, algo, "actor", o.opt_actor)
     L = algo.learner
-    for l, (x, y) in enumerate(zip(cpu_params(algo.value), o.value)):
-        got_v[f"u.value.{l}"], want_v[f"u.value.{l}"] = x, y
+    pair_nets(got_v, want_v, "value", algo.value, o.value)
     m, v = split_like(L.value_m, algo.value), split_like(L.value_v, algo.value)
     for l in range(len(m)):
         got_v[f"u.m_value.{l}"], want_v[f"u.m_value.{l}"] = m[l], o.opt_value.m[l]
         got_v[f"u.v_value.{l}"], want_v[f"u.v_value.{l}"] = v[l], o.opt_value.v[l]
-    q, y = L.debug_q_y(B)
-    got["u.q"], want["u.q"] = q.cpu(), o.last["q1"].reshape(-1)
-    got["u.y"], want["u.y"] = y.cpu(), o.last["y"].reshape(-1)
-    as_np = lambda dct: {k: np.asarray(v.detach().cpu().double().numpy()) for k, v in dct.items()}   # noqa: E731
+    pair_q_y(got, want, algo, B, o.last["q1"], o.last["y"])
     return as_np(got), as_np(want), as_np(got_v), as_np(want_v)
 
 
-def worst_ratio(got, want, got_v, want_v):
-    """max over the parameter, target and moment keys, V's included, of (deviation / the parameter gate)"""
-    return max([sc.rel_dev(got[k], v) / sc.PARAM_TOL for k, v in want.items() if sc._is_param_key(k)] +
-               [sc.rel_dev(got_v[k], v) / sc.PARAM_TOL for k, v in want_v.items()])
+def gates_away(got, want, got_v, want_v):
+    """max over the parameter, target and moment keys, V's included (every V key is one), of (deviation / the parameter
+    gate)"""
+    return max(worst_ratio(got, want, TOL, params_only=True)[0], worst_ratio(got_v, want_v, sc.PARAM_TOL)[0])
 
 
 @pytest.mark.parametrize("B", [256, 100], ids=["B256", "B100"])
@@ -152,24 +146,13 @@ def test_iql_matches_the_oracle(B):
     assert abs(q["v_mean"] - float(o.last["v_mean"])) <= TOL * float(o.last["v"].abs().max())
     assert abs(q["adv_mean"] - float(o.last["adv_mean"])) <= TOL * max(float(o.last["u"].abs().max()), float(o.last["v"].abs().max()))
     for name, w in wrong.items():
-        r = worst_ratio(*got_and_want(algo, w, B))
+        r = gates_away(*got_and_want(algo, w, B))
         print(f"B={B}: {name} is {r:.0f} gates away")
         assert r >= 10.0, f"{name}: the learner is only {r:.1f} gates away from the wrong oracle"
 
 
 # ---- bitwise links -----------------------------------------------------------------------------------------------------
-def assert_same_state(a, b, keys=("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"), targets=(0, 1), value=False):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
-    x, y = a.state_dict(), b.state_dict()
-    assert x["counters"] == y["counters"], (x["counters"], y["counters"])
-    for k in (*keys, *(V_KEYS if value else ())):
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    if value:
-        assert x["value_step"] == y["value_step"]
-    for i in targets:
-        assert t.equal(x["targets"][i], y["targets"][i]), f"targets[{i}]"
+WITH_V = dict(extra=V_KEYS + ("value_step",))            # V, its moments and its step count ride along
 
 
 def test_with_the_mode_off_it_is_plain_td3_again():
@@ -222,42 +205,15 @@ def test_a_td3_learner_of_the_same_process_is_untouched():
     assert_same_state(straight, around)
 
 
-RB, E, LEP, NSTEP = 64, 40, 30, 3
-
-
-def replay(nstep):
-    """E episodes of random length with 10 % done rows, every row random normal; n-step mode or plain."""
-    from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
-    from oprl_amd.buffers.nstep_buffer import NStepEpisodicReplayBuffer
-    S, A = fx.ENVS[ENV]
-    kw = dict(buffer_size_transitions=E * LEP, state_dim=S, action_dim=A, max_episode_lenth=LEP, device="cuda", seed=7)
-    buf = (NStepEpisodicReplayBuffer(n_step=NSTEP, gamma=GAMMA, **kw) if nstep else EpisodicReplayBuffer(**kw)).create()
-    gen = t.Generator(device="cuda").manual_seed(1000)
-    for v in buf._tensors.values():
-        v.copy_(t.randn(v.shape, device="cuda", generator=gen))
-    buf._tensors["dones"].copy_(t.as_tensor((np.random.RandomState(6).rand(E, LEP, 1) < 0.1).astype(np.float32)))
-    lens = [int(x) for x in np.random.RandomState(4).randint(1, LEP + 1, size=E)]
-    buf.ep_lens = lens + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = sum(lens)
-    buf._lens_dirty = True
-    return buf
+RB, NSTEP = 64, 3
 
 
 @pytest.mark.parametrize("nstep", [False, True], ids=["plain", "nstep3"])
 def test_step_n_equals_sample_then_update_bitwise(nstep):
     """step_n(3) is bit for bit three sample() + update() pairs, over a plain replay and over an n-step replay (n = 3),
     V, its moments and its step count included."""
-    buf = replay(nstep)
-    fused, loop = make(RB), make(RB)
-    loop.load_state_dict(fused.state_dict())
-    for seed in (3, 5):
-        fused.learner.step_n(buf.handle, 3, RB, seed=seed)
-        buf.seed = seed
-        for _ in range(3):
-            buf._sample_counter = loop.update_step
-            loop.update(*buf.sample(RB))
-        assert_same_state(fused, loop, value=True)
+    buf = random_replay(ENV, NSTEP if nstep else None, GAMMA)
+    fused, loop, _ = check_step_n_equals_loop(lambda: (make(RB), make(RB)), buf, RB, **WITH_V)
     assert fused.update_step == 6 and fused.learner.value_step == 6
     fresh = make(RB).state_dict()
     assert not t.equal(fused.learner.actor_arena.cpu(), fresh["actor"]) and not t.equal(fused.state_dict()["value"], fresh["value"])
@@ -304,7 +260,7 @@ def test_the_offline_trainer_equals_sample_and_update_pairs_bitwise():
     for _ in range(32):
         buf._sample_counter = loop.update_step
         loop.update(*buf.sample(B))
-    assert_same_state(algo, loop, value=True)
+    assert_same_state(algo, loop, **WITH_V)
     assert algo.state_dict()["counters"][:3] == [32, 32, 32] and algo.learner.value_step == 32
     assert algo.learner.read_iql() == loop.learner.read_iql()
     assert not t.equal(algo.state_dict()["actor"], learner().state_dict()["actor"])
@@ -314,37 +270,20 @@ def test_resume():
     """A checkpoint taken after two updates, loaded into a fresh learner, gives bit-identical state after two more — V,
     its moments and its step count included; a checkpoint without them is refused by name."""
     B = 100
-    data = batches(B, 4)
-    a = make(B)
-    for x in data[:2]:
-        step(a, x)
-    sd = a.state_dict()
-    assert sd["value_step"] == 2 and all(k in sd for k in V_KEYS)
-    b = make(B)
-    with pytest.raises(ValueError, match="value_m"):
-        b.load_state_dict({k: v for k, v in sd.items() if k != "value_m"})
-    b.load_state_dict(sd)
-    for x in data[2:]:
-        step(a, x)
-        step(b, x)
+
+    def partial_checkpoint_is_refused(b, sd):
+        assert sd["value_step"] == 2 and all(k in sd for k in V_KEYS)
+        with pytest.raises(ValueError, match="value_m"):
+            b.load_state_dict({k: v for k, v in sd.items() if k != "value_m"})
+
+    a, _b, sd = check_resume(lambda: make(B), step, batches(B, 4), 2, before_load=partial_checkpoint_is_refused, **WITH_V)
     assert a.update_step == 4
-    assert_same_state(a, b, value=True)
     assert not t.equal(a.state_dict()["value"], sd["value"])
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------
-INVALID, STATE = -1, -3
-
-
-def refused(rc, status, word):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert word in msg, (word, msg)
-
-
 def counters(algo):
-    t.cuda.synchronize()
-    return algo.learner.state_dict()["counters"] + [algo.learner.value_step]
+    return support.counters(algo, "value_step")
 
 
 class ValueNet:
@@ -427,7 +366,7 @@ def test_refusals():
     # ... and after all that the learner steps as one that was never asked
     step(iql, x[1])
     step(twin, x[1])
-    assert_same_state(iql, twin, value=True)
+    assert_same_state(iql, twin, **WITH_V)
     # a fused learner
     fused = make(B, cls=TD3, no_fuse=False)
     step(fused, x[0])

@@ -13,10 +13,10 @@ import torch as t
 from oprl_amd import _capi
 from tests import nstep_oracle as no
 from tests.lanes_oracle import LanesOracle, random_step
+from tests.support import INVALID, assert_same_state, loop_updates, refused
 
 pytestmark = pytest.mark.gpu
 NAMES = ("states", "actions", "rewards", "dones")
-INVALID = -1
 
 
 def make(E, L, S, A, cls=None, **kw):
@@ -172,18 +172,6 @@ def _ddpg(S, A):
     return DDPG(logger=NullLogger("/tmp/oprl_amd_test"), state_dim=S, action_dim=A, device="cuda", precision="f32").create()
 
 
-def assert_same_state(a, b):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
-    x, y = a.state_dict(), b.state_dict()
-    for k in ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"):
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), f"targets[{i}]"
-    assert x["counters"] == y["counters"]
-
-
 def test_step_n_over_a_lanes_replay_equals_sample_then_update():
     S, A, B = 24, 6, 32
     buf, ora, _ = wrapped(12, 10, S, A, 4, 200, stride=3)
@@ -192,10 +180,7 @@ def test_step_n_over_a_lanes_replay_equals_sample_then_update():
     assert_same_state(fused, loop)
     print("launch form at B = 32:", fused.debug_form(B))
     fused.learner.step_n(buf.handle, 3, B, seed=11)
-    buf.seed = 11
-    for _ in range(3):
-        buf._sample_counter = loop.update_step
-        loop.update(*buf.sample(B))
+    loop_updates(loop, buf, 3, 11, B)
     assert_same_state(fused, loop)
     assert fused.update_step == 3
     assert_equal(buf, ora)
@@ -219,7 +204,6 @@ def write_rows(buf, ep, k, s, a, r, d, s2, lens, counter, n=None):
 def test_c_level_refusals_change_nothing():
     E, L, S, A, N = 6, 5, 3, 2, 4
     buf, ora, _ = wrapped(E, L, S, A, N, 43)
-    lib = buf._lib
     n = len(buf)
     t.cuda.synchronize()
     tensors = {k: v.clone() for k, v in buf._tensors.items()}
@@ -245,9 +229,7 @@ def test_c_level_refusals_change_nothing():
     for what, kw in cases.items():
         args = dict(s=s, a=a, r=r, d=d, s2=s2, lens=lens, counter=counter)
         args.update(kw)
-        rc = write_rows(buf, **args)
-        msg = lib.oprl_last_error()
-        assert rc == INVALID and len(msg) > 0, (what, rc, msg)
+        refused(write_rows(buf, **args), INVALID)
         t.cuda.synchronize()
         for k, v in buf._tensors.items():
             assert t.equal(v, tensors[k]), (what, k)

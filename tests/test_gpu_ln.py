@@ -18,14 +18,16 @@ from oprl_amd.algos.td3 import TD3
 from oprl_amd.logging import NullLogger
 from tests import ln_oracle as lno
 from tests import scenarios as sc
+from tests import support
 from tests.hip_adapters import cpu_params, hip_adam, load_params
+from tests.support import INVALID, STATE, check_step_n_equals_loop, fill_full_episodes, run_pair, to_double, worst_ratio
 
 pytestmark = pytest.mark.gpu
 
 S, A, N, G = lno.S, lno.A, lno.N, lno.G
 TOL = 2e-5                          # network outputs (tests/test_gpu_algos.py)
 SEED, RANK = 7, 0
-INVALID, STATE = -1, -3
+LN_KEYS = ("critic_ln", "critic_ln_target", "critic_ln_m", "critic_ln_v")
 
 
 def subset(n, m):
@@ -66,14 +68,8 @@ def make(name, B, n_min=2, scenario=True, **kw):
     return algo
 
 
-def run_pair(algo, oracles, data):
-    for s, a, r, d, s2, e1, e2 in data:
-        algo.update(*(x.cuda() for x in (s, a, r, d, s2)), noise=(e1.cuda(), e2.cuda()))
-        f = [x.double() for x in (s, a, r, d, s2, e1, e2)]
-        for o in oracles:
-            o.update(*f)
-    t.cuda.synchronize()
-    algo.learner.check()
+def step(algo, x):
+    algo.update(*(v.cuda() for v in x[:5]), noise=(x[5].cuda(), x[6].cuda()))
 
 
 def state_of(algo, B):
@@ -102,15 +98,6 @@ def state_of(algo, B):
     return {k: np.asarray(v.detach().cpu().double().numpy()) for k, v in got.items()}
 
 
-def worst_ratio(got, want):
-    """max over keys of (deviation / the key's gate), and the key"""
-    worst = (0.0, "")
-    for k, v in want.items():
-        lim = sc.PARAM_TOL if sc._is_param_key(k) else TOL
-        worst = max(worst, (sc.rel_dev(got[k], v) / lim, k))
-    return worst
-
-
 @pytest.mark.parametrize("name,B,n_min,seed", lno.SCENARIOS, ids=[f"{a}-B{b}-M{m}" for a, b, m, _ in lno.SCENARIOS])
 def test_layer_norm_learners_match_the_oracle(name, B, n_min, seed):
     """Four updates (REDQ: G = 3, critic-only updates before and after an actor step; M = 3 takes the minimum through
@@ -118,11 +105,11 @@ def test_layer_norm_learners_match_the_oracle(name, B, n_min, seed):
     moments, log alpha and its moments, the last q / y rows, and gamma / beta, their targets and their moments."""
     algo = make(name, B, n_min)
     o = lno.scenario_oracle(name, subset(N, n_min), n_min)
-    run_pair(algo, [o], lno.scenario_batches(seed, B, 4))
+    run_pair(algo, [o], lno.scenario_batches(seed, B, 4), step, to_double)
     assert algo.learner.update_count == 4
     got, want = state_of(algo, B), lno.digest(o)
     assert "u.critic.0.ln" in want and "u.m_critic.ln" in want and "u.log_alpha_m" in want
-    print("worst: %.3f gates at %s" % worst_ratio(got, want))
+    print("worst: %.3f gates at %s" % worst_ratio(got, want, TOL))
     sc.compare(got, want, TOL, param_tol=sc.PARAM_TOL)
 
 
@@ -133,11 +120,11 @@ def test_the_comparison_discriminates():
     algo = make("redq", B, 2, target_update_coef=0.5)
     right = lno.scenario_oracle("redq", subset(N, 2), 2, tau=0.5)
     wrong = {k: lno.scenario_oracle("redq", subset(N, 2), 2, tau=0.5, **{k: True}) for k in ("no_ln", "freeze_ln", "no_ln_polyak")}
-    run_pair(algo, [right, *wrong.values()], lno.scenario_batches(100, B, 4))
+    run_pair(algo, [right, *wrong.values()], lno.scenario_batches(100, B, 4), step, to_double)
     got = state_of(algo, B)
     sc.compare(got, lno.digest(right), TOL, param_tol=sc.PARAM_TOL)
     for k, o in wrong.items():
-        r, key = worst_ratio(got, lno.digest(o))
+        r, key = worst_ratio(got, lno.digest(o), TOL)
         print(f"{k}: {r:.1f} gates at {key}")
         assert r >= 10.0, f"{k}: the learner is only {r:.1f} gates away from the wrong oracle"
 
@@ -175,52 +162,24 @@ def _replay(dev, seed=0, E=40, Lep=100):
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
     buf = EpisodicReplayBuffer(buffer_size_transitions=E * Lep, state_dim=S, action_dim=A, device=str(dev),
                                seed=seed, max_episode_lenth=Lep).create()
-    g = t.Generator(device=dev).manual_seed(4321)
-    buf._tensors["states"].copy_(t.randn((E, Lep + 1, S), device=dev, generator=g))
-    buf._tensors["actions"].copy_(t.rand((E, Lep, A), device=dev, generator=g) * 2 - 1)
-    buf._tensors["rewards"].copy_(t.rand((E, Lep, 1), device=dev, generator=g))
-    buf._tensors["dones"].copy_((t.rand((E, Lep, 1), device=dev, generator=g) < 0.02).float())
-    buf.ep_lens = [Lep] * E
-    buf.episodes_counter = E
-    buf._number_transitions = E * Lep
-    buf._lens_dirty = True
+    fill_full_episodes(buf, E, Lep)
     return buf
 
 
-def _assert_same_state(a, b, ln=True):
-    x, y = a.state_dict(), b.state_dict()
-    assert x["counters"] == y["counters"], (x["counters"], y["counters"])
-    keys = ["actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"]
+def assert_same_state(a, b, ln=True):     # kept: gamma / beta ride along, present exactly when asked for, and stepped
+    x = a.state_dict()
+    assert ln == ("critic_ln" in x) and "log_alpha" in x
     if ln:
-        keys += ["critic_ln", "critic_ln_target", "critic_ln_m", "critic_ln_v"]
         assert float(x["critic_ln_v"].abs().max()) > 0.0
-    assert all(k in x for k in keys) and ln == ("critic_ln" in x)
-    for k in keys:
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), f"targets[{i}]"
-    for i, (p, q) in enumerate(zip(x["log_alpha"], y["log_alpha"])):
-        assert t.equal(p, q), f"log_alpha[{i}]"
+    support.assert_same_state(a, b, extra=LN_KEYS if ln else ())
 
 
 def test_step_n_equals_sample_then_update_bitwise():
     """step_n(K = G) over a replay with 2 % done rows is bit for bit G times sample() + update() with the sampler's rows."""
     B, dev = 256, t.device("cuda", 0)
     buf = _replay(dev)
-    fused, loop = make("redq", B), make("redq", B)
-    loop.load_state_dict(fused.state_dict())
-    n_done = 0
-    for seed in (3, 5):
-        fused.learner.step_n(buf.handle, G, B, seed=seed)
-        buf.seed = seed
-        for _ in range(G):
-            buf._sample_counter = loop.update_step
-            batch = buf.sample(B)
-            n_done += int(batch[3].sum().item())
-            loop.update(*batch)
-        t.cuda.synchronize()
-        fused.learner.check()
-        _assert_same_state(fused, loop)
+    fused, loop, n_done = check_step_n_equals_loop(lambda: (make("redq", B), make("redq", B)), buf, B, K=G, extra=LN_KEYS)
+    assert_same_state(fused, loop)
     assert n_done > 0
 
 
@@ -231,15 +190,14 @@ def test_resume_in_the_middle_of_a_group():
     data = lno.scenario_batches(100, B, 5)
     a = make("redq", B)
     for x in data[:1]:
-        a.update(*(v.cuda() for v in x[:5]), noise=(x[5].cuda(), x[6].cuda()))
+        step(a, x)
     b = make("redq", B, scenario=False)
     b.load_state_dict(a.state_dict())
     for x in data[1:]:
         for algo in (a, b):
-            algo.update(*(v.cuda() for v in x[:5]), noise=(x[5].cuda(), x[6].cuda()))
-    t.cuda.synchronize()
+            step(algo, x)
     assert a.update_step == 5
-    _assert_same_state(a, b)
+    assert_same_state(a, b)
     plain = make("redq", B, layer_norm=False)
     with pytest.raises(ValueError, match="critic_ln"):
         plain.load_state_dict(a.state_dict())
@@ -261,9 +219,8 @@ def test_the_field_off_changes_nothing(name):
     assert not hasattr(a, "critic_ln") and a.learner._ln is None
     for x in lno.scenario_batches(100, B, 2):
         for algo in (a, b):
-            algo.update(*(v.cuda() for v in x[:5]), noise=(x[5].cuda(), x[6].cuda()))
-    t.cuda.synchronize()
-    _assert_same_state(a, b, ln=False)
+            step(algo, x)
+    assert_same_state(a, b, ln=False)
 
 
 @pytest.mark.parametrize("name", ["sac", "redq"])
@@ -357,9 +314,7 @@ def _refused(algo, code, word, **kw):
     from oprl_amd.algos.nn_models import CriticLayerNorm
     lib = _capi.load()
     holder = CriticLayerNorm(len(nets_of(algo)[0]) if not isinstance(algo, TD3) else 2).cuda().make_state()
-    rc = lib.oprl_learner_set_layernorm(algo.learner.handle, C.byref(_ln_desc(holder, **kw)))
-    msg = lib.oprl_last_error()
-    assert rc == code and word in msg, (rc, msg)
+    support.refused(lib.oprl_learner_set_layernorm(algo.learner.handle, C.byref(_ln_desc(holder, **kw))), code, word)
 
 
 def test_set_layernorm_refuses_with_its_codes_and_leaves_the_learner_usable():
@@ -414,5 +369,5 @@ def test_set_layernorm_refuses_with_its_codes_and_leaves_the_learner_usable():
     assert lib.oprl_learner_dp_update(h, *(_capi.ptr(x) for x in batch[:5]), B, None, None, _capi.current_stream()) == STATE
     # ... and the refused calls changed nothing: the learner with the mode on still meets the oracle
     o = lno.scenario_oracle("sac", None)
-    run_pair(on, [o], lno.scenario_batches(600, B, 2))
+    run_pair(on, [o], lno.scenario_batches(600, B, 2), step, to_double)
     sc.compare(state_of(on, B), lno.digest(o), TOL, param_tol=sc.PARAM_TOL)

@@ -12,6 +12,9 @@ import torch as t
 from oprl_amd import _capi
 from tests import nstep_oracle as no
 from tests import scenarios as sc
+from tests import support
+from tests.support import (INVALID, STATE, assert_same_state, fill_random, live_lens, loop_updates, refused, set_table,  # noqa: F401
+                           storage)
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-5          # the output gate of tests/test_gpu_algos.py
@@ -23,32 +26,12 @@ def make_buffer(E, L, S, A, n_step=3, gamma=0.99, seed=7, cls=None):
     kw = dict(n_step=n_step) if cls is None else {}
     buf = (cls or NStepEpisodicReplayBuffer)(buffer_size_transitions=E * L, state_dim=S, action_dim=A,
                                              max_episode_lenth=L, gamma=gamma, device="cuda", seed=seed, **kw).create()
-    gen = t.Generator(device="cuda").manual_seed(1000 + E + L)
-    for k, v in buf._tensors.items():           # every row random normal: the never-written ones too
-        v.copy_(t.randn(v.shape, device="cuda", generator=gen))
-    return buf
-
-
-def set_table(buf, lens):
-    """Write the episode table directly (the storage already holds data)."""
-    lens = [int(x) for x in lens]
-    buf.ep_lens = lens + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = sum(lens)
-    buf._lens_dirty = True
+    return fill_random(buf, gen_seed=1000 + E + L)
 
 
 def set_mode(buf, n, gamma):
     buf.n_step, buf.gamma = n, gamma
     buf._set_nstep()
-
-
-def storage(buf):
-    return [getattr(buf, k).cpu().numpy() for k in ("states", "actions", "rewards", "dones")]
-
-
-def live_lens(buf):
-    return buf.ep_lens[:buf.episodes_counter]
 
 
 def uniform_sample(buf, B, inds=None):
@@ -196,51 +179,12 @@ def learner_replays():
     """An n-step replay (n = 3) at walker dims and a plain replay over the same storage contents and table."""
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
     E, L = 40, 30
-    rs = np.random.RandomState(4)
-    lens = rs.randint(1, L + 1, size=E)
-    bufs = []
-    for cls in (None, EpisodicReplayBuffer):
-        buf = make_buffer(E, L, LS, LA, n_step=LN, gamma=LGAMMA, cls=cls)
-        buf._tensors["dones"].copy_(t.as_tensor((np.random.RandomState(6).rand(E, L, 1) < 0.1).astype(np.float32)))
-        set_table(buf, lens)
-        bufs.append(buf)
-    assert all(t.equal(bufs[0]._tensors[k], bufs[1]._tensors[k]) for k in bufs[0]._tensors)
-    return bufs
+    return support.twin_replays(make_buffer(E, L, LS, LA, n_step=LN, gamma=LGAMMA),
+                                make_buffer(E, L, LS, LA, n_step=LN, gamma=LGAMMA, cls=EpisodicReplayBuffer), E, L)
 
 
 def make_algo(name, prec):
-    from oprl_amd.algos.ddpg import DDPG
-    from oprl_amd.algos.sac import SAC
-    from oprl_amd.algos.td3 import TD3
-    from oprl_amd.algos.tqc import TQC
-    from oprl_amd.logging import NullLogger
-    cls = dict(ddpg=DDPG, td3=TD3, sac=SAC, tqc=TQC)[name]
-    kw = {} if name == "ddpg" else dict(log_every=10 ** 9)
-    t.manual_seed(0)
-    return cls(logger=NullLogger("/tmp/oprl_amd_test"), state_dim=LS, action_dim=LA, device="cuda", precision=prec,
-               **kw).create()
-
-
-def assert_same_state(a, b):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
-    x, y = a.state_dict(), b.state_dict()
-    for k in ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"):
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), f"targets[{i}]"
-    assert ("log_alpha" in x) == ("log_alpha" in y)
-    for p, q in zip(x.get("log_alpha", []), y.get("log_alpha", [])):
-        assert t.equal(p, q), "log_alpha"
-    assert x["counters"] == y["counters"]
-
-
-def loop_updates(algo, buf, K, seed):
-    buf.seed = seed
-    for _ in range(K):
-        buf._sample_counter = algo.update_step
-        algo.update(*buf.sample(LB))
+    return support.make_algo(name, prec, LS, LA)
 
 
 @pytest.mark.parametrize("name,prec", [("ddpg", "f32"), ("td3", "f32"), ("sac", "f32"), ("tqc", "f32"), ("ddpg", "x2"),
@@ -251,7 +195,7 @@ def test_step_n_over_an_nstep_replay_equals_sample_then_update(learner_replays, 
     assert_same_state(fused, loop)
     print(name, prec, "launch form at B = 64:", fused.debug_form(LB))
     fused.learner.step_n(nbuf.handle, 3, LB, seed=11)
-    loop_updates(loop, nbuf, 3, 11)
+    loop_updates(loop, nbuf, 3, 11, LB)
     assert_same_state(fused, loop)
     assert fused.update_step == 3
     # the n-step rows are not the one-step rows (the comparison above is not vacuous)
@@ -308,19 +252,11 @@ def test_ddpg_td_target_is_the_nstep_target(learner_replays):
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------
-def refused(rc, status):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert len(msg) > 0
-    return msg
-
-
 def test_refusals(learner_replays):
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
     from oprl_amd.buffers.prioritized_buffer import PrioritizedEpisodicReplayBuffer
     from oprl_amd.group import LearnerGroup
     lib = _capi.load()
-    INVALID, STATE = -1, -3
     nbuf, _ = learner_replays
     plain = EpisodicReplayBuffer(buffer_size_transitions=40, state_dim=3, action_dim=2, max_episode_lenth=10,
                                  device="cuda").create()

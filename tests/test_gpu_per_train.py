@@ -15,8 +15,10 @@ from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import per_oracle as po
 from tests import scenarios as sc
-from tests.hip_adapters import cpu_params, hip_adam
+from tests.hip_adapters import cpu_params
 from tests.per_train_oracle import WeightedOracle, WeightedREDQOracle
+from tests.support import (as_np, assert_same_state, fill_full_episodes, pair_adam, pair_nets, pair_q_y, run_pair, to_double,
+                           worst_ratio)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,17 +78,6 @@ def update(name, algo, x, weighted=True):
     algo.update(s, a, r, d, s2, **kw)
 
 
-def assert_same_state(a, b, what=""):
-    x, y = a.state_dict(), b.state_dict()
-    assert x["counters"] == y["counters"], (what, x["counters"], y["counters"])
-    for k in ("critic", "critic_m", "critic_v", "actor", "actor_m", "actor_v"):
-        assert t.equal(x[k], y[k]), (what, k, (x[k] - y[k]).abs().max().item())
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), (what, f"targets[{i}]")
-    for i, (p, q) in enumerate(zip(x.get("log_alpha", []), y.get("log_alpha", []))):
-        assert t.equal(p, q), (what, f"log_alpha[{i}]")
-
-
 # ---------------------------------------------------------------- 1. w = 1 is today's update
 @pytest.mark.parametrize("name,B", CASES, ids=IDS)
 def test_unit_weights_are_todays_update_bitwise(name, B):
@@ -105,7 +96,7 @@ def test_unit_weights_are_todays_update_bitwise(name, B):
         assert wl.last_td_abs.shape == (B,) and bool(t.isfinite(wl.last_td_abs).all())
         if name == "ddpg":
             assert t.equal(wl.last_td_abs, (q1 - y1).abs())
-        assert_same_state(wl, pl, f"update {k}")
+        assert_same_state(wl, pl, what=f"update {k}")
     wl.learner.check()
     assert wl.update_step == 4
 
@@ -123,43 +114,23 @@ def oracle_for(name, algo, **knobs):
     return WeightedOracle(name, S, A, cpu_params(algo.actor), [cpu_params(n) for n in critic_nets(name, algo)], **kw, **knobs)
 
 
-def run_pair(name, algo, oracles, data):
-    for x in data:
-        update(name, algo, x)
-        f = [v.double() for v in x]
-        for o in oracles:
-            o.update(*f)
-    t.cuda.synchronize()
-    algo.learner.check()
-
-
 def got_and_want(name, algo, o, B):
     L = algo.learner
     got, want = {}, {}
     nets, tnets = critic_nets(name, algo), critic_nets(name, algo, target=True)
     for i in range(len(nets)):
-        for l, (x, y) in enumerate(zip(cpu_params(nets[i]), o.critics[i])):
-            got[f"u.critic.{i}.{l}"], want[f"u.critic.{i}.{l}"] = x, y
-        for l, (x, y) in enumerate(zip(cpu_params(tnets[i]), o.targets[i])):
-            got[f"u.critic_target.{i}.{l}"], want[f"u.critic_target.{i}.{l}"] = x, y
-    for l, (x, y) in enumerate(zip(cpu_params(algo.actor), o.actor)):
-        got[f"u.actor.{l}"], want[f"u.actor.{l}"] = x, y
+        pair_nets(got, want, f"critic.{i}", nets[i], o.critics[i])
+        pair_nets(got, want, f"critic_target.{i}", tnets[i], o.targets[i])
+    pair_nets(got, want, "actor", algo.actor, o.actor)
     if name in ("ddpg", "td3"):
-        for l, (x, y) in enumerate(zip(cpu_params(algo.actor_target), o.actor_target)):
-            got[f"u.actor_target.{l}"], want[f"u.actor_target.{l}"] = x, y
-    for which, opt in (("critic", o.opt_critic), ("actor", o.opt_actor)):
-        m, v = hip_adam(algo, which)
-        for l in range(len(m)):
-            got[f"u.m_{which}.{l}"], want[f"u.m_{which}.{l}"] = m[l], opt.m[l]
-            got[f"u.v_{which}.{l}"], want[f"u.v_{which}.{l}"] = v[l], opt.v[l]
+        pair_nets(got, want, "actor_target", algo.actor_target, o.actor_target)
+    pair_adam(got, want, algo, "critic", o.opt_critic)
+    pair_adam(got, want, algo, "actor", o.opt_actor)
     if L.log_alpha is not None:
         got["u.log_alpha"], want["u.log_alpha"] = L.log_alpha.cpu().reshape(1), o.log_alpha.reshape(1)
         got["u.log_alpha_m"], want["u.log_alpha_m"] = L.log_alpha_m.cpu().reshape(1), o.opt_alpha.m[0]
         got["u.log_alpha_v"], want["u.log_alpha_v"] = L.log_alpha_v.cpu().reshape(1), o.opt_alpha.v[0]
-    q, y = L.debug_q_y(B)
-    got["u.q"], want["u.q"] = q.cpu(), o.last["q"].reshape(-1)
-    got["u.y"], want["u.y"] = y.cpu(), o.last["y"].reshape(-1)
-    as_np = lambda dct: {k: np.asarray(v.detach().cpu().double().numpy()) for k, v in dct.items()}   # noqa: E731
+    pair_q_y(got, want, algo, B, o.last["q"], o.last["y"])
     return as_np(got), as_np(want)
 
 
@@ -170,20 +141,13 @@ def td_ratio(algo, o):
     return dev / (TOL * scale), dev, scale
 
 
-def worst_ratio(got, want):
-    w = 0.0
-    for k, v in want.items():
-        w = max(w, sc.rel_dev(got[k], v) / (sc.PARAM_TOL if sc._is_param_key(k) else TOL))
-    return w
-
-
 @pytest.mark.parametrize("name,B", CASES, ids=IDS)
 def test_weighted_updates_match_float64(name, B):
     """Four weighted updates: every net, target, both optimizers' moments, the temperature, and the last update's q / y
     rows within the suite's gates, and its |TD| within 2e-5 of max(max|q|, max|y|)."""
     algo = make(name, B, prioritized=True)
     o = oracle_for(name, algo)
-    run_pair(name, algo, [o], batches(B, 4))
+    run_pair(algo, [o], batches(B, 4), lambda a, x: update(name, a, x), to_double)
     assert algo.update_step == 4
     got, want = got_and_want(name, algo, o, B)
     worst = sc.compare(got, want, TOL, param_tol=sc.PARAM_TOL)
@@ -202,11 +166,11 @@ def test_the_comparison_discriminates(name):
     wrong = {"ignores the weights": oracle_for(name, algo, ignore_weights=True),
              "weights the actor loss": oracle_for(name, algo, weight_actor=True),
              "normalises by sum(w)": oracle_for(name, algo, normalise_by_sum=True)}
-    run_pair(name, algo, [right, *wrong.values()], batches(B, 4))
+    run_pair(algo, [right, *wrong.values()], batches(B, 4), lambda a, x: update(name, a, x), to_double)
     got, want = got_and_want(name, algo, right, B)
     sc.compare(got, want, TOL, param_tol=sc.PARAM_TOL)
     for what, o in wrong.items():
-        r = worst_ratio(*got_and_want(name, algo, o, B))
+        r, _key = worst_ratio(*got_and_want(name, algo, o, B), TOL)
         print(f"{name}: oracle that {what}: {r:.1f} gates away")
         assert r >= 10.0, f"{what}: the learner is only {r:.1f} gates away from the wrong oracle"
 
@@ -219,15 +183,7 @@ def prio_replay(seed=3, E=40, Lep=100, fill=True):
                                           seed=seed, max_episode_lenth=Lep).create()
     if not fill:
         return buf
-    g = t.Generator(device=dev).manual_seed(4321)
-    buf._tensors["states"].copy_(t.randn((E, Lep + 1, S), device=dev, generator=g))
-    buf._tensors["actions"].copy_(t.rand((E, Lep, A), device=dev, generator=g) * 2 - 1)
-    buf._tensors["rewards"].copy_(t.rand((E, Lep, 1), device=dev, generator=g))
-    buf._tensors["dones"].copy_((t.rand((E, Lep, 1), device=dev, generator=g) < 0.02).float())
-    buf.ep_lens = [Lep] * E
-    buf.episodes_counter = E
-    buf._number_transitions = E * Lep
-    buf._lens_dirty = True
+    g = fill_full_episodes(buf, E, Lep)
     td0 = t.rand(E * Lep, device=dev, generator=g) * 2       # random initial priorities on every slot
     buf.update_priorities(t.arange(E * Lep, dtype=t.int32, device=dev), td0)
     return buf

@@ -14,13 +14,15 @@ import torch as t
 
 from oprl_amd import _capi
 from tests import prior_oracle as po
+from tests import support
 from tests.config_scripts import load_config
+from tests.support import INVALID, STATE, fill_random, live_lens, loop_updates, refused, set_table, storage
 
 pytestmark = pytest.mark.gpu
 KEYS = ("s", "a", "r", "d", "s2")
 INTS = ("ep", "step", "src")
 SENT_F, SENT_I = 12345.0, -777
-INVALID, STATE = -1, -3
+LONG = dict(min_len=21)             # these refusals explain themselves: more than 20 bytes of message
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -44,29 +46,7 @@ def make_buffer(E, L, S, A, seed=7, prior=None, share=0.5, fill=True):
     from oprl_amd.buffers.prior_buffer import PriorDataReplayBuffer
     kw = dict(buffer_size_transitions=E * L, state_dim=S, action_dim=A, max_episode_lenth=L, device="cuda", seed=seed)
     buf = (PriorDataReplayBuffer(prior=prior, prior_share=share, **kw) if prior is not None else EpisodicReplayBuffer(**kw)).create()
-    if fill:
-        gen = t.Generator(device="cuda").manual_seed(1000 + E + L)
-        for k in ("actions", "rewards", "dones", "states"):
-            v = buf._tensors[k]
-            v.copy_(t.randn(v.shape, device="cuda", generator=gen))
-    return buf
-
-
-def set_table(buf, lens):
-    """Write the episode table directly (the storage already holds data)."""
-    lens = [int(x) for x in lens]
-    buf.ep_lens = lens + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = sum(lens)
-    buf._lens_dirty = True
-
-
-def storage(buf):
-    return [getattr(buf, k).cpu().numpy() for k in ("states", "actions", "rewards", "dones")]
-
-
-def live_lens(buf):
-    return buf.ep_lens[:buf.episodes_counter]
+    return fill_random(buf, ("actions", "rewards", "dones", "states"), gen_seed=1000 + E + L) if fill else buf
 
 
 def oracle(buf, B, counter, inds=None):
@@ -262,34 +242,15 @@ def test_rows_staged_in_the_prior_are_seen_by_the_next_mixed_sample():
 
 
 # ---- refusals and round trips -----------------------------------------------------------------------------------------------
-def refused(rc, status):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert len(msg) > 20
-    return msg
-
-
 LS, LA, LB = 12, 3, 32
 
 
 def make_algo(name, prec):
-    from oprl_amd.algos.ddpg import DDPG
-    from oprl_amd.algos.iql import IQL
-    from oprl_amd.algos.sac import SAC
-    from oprl_amd.algos.td3 import TD3
-    from oprl_amd.algos.tqc import TQC
-    from oprl_amd.logging import NullLogger
-    cls = dict(ddpg=DDPG, td3=TD3, sac=SAC, tqc=TQC, iql=IQL)[name]
-    kw = {} if name == "ddpg" else dict(log_every=10 ** 9)
-    if name in ("tqc", "iql"):
-        kw["max_batch"] = 256
-    t.manual_seed(0)
-    return cls(logger=NullLogger("/tmp/oprl_amd_test"), state_dim=LS, action_dim=LA, device="cuda", precision=prec,
-               **kw).create()
+    return support.make_algo(name, prec, LS, LA, **(dict(max_batch=256) if name in ("tqc", "iql") else {}))
 
 
 @pytest.fixture(scope="module")
-def learner_replays():
+def learner_replays():          # not twin_replays: two shapes, and one stream of draws runs through both tables
     """A prior of 20 x 12 steps and an online replay of 10 x 7 over it, at the learners' dims."""
     rs = np.random.RandomState(4)
     prior = make_buffer(20, 12, LS, LA)
@@ -309,40 +270,41 @@ def test_set_prior_refusals():
     h, p = buf._handle, prior._handle
     nan, inf = float("nan"), float("inf")
     for share in (-0.1, 1.1, nan, inf, -inf):
-        assert b"share" in refused(lib.oprl_replay_set_prior(h, p, share), INVALID), share
-    assert b"itself" in refused(lib.oprl_replay_set_prior(h, h, 0.5), INVALID)
+        refused(lib.oprl_replay_set_prior(h, p, share), INVALID, b"share", **LONG)
+    refused(lib.oprl_replay_set_prior(h, h, 0.5), INVALID, b"itself", **LONG)
     for S, A in ((13, 2), (12, 3)):
         other = make_buffer(4, 5, S, A, fill=False)
-        assert b"dims" in refused(lib.oprl_replay_set_prior(h, other._handle, 0.5), INVALID)
-        assert b"dims" in refused(lib.oprl_replay_set_prior(other._handle, p, 0.5), INVALID)
+        refused(lib.oprl_replay_set_prior(h, other._handle, 0.5), INVALID, b"dims", **LONG)
+        refused(lib.oprl_replay_set_prior(other._handle, p, 0.5), INVALID, b"dims", **LONG)
     # n-step, hindsight and prioritized handles, on either side
     x, y = make_buffer(4, 5, 12, 2, fill=False), make_buffer(4, 5, 12, 2, fill=False)
     for word, on, off in ((b"n-step", lambda r: lib.oprl_replay_set_nstep(r, 3, 0.99), lambda r: lib.oprl_replay_set_nstep(r, 1, 0.99)),
                           (b"hindsight", lambda r: lib.oprl_replay_set_her(r, 6, 9, 3, 0.8, 0, 0, 0.1),
                            lambda r: lib.oprl_replay_set_her(r, 0, 0, 0, 0.0, 0, 0, 0.0))):
         assert on(x._handle) == 0
-        assert word in refused(lib.oprl_replay_set_prior(x._handle, y._handle, 0.5), STATE)
-        msg = refused(lib.oprl_replay_set_prior(y._handle, x._handle, 0.5), STATE)
+        refused(lib.oprl_replay_set_prior(x._handle, y._handle, 0.5), STATE, word, **LONG)
+        msg = refused(lib.oprl_replay_set_prior(y._handle, x._handle, 0.5), STATE, **LONG)
         assert word in msg and b"prior replay" in msg
         assert off(x._handle) == 0
     prio = PrioritizedEpisodicReplayBuffer(buffer_size_transitions=20, state_dim=12, action_dim=2, max_episode_lenth=5, device="cuda").create()
-    assert b"prioritized" in refused(lib.oprl_replay_set_prior(prio._handle, y._handle, 0.5), STATE)
-    msg = refused(lib.oprl_replay_set_prior(y._handle, prio._handle, 0.5), STATE)
+    refused(lib.oprl_replay_set_prior(prio._handle, y._handle, 0.5), STATE, b"prioritized", **LONG)
+    msg = refused(lib.oprl_replay_set_prior(y._handle, prio._handle, 0.5), STATE, **LONG)
     assert b"prioritized" in msg and b"prior replay" in msg
     # one prior per batch
-    assert b"prior of its own" in refused(lib.oprl_replay_set_prior(y._handle, h, 0.5), STATE)
+    refused(lib.oprl_replay_set_prior(y._handle, h, 0.5), STATE, b"prior of its own", **LONG)
     # ... and each of them changed nothing: x and y are still plain and without a prior, buf samples what it sampled
     rows = [t.zeros((4, w), device="cuda") for w in (12, 2, 1, 1, 12)]
     ptrs = [_capi.ptr(r) for r in rows]
     for r in (x, y):
-        assert b"no prior" in refused(lib.oprl_replay_sample_mix(r._handle, 4, None, 0, 0, *ptrs, None, None, None, _capi.current_stream()), STATE)
+        refused(lib.oprl_replay_sample_mix(r._handle, 4, None, 0, 0, *ptrs, None, None, None, _capi.current_stream()), STATE,
+                b"no prior", **LONG)
     assert_same(raw_sample(buf, 61, 2, 0, "oprl_replay_sample_mix"), before, "after the refusals")
     # a handle with a prior takes no n-step returns, no hindsight goals and no sum tree
     assert lib.oprl_replay_set_prior(x._handle, y._handle, 0.0) == 0          # (share 0 is allowed: the mode is on)
-    assert b"prior data" in refused(lib.oprl_replay_set_nstep(x._handle, 3, 0.99), STATE)
+    refused(lib.oprl_replay_set_nstep(x._handle, 3, 0.99), STATE, b"prior data", **LONG)
     assert lib.oprl_replay_set_nstep(x._handle, 1, 0.99) == 0                 # (n = 1 is the mode off: nothing to refuse)
-    assert b"prior data" in refused(lib.oprl_replay_set_her(x._handle, 6, 9, 3, 0.8, 0, 0, 0.1), STATE)
-    assert b"prior data" in refused(lib.oprl_replay_prio_enable(x._handle, 0.6, 1e-6, None), STATE)
+    refused(lib.oprl_replay_set_her(x._handle, 6, 9, 3, 0.8, 0, 0, 0.1), STATE, b"prior data", **LONG)
+    refused(lib.oprl_replay_prio_enable(x._handle, 0.6, 1e-6, None), STATE, b"prior data", **LONG)
     assert lib.oprl_replay_set_prior(x._handle, None, nan) == 0               # the mode off: the share is not read
     assert lib.oprl_replay_set_nstep(x._handle, 3, 0.99) == 0 and lib.oprl_replay_set_nstep(x._handle, 1, 0.99) == 0
     t.cuda.synchronize()
@@ -404,7 +366,7 @@ def test_group_step_n_refuses_a_mixed_replay(learner_replays):
     g = LearnerGroup(members)
     seeds = (C.c_uint64 * 2)(1, 2)
     lib = _capi.load()
-    assert b"prior data" in refused(lib.oprl_group_step_n(g.handle, buf.handle, 1, LB, seeds, _capi.current_stream()), STATE)
+    refused(lib.oprl_group_step_n(g.handle, buf.handle, 1, LB, seeds, _capi.current_stream()), STATE, b"prior data", **LONG)
     assert members[0].update_step == 0 and members[1].update_step == 0
 
 
@@ -423,29 +385,12 @@ def test_checkpoint_round_trip():
 
 
 # ---- learners ---------------------------------------------------------------------------------------------------------------
-def assert_same_state(a, b):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
+V_KEYS = ("value", "value_m", "value_v", "value_step")
+
+
+def assert_same_state(a, b):        # kept: IQL's V, its moments and its step count ride along when either learner has them
     x, y = a.state_dict(), b.state_dict()
-    for k in ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v", "value", "value_m", "value_v"):
-        assert (k in x) == (k in y)
-        if k in x:
-            assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    assert x.get("value_step") == y.get("value_step")
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), f"targets[{i}]"
-    assert ("log_alpha" in x) == ("log_alpha" in y)
-    for p, q in zip(x.get("log_alpha", []), y.get("log_alpha", [])):
-        assert t.equal(p, q), "log_alpha"
-    assert x["counters"] == y["counters"]
-
-
-def loop_updates(algo, buf, K, seed):
-    buf.seed = seed
-    for _ in range(K):
-        buf._sample_counter = algo.update_step
-        algo.update(*buf.sample(LB))
+    support.assert_same_state(a, b, extra=tuple(k for k in V_KEYS if k in x or k in y))
 
 
 @pytest.mark.parametrize("name,prec", [("ddpg", "f32"), ("td3", "x2"), ("sac", "f32"), ("tqc", "f32"), ("iql", "f32")])
@@ -456,7 +401,7 @@ def test_step_n_over_a_mixed_replay_equals_sample_then_update(learner_replays, n
     assert_same_state(fused, loop)
     print(name, prec, "launch form at B = 32:", fused.debug_form(LB))
     fused.learner.step_n(buf.handle, 3, LB, seed=11)
-    loop_updates(loop, buf, 3, 11)
+    loop_updates(loop, buf, 3, 11, LB)
     assert_same_state(fused, loop)
     assert fused.update_step == 3
     # the batch is mixed (the comparison above is not vacuous): half of it is the prior's plain sample
@@ -466,12 +411,12 @@ def test_step_n_over_a_mixed_replay_equals_sample_then_update(learner_replays, n
     assert src.sum().item() == 16 and t.equal(rows[0][:16], prior.sample(LB)[0][:16])
     # update_from_buffer over the buffer class: one more update, alone and with the next observation's action riding
     fused.update_from_buffer(buf, LB)
-    loop_updates(loop, buf, 1, 11)
+    loop_updates(loop, buf, 1, 11, LB)
     assert_same_state(fused, loop)
     obs = np.linspace(-1, 1, LS).astype(np.float32)
     fused.update_from_buffer(buf, LB, act_next=obs)
     act = fused.actor.explore(obs)
-    loop_updates(loop, buf, 1, 11)
+    loop_updates(loop, buf, 1, 11, LB)
     assert_same_state(fused, loop)
     assert fused.update_step == 5 and np.all(np.isfinite(act)) and np.shape(act)[-1] == LA
     # no flag is left behind: step_n over a plain replay, against the learner that never saw the mixed handle

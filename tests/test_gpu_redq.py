@@ -5,7 +5,6 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch as t
 
@@ -14,8 +13,10 @@ from oprl_amd.algos.redq import REDQ
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import scenarios as sc
-from tests.hip_adapters import cpu_params, hip_adam, split_like
+from tests.hip_adapters import cpu_params
 from tests.redq_oracle import REDQOracle
+from tests.support import (as_np, assert_same_state, check_step_n_equals_loop, fill_full_episodes, pair_adam, pair_nets, pair_q_y,
+                           run_pair, to_double, worst_ratio)
 
 pytestmark = pytest.mark.gpu
 
@@ -57,48 +58,24 @@ def batches(B, n):
     return out
 
 
-def run_pair(algo, oracles, data):
-    for s, a, r, d, s2, e1, e2 in data:
-        algo.update(*(x.cuda() for x in (s, a, r, d, s2)), noise=(e1.cuda(), e2.cuda()))
-        f = [x.double() for x in (s, a, r, d, s2, e1, e2)]
-        for o in oracles:
-            o.update(*f)
-    t.cuda.synchronize()
-    algo.learner.check()
+def step(algo, x):
+    algo.update(*(v.cuda() for v in x[:5]), noise=(x[5].cuda(), x[6].cuda()))
 
 
 def got_and_want(algo, o, B):
     L = algo.learner
     got, want = {}, {}
-    for i in range(N if algo.n_critics == N else algo.n_critics):
-        for l, (x, y) in enumerate(zip(cpu_params(algo.critic.nets[i]), o.critics[i])):
-            got[f"u.critic.{i}.{l}"], want[f"u.critic.{i}.{l}"] = x, y
-        for l, (x, y) in enumerate(zip(cpu_params(algo.critic_target.nets[i]), o.targets[i])):
-            got[f"u.critic_target.{i}.{l}"], want[f"u.critic_target.{i}.{l}"] = x, y
-    for l, (x, y) in enumerate(zip(cpu_params(algo.actor), o.actor)):
-        got[f"u.actor.{l}"], want[f"u.actor.{l}"] = x, y
-    for which, opt in (("critic", o.opt_critic), ("actor", o.opt_actor)):
-        m, v = hip_adam(algo, which)
-        for l in range(len(m)):
-            got[f"u.m_{which}.{l}"], want[f"u.m_{which}.{l}"] = m[l], opt.m[l]
-            got[f"u.v_{which}.{l}"], want[f"u.v_{which}.{l}"] = v[l], opt.v[l]
+    for i in range(algo.n_critics):
+        pair_nets(got, want, f"critic.{i}", algo.critic.nets[i], o.critics[i])
+        pair_nets(got, want, f"critic_target.{i}", algo.critic_target.nets[i], o.targets[i])
+    pair_nets(got, want, "actor", algo.actor, o.actor)
+    pair_adam(got, want, algo, "critic", o.opt_critic)
+    pair_adam(got, want, algo, "actor", o.opt_actor)
     got["u.log_alpha"], want["u.log_alpha"] = L.log_alpha.cpu().reshape(1), o.log_alpha.reshape(1)
     got["u.log_alpha_m"], want["u.log_alpha_m"] = L.log_alpha_m.cpu().reshape(1), o.opt_alpha.m[0]
     got["u.log_alpha_v"], want["u.log_alpha_v"] = L.log_alpha_v.cpu().reshape(1), o.opt_alpha.v[0]
-    q, y = algo.learner.debug_q_y(B)
-    got["u.q"], want["u.q"] = q.cpu(), o.last["q"].reshape(-1)
-    got["u.y"], want["u.y"] = y.cpu(), o.last["y"].reshape(-1)
-    as_np = lambda dct: {k: np.asarray(v.detach().cpu().double().numpy()) for k, v in dct.items()}   # noqa: E731
+    pair_q_y(got, want, algo, B, o.last["q"], o.last["y"])
     return as_np(got), as_np(want)
-
-
-def worst_ratio(got, want):
-    """max over keys of (deviation / the key's gate)"""
-    w = 0.0
-    for k, v in want.items():
-        lim = sc.PARAM_TOL if sc._is_param_key(k) else TOL
-        w = max(w, sc.rel_dev(got[k], v) / lim)
-    return w
 
 
 PARITY = [(256, 2), (256, 1), (256, 3), (100, 2)]
@@ -111,7 +88,7 @@ def test_redq_matches_the_oracle(B, n_min):
     M = 3 takes the minimum through k_redq_min; B = 100 is a ragged batch."""
     algo = make(n_min, B)
     o = oracle_for(algo, n_min)
-    run_pair(algo, [o], batches(B, 4))
+    run_pair(algo, [o], batches(B, 4), step, to_double)
     assert algo.learner.update_count == 4
     got, want = got_and_want(algo, o, B)
     sc.compare(got, want, TOL, param_tol=sc.PARAM_TOL)
@@ -125,11 +102,11 @@ def test_the_comparison_discriminates():
     right = oracle_for(algo, 2)
     wrong = {"subset of u+1": oracle_for(algo, 2, subset_shift=1), "mean": oracle_for(algo, 2, use_mean=True),
              "polyak on actor steps": oracle_for(algo, 2, polyak_on_actor_steps=True)}
-    run_pair(algo, [right, *wrong.values()], batches(B, 4))
+    run_pair(algo, [right, *wrong.values()], batches(B, 4), step, to_double)
     got, want = got_and_want(algo, right, B)
     sc.compare(got, want, TOL, param_tol=sc.PARAM_TOL)
     for name, o in wrong.items():
-        r = worst_ratio(*got_and_want(algo, o, B))
+        r, _key = worst_ratio(*got_and_want(algo, o, B), TOL)
         assert r >= 10.0, f"{name}: the learner is only {r:.1f} gates away from the wrong oracle"
 
 
@@ -155,48 +132,16 @@ def _replay(dev, seed=0, E=40, Lep=100):
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
     buf = EpisodicReplayBuffer(buffer_size_transitions=E * Lep, state_dim=S, action_dim=A, device=str(dev),
                                seed=seed, max_episode_lenth=Lep).create()
-    g = t.Generator(device=dev).manual_seed(4321)
-    buf._tensors["states"].copy_(t.randn((E, Lep + 1, S), device=dev, generator=g))
-    buf._tensors["actions"].copy_(t.rand((E, Lep, A), device=dev, generator=g) * 2 - 1)
-    buf._tensors["rewards"].copy_(t.rand((E, Lep, 1), device=dev, generator=g))
-    buf._tensors["dones"].copy_((t.rand((E, Lep, 1), device=dev, generator=g) < 0.02).float())
-    buf.ep_lens = [Lep] * E
-    buf.episodes_counter = E
-    buf._number_transitions = E * Lep
-    buf._lens_dirty = True
+    fill_full_episodes(buf, E, Lep)
     return buf
-
-
-def _assert_same_state(a, b):
-    x, y = a.state_dict(), b.state_dict()
-    assert x["counters"] == y["counters"], (x["counters"], y["counters"])
-    for k in ("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"):
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    for i, (p, q) in enumerate(zip(x["targets"], y["targets"])):
-        assert t.equal(p, q), f"targets[{i}]"
-    for i, (p, q) in enumerate(zip(x["log_alpha"], y["log_alpha"])):
-        assert t.equal(p, q), f"log_alpha[{i}]"
 
 
 def test_step_n_equals_sample_then_update_bitwise():
     """step_n(K = G) over a replay with 2 % done rows is bit for bit G times sample() + update() with the sampler's rows."""
     B, dev = 256, t.device("cuda", 0)
     buf = _replay(dev)
-    fused, loop = make(2, B), make(2, B)
-    loop.load_state_dict(fused.state_dict())
-    n_done = 0
-    for seed in (3, 5):
-        fused.learner.step_n(buf.handle, G, B, seed=seed)
-        buf.seed = seed
-        for _ in range(G):
-            buf._sample_counter = loop.update_step
-            batch = buf.sample(B)
-            n_done += int(batch[3].sum().item())
-            loop.update(*batch)
-        t.cuda.synchronize()
-        fused.learner.check()
-        _assert_same_state(fused, loop)
-    assert n_done > 0
+    fused, _loop, n_done = check_step_n_equals_loop(lambda: (make(2, B), make(2, B)), buf, B, K=G)
+    assert n_done > 0 and "log_alpha" in fused.state_dict()
 
 
 def test_resume_in_the_middle_of_a_group():
@@ -205,15 +150,15 @@ def test_resume_in_the_middle_of_a_group():
     data = batches(B, 5)
     a = make(2, B)
     for x in data[:1]:
-        a.update(*(v.cuda() for v in x[:5]), noise=(x[5].cuda(), x[6].cuda()))
+        step(a, x)
     b = make(2, B)
     b.load_state_dict(a.state_dict())
     for x in data[1:]:
         for algo in (a, b):
-            algo.update(*(v.cuda() for v in x[:5]), noise=(x[5].cuda(), x[6].cuda()))
-    t.cuda.synchronize()
+            step(algo, x)
     assert a.update_step == 5
-    _assert_same_state(a, b)
+    assert_same_state(a, b)
+    assert "log_alpha" in a.state_dict()
 
 
 @pytest.mark.parametrize("kw,msg", [

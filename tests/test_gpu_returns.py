@@ -17,9 +17,9 @@ import torch as t
 from oprl_amd import _capi
 from tests import calql_oracle as cal
 from tests import prior_oracle as po
+from tests.support import INVALID, STATE, fill_random, refused, set_table
 
 pytestmark = pytest.mark.gpu
-INVALID, STATE = -1, -3
 E, L, S, A = 8, 150, 5, 2
 LENS = [150, 129, 128, 65, 64, 63, 1, 0]
 PE, PL, P_LENS = 3, 12, [12, 5, 1]
@@ -59,16 +59,10 @@ _cache: dict = {}
 
 
 def fill(buf, r, d, lens):
-    gen = t.Generator(device="cuda").manual_seed(77)
-    for k in ("states", "actions"):
-        v = buf._tensors[k]
-        v.copy_(t.randn(v.shape, device="cuda", generator=gen))
+    fill_random(buf, ("states", "actions"), gen_seed=77)
     buf._tensors["rewards"].copy_(t.as_tensor(r).reshape(buf._tensors["rewards"].shape))
     buf._tensors["dones"].copy_(t.as_tensor(d).reshape(buf._tensors["dones"].shape))
-    buf.ep_lens = [int(x) for x in lens] + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = int(sum(lens))
-    buf._lens_dirty = True
+    set_table(buf, lens)
     return buf
 
 
@@ -248,12 +242,6 @@ def test_rows_staged_and_not_yet_flushed_are_seen():
     args = ((None, None, pr, pd), p_lens, (None, None, mr, md), m_lens, 0.5, ep, step, 0.9)
     check(mix.returns_to_go(ep, step, 0.9), ep, step, 0.9, "staged rows, both sources", want=cal.mixed_returns(*args),
           tol=cal.mixed_returns(*args, fn=cal.tolerance), exact=cal.mixed_returns(*args, fn=cal.returns_f32))
-
-
-def refused(rc, status, word):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert word in msg, (word, msg)
 
 
 def test_refusals():

@@ -14,7 +14,6 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch as t
 
@@ -24,7 +23,9 @@ from oprl_amd.algos.td3_bc import TD3BC
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests import scenarios as sc
-from tests.hip_adapters import cpu_params, hip_adam, load_params
+from tests.hip_adapters import load_params
+from tests.support import (INVALID, STATE, as_np, assert_same_state, check_resume, check_step_n_equals_loop, counters, pair_adam,
+                           pair_nets, pair_q_y, random_replay, refused, run_pair, worst_ratio)
 from tests.td3bc_oracle import TD3BCOracle
 
 pytestmark = pytest.mark.gpu
@@ -68,40 +69,17 @@ def step(algo, x):
     algo.update(*(v.cuda() for v in x[:5]), noise=x[5].cuda())
 
 
-def run_pair(algo, oracles, data):
-    for x in data:
-        step(algo, x)
-        for o in oracles:
-            o.update(*x)
-    t.cuda.synchronize()
-    algo.learner.check()
-
-
 def got_and_want(algo, o, B):
     got, want = {}, {}
-    for name, mod, ref in (("critic", algo.critic, o.critic), ("critic_target", algo.critic_target, o.critic_target),
-                           ("actor", algo.actor, o.actor), ("actor_target", algo.actor_target, o.actor_target)):
-        for l, (x, y) in enumerate(zip(cpu_params(mod), ref)):
-            got[f"u.{name}.{l}"], want[f"u.{name}.{l}"] = x, y
-    for which, opt in (("critic", o.opt_critic), ("actor", o.opt_actor)):
-        m, v = hip_adam(algo, which)
-        for l in range(len(m)):
-            got[f"u.m_{which}.{l}"], want[f"u.m_{which}.{l}"] = m[l], opt.m[l]
-            got[f"u.v_{which}.{l}"], want[f"u.v_{which}.{l}"] = v[l], opt.v[l]
-    q, y = algo.learner.debug_q_y(B)
-    got["u.q"], want["u.q"] = q.cpu(), o.last["q1"].reshape(-1)
-    got["u.y"], want["u.y"] = y.cpu(), o.last["y"].reshape(-1)
+    for name in ("critic", "critic_target", "actor", "actor_target"):
+        pair_nets(got, want, name, getattr(algo, name), getattr(o, name))
+    pair_adam(got, want, algo, "critic", o.opt_critic)
+    pair_adam(got, want, algo, "actor", o.opt_actor)
+    pair_q_y(got, want, algo, B, o.last["q1"], o.last["y"])
     bc = algo.learner.read_bc()
     for k in ("bc_lambda", "q_abs_mean", "bc_mse"):
         got[f"u.{k}"], want[f"u.{k}"] = t.tensor([bc[k]]), o.last_actor[k].reshape(1)
-    as_np = lambda dct: {k: np.asarray(v.detach().cpu().double().numpy()) for k, v in dct.items()}   # noqa: E731
     return as_np(got), as_np(want)
-
-
-def worst_ratio(got, want):
-    """max over the parameter, target and moment keys of (deviation / the parameter gate): lambda and the cloning term
-    themselves, which a wrong oracle misses trivially, do not count"""
-    return max(sc.rel_dev(got[k], v) / sc.PARAM_TOL for k, v in want.items() if sc._is_param_key(k))
 
 
 PARITY = [("walker", 256), ("walker", 100), ("cheetah", 256), ("cheetah", 100)]
@@ -117,7 +95,7 @@ def test_td3bc_matches_the_oracle(env, B):
     algo = make(env, B, fixture_nets=True)
     o = oracle_for(env, algo)
     wrong = {"no_bc": oracle_for(env, algo, no_bc=True), "no_lambda": oracle_for(env, algo, no_lambda=True)}
-    run_pair(algo, [o, *wrong.values()], data)
+    run_pair(algo, [o, *wrong.values()], data, step)
     assert algo.learner.update_count == 4 and algo.learner.state_dict()["counters"][:3] == [4, 4, 2]
     got, want = got_and_want(algo, o, B)
     for k in ("bc_lambda", "q_abs_mean", "bc_mse"):
@@ -128,25 +106,14 @@ def test_td3bc_matches_the_oracle(env, B):
     assert scal["actor_loss"] == pytest.approx(float(o.last_actor["actor_loss"]), rel=1e-4)       # TD3's meaning: -mean Q1(s, pi)
     assert scal["critic_loss"] == pytest.approx(float(o.last["critic_loss"]), rel=1e-4)
     for name, w in wrong.items():
-        r = worst_ratio(*got_and_want(algo, w, B))
+        # (the parameter, target and moment keys only: lambda and the cloning term themselves, which a wrong oracle misses
+        # trivially, do not count)
+        r, _key = worst_ratio(*got_and_want(algo, w, B), TOL, params_only=True)
         print(f"{env} B={B}: {name} is {r:.0f} gates away")
         assert r >= 10.0, f"{name}: the learner is only {r:.1f} gates away from the wrong oracle"
 
 
 # ---- bitwise links -----------------------------------------------------------------------------------------------------
-def assert_same_state(a, b, keys=("actor", "actor_m", "actor_v", "critic", "critic_m", "critic_v"), targets=(0, 1), counters=True):
-    t.cuda.synchronize()
-    a.learner.check()
-    b.learner.check()
-    x, y = a.state_dict(), b.state_dict()
-    if counters:
-        assert x["counters"] == y["counters"], (x["counters"], y["counters"])
-    for k in keys:
-        assert t.equal(x[k], y[k]), (k, (x[k] - y[k]).abs().max().item())
-    for i in targets:
-        assert t.equal(x["targets"][i], y["targets"][i]), f"targets[{i}]"
-
-
 def test_the_critic_step_of_update_0_is_plain_td3s():
     """The critic steps before the actor: after update 0 the critics, their moments and (Polyak of the stepped critics)
     their targets equal a plain no_fuse TD3's from the same nets, batch and noise, bit for bit; the actors do not."""
@@ -183,26 +150,7 @@ def test_with_the_mode_off_it_is_plain_td3_again():
     assert not t.equal(bc.learner.actor_arena, plain.learner.actor_arena)
 
 
-RB, E, LEP, NSTEP = 64, 40, 30, 3
-
-
-def replay(env, nstep):
-    """E episodes of random length with 10 % done rows, every row random normal; n-step mode or plain."""
-    from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer
-    from oprl_amd.buffers.nstep_buffer import NStepEpisodicReplayBuffer
-    S, A = fx.ENVS[env]
-    kw = dict(buffer_size_transitions=E * LEP, state_dim=S, action_dim=A, max_episode_lenth=LEP, device="cuda", seed=7)
-    buf = (NStepEpisodicReplayBuffer(n_step=NSTEP, gamma=GAMMA, **kw) if nstep else EpisodicReplayBuffer(**kw)).create()
-    gen = t.Generator(device="cuda").manual_seed(1000)
-    for v in buf._tensors.values():
-        v.copy_(t.randn(v.shape, device="cuda", generator=gen))
-    buf._tensors["dones"].copy_(t.as_tensor((np.random.RandomState(6).rand(E, LEP, 1) < 0.1).astype(np.float32)))
-    lens = [int(x) for x in np.random.RandomState(4).randint(1, LEP + 1, size=E)]
-    buf.ep_lens = lens + [0] * (buf._max_episodes - len(lens))
-    buf.episodes_counter = len(lens)
-    buf._number_transitions = sum(lens)
-    buf._lens_dirty = True
-    return buf
+RB, NSTEP = 64, 3
 
 
 @pytest.mark.parametrize("nstep", [False, True], ids=["plain", "nstep3"])
@@ -210,16 +158,8 @@ def test_step_n_equals_sample_then_update_bitwise(nstep):
     """step_n(3) is bit for bit three sample() + update() pairs (the target noise drawn on the device in both), over a
     plain replay and over an n-step replay (n = 3)."""
     env = "cheetah"
-    buf = replay(env, nstep)
-    fused, loop = make(env, RB), make(env, RB)
-    loop.load_state_dict(fused.state_dict())
-    for seed in (3, 5):
-        fused.learner.step_n(buf.handle, 3, RB, seed=seed)
-        buf.seed = seed
-        for _ in range(3):
-            buf._sample_counter = loop.update_step
-            loop.update(*buf.sample(RB))
-        assert_same_state(fused, loop)
+    buf = random_replay(env, NSTEP if nstep else None, GAMMA)
+    fused, loop, _ = check_step_n_equals_loop(lambda: (make(env, RB), make(env, RB)), buf, RB)
     assert fused.update_step == 6
     assert not t.equal(fused.learner.actor_arena, make(env, RB).learner.actor_arena)   # (it trained)
     assert fused.learner.read_bc() == loop.learner.read_bc() and fused.learner.read_bc()["bc_lambda"] > 0
@@ -228,17 +168,8 @@ def test_step_n_equals_sample_then_update_bitwise(nstep):
 def test_resume():
     """A checkpoint taken after three updates, loaded into a fresh learner, gives bit-identical state after three more."""
     env, B = "walker", 100
-    data = batches(env, B, 6)
-    a = make(env, B)
-    for x in data[:3]:
-        step(a, x)
-    b = make(env, B)
-    b.load_state_dict(a.state_dict())
-    for x in data[3:]:
-        step(a, x)
-        step(b, x)
+    a, _b, _sd = check_resume(lambda: make(env, B), step, batches(env, B, 6), 3)
     assert a.update_step == 6
-    assert_same_state(a, b)
 
 
 def test_a_td3_learner_of_the_same_process_is_untouched():
@@ -263,20 +194,6 @@ def test_a_td3_learner_of_the_same_process_is_untouched():
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------
-INVALID, STATE = -1, -3
-
-
-def refused(rc, status, word):
-    msg = _capi.load().oprl_last_error()
-    assert rc == status, (rc, status, msg)
-    assert word in msg, (word, msg)
-
-
-def counters(algo):
-    t.cuda.synchronize()
-    return algo.learner.state_dict()["counters"]
-
-
 def test_refusals():
     """Every case DESIGN.md §16 lists as refused returns its status with a message that names the reason; the update
     count and the Adam step counts stay where they were, and a refused learner goes on as what it was."""

@@ -12,6 +12,7 @@ import pytest
 
 from oprl_amd import _capi
 from tests import her_oracle as ho
+from tests import support
 from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -20,24 +21,14 @@ HER_FUNCS = {"oprl_replay_set_her": 8, "oprl_replay_sample_her": 14}
 
 def cpu_buffer(**kw):
     from oprl_amd.buffers.hindsight_buffer import HindsightEpisodicReplayBuffer
-    args = dict(buffer_size_transitions=350, state_dim=12, action_dim=3, max_episode_lenth=50, goal_dim=3,
-                achieved_offset=6, desired_offset=9, threshold=0.1)
-    args.update(kw)
-    return HindsightEpisodicReplayBuffer(**args)
+    args = dict(state_dim=12, action_dim=3, goal_dim=3, achieved_offset=6, desired_offset=9, threshold=0.1)
+    return support.cpu_buffer(HindsightEpisodicReplayBuffer, **{**args, **kw})
 
 
 # ---- ABI and bindings ---------------------------------------------------------------------------------------------------
 def test_her_functions_are_declared_bound_and_exported():
-    lib = _capi.load()
-    assert _capi.OPRL_ABI_VERSION == 4 and lib.oprl_abi_version() == 4 and len(_capi.ALGO) == 6
-    header = (ROOT / "include" / "oprl_amd.h").read_text()
-    assert "#define OPRL_ABI_VERSION 4" in header
-    for name, arity in HER_FUNCS.items():
-        assert f"int {name}(" in header
-        assert name in _capi.SIGNATURES and hasattr(lib, name)
-        assert len(_capi.SIGNATURES[name][1]) == arity
-        decl = header.split(f"int {name}(", 1)[1].split(");", 1)[0]
-        assert decl.count(",") + 1 == arity, (name, decl)
+    support.assert_abi_bound(HER_FUNCS)
+    assert len(_capi.ALGO) == 6
 
 
 def test_her_functions_refuse_null_handles_without_a_gpu():
@@ -50,8 +41,7 @@ def test_her_functions_refuse_null_handles_without_a_gpu():
 
 
 def test_source_is_built_and_alias_resolves():
-    from oprl_amd import build
-    assert "replay_her.hip" in build.SOURCES and (build.CSRC / "replay_her.hip").exists()
+    support.assert_source_built("replay_her", header=False)
     from oprl.buffers.hindsight_buffer import HindsightEpisodicReplayBuffer as Aliased
     from oprl.environment.synthetic_goal import SyntheticGoalEnv as AliasedEnv
     from oprl_amd.buffers.episodic_buffer import EpisodicReplayBuffer

@@ -23,6 +23,7 @@ from oracle import fixtures as fx
 from tests import ln_oracle as lno
 from tests import scenarios as sc
 from tests.config_scripts import load_config
+from tests.support import assert_abi_bound, assert_source_built
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_learner_set_layernorm": 2, "oprl_mlp_ln": 19}
@@ -30,16 +31,8 @@ TOL = 2e-5
 
 
 def test_the_abi_additions_are_bound():
-    assert _capi.OPRL_ABI_VERSION == 4
-    lib = _capi.load()
-    assert lib.oprl_abi_version() == 4
-    header = (ROOT / "include" / "oprl_amd.h").read_text()
-    assert "#define OPRL_ABI_VERSION 4" in header and "typedef struct oprl_layernorm {" in header
-    for name, n_args in ENTRIES.items():
-        assert hasattr(lib, name)
-        res, args = _capi.SIGNATURES[name]
-        assert res is C.c_int and len(args) == n_args
-        assert f"int {name}(" in header
+    lib, header = assert_abi_bound(ENTRIES)
+    assert "typedef struct oprl_layernorm {" in header
     assert [f for f, _ in _capi.OprlLayerNorm._fields_] == ["theta", "theta_target", "adam_m", "adam_v", "eps"]
     # null handles and structs are refused without a GPU
     d = _capi.OprlLayerNorm()
@@ -48,9 +41,7 @@ def test_the_abi_additions_are_bound():
 
 
 def test_the_build_lists_the_new_source():
-    from oprl_amd import build
-    assert "ln_slice.hip" in build.SOURCES
-    assert (build.CSRC / "ln_slice.hip").exists() and (build.CSRC / "ln_slice.h").exists()
+    assert_source_built("ln_slice")
 
 
 def test_layer_norm_is_the_last_public_field_and_off_by_default():

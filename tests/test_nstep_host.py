@@ -10,24 +10,18 @@ import pytest
 
 from oprl_amd import _capi
 from tests import nstep_oracle as no
+from tests import support
 
 NSTEP_FUNCS = ["oprl_replay_set_nstep", "oprl_replay_sample_nstep"]
 
 
 def cpu_buffer(**kw):
     from oprl_amd.buffers.nstep_buffer import NStepEpisodicReplayBuffer
-    return NStepEpisodicReplayBuffer(buffer_size_transitions=350, state_dim=3, action_dim=1, max_episode_lenth=50, **kw)
+    return support.cpu_buffer(NStepEpisodicReplayBuffer, **{**dict(state_dim=3, action_dim=1), **kw})
 
 
 def test_nstep_functions_are_declared_bound_and_exported():
-    from pathlib import Path
-    lib = _capi.load()
-    assert _capi.OPRL_ABI_VERSION == 4 and lib.oprl_abi_version() == 4
-    header = (Path(__file__).resolve().parents[1] / "include" / "oprl_amd.h").read_text()
-    assert "#define OPRL_ABI_VERSION 4" in header
-    for name in NSTEP_FUNCS:
-        assert f"int {name}(" in header
-        assert name in _capi.SIGNATURES and hasattr(lib, name)
+    support.assert_abi_bound(NSTEP_FUNCS)
 
 
 def test_nstep_functions_refuse_null_handles_without_a_gpu():

@@ -10,6 +10,7 @@ import pytest
 
 from oprl_amd import _capi
 from tests import per_oracle as po
+from tests import support
 
 PRIO_FUNCS = ["oprl_replay_prio_enable", "oprl_replay_prio_sample", "oprl_replay_prio_update",
               "oprl_replay_prio_read", "oprl_replay_prio_load"]
@@ -17,15 +18,11 @@ PRIO_FUNCS = ["oprl_replay_prio_enable", "oprl_replay_prio_sample", "oprl_replay
 
 def cpu_buffer(**kw):
     from oprl_amd.buffers.prioritized_buffer import PrioritizedEpisodicReplayBuffer
-    return PrioritizedEpisodicReplayBuffer(buffer_size_transitions=350, state_dim=3, action_dim=1,
-                                           max_episode_lenth=50, **kw)
+    return support.cpu_buffer(PrioritizedEpisodicReplayBuffer, **{**dict(state_dim=3, action_dim=1), **kw})
 
 
 def test_prio_functions_are_exported_and_bound():
-    lib = _capi.load()
-    assert _capi.OPRL_ABI_VERSION == 4 and lib.oprl_abi_version() == 4
-    for name in PRIO_FUNCS:
-        assert name in _capi.SIGNATURES and hasattr(lib, name)
+    support.assert_abi_bound(PRIO_FUNCS)
 
 
 def test_prio_functions_refuse_bad_arguments_without_a_gpu():

@@ -14,6 +14,7 @@ import pytest
 
 from oprl_amd import _capi
 from tests import prior_oracle as po
+from tests import support
 from tests.config_scripts import load_config
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -29,24 +30,13 @@ def plain_buffer(**kw):
 
 def cpu_buffer(prior="default", **kw):
     from oprl_amd.buffers.prior_buffer import PriorDataReplayBuffer
-    args = dict(buffer_size_transitions=350, state_dim=5, action_dim=2, max_episode_lenth=50,
-                prior=plain_buffer() if isinstance(prior, str) else prior)
-    args.update(kw)
-    return PriorDataReplayBuffer(**args)
+    args = dict(state_dim=5, action_dim=2, prior=plain_buffer() if isinstance(prior, str) else prior)
+    return support.cpu_buffer(PriorDataReplayBuffer, **{**args, **kw})
 
 
 # ---- ABI and bindings ---------------------------------------------------------------------------------------------------
 def test_prior_functions_are_declared_bound_and_exported():
-    lib = _capi.load()
-    assert _capi.OPRL_ABI_VERSION == 4 and lib.oprl_abi_version() == 4
-    header = (ROOT / "include" / "oprl_amd.h").read_text()
-    assert "#define OPRL_ABI_VERSION 4" in header
-    for name, arity in PRIOR_FUNCS.items():
-        assert f"int {name}(" in header
-        assert name in _capi.SIGNATURES and hasattr(lib, name)
-        assert len(_capi.SIGNATURES[name][1]) == arity
-        decl = header.split(f"int {name}(", 1)[1].split(");", 1)[0]
-        assert decl.count(",") + 1 == arity, (name, decl)
+    support.assert_abi_bound(PRIOR_FUNCS)
     # the arity and shape of oprl_replay_sample_her
     assert _capi.SIGNATURES["oprl_replay_sample_mix"] == _capi.SIGNATURES["oprl_replay_sample_her"]
 
@@ -60,8 +50,7 @@ def test_prior_functions_refuse_null_handles_without_a_gpu():
 
 
 def test_source_is_built_and_alias_resolves():
-    from oprl_amd import build
-    assert "replay_mix.hip" in build.SOURCES and (build.CSRC / "replay_mix.hip").exists()
+    support.assert_source_built("replay_mix", header=False)
     from oprl.buffers.prior_buffer import PriorDataReplayBuffer as Aliased
     from oprl.environment.normalized import NormalizedObsEnv as AliasedEnv
     from oprl.trainers.finetune import finetune as aliased_finetune

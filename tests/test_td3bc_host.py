@@ -3,37 +3,25 @@ source, the alias import works, configs/td3_bc.py parses its flags and refuses w
 refuses it refuses before the GPU is touched, and the oracle's hand-written gradient is autograd's."""
 from __future__ import annotations
 
-import ctypes as C
 import sys
 from pathlib import Path
 
 import pytest
 import torch as t
 
-from oprl_amd import _capi
 from oprl_amd.algos.td3_bc import TD3BC
 from oprl_amd.logging import NullLogger
 from oracle import fixtures as fx
 from tests.td3bc_oracle import TD3BCOracle
 from tests.config_scripts import load_config
+from tests.support import assert_abi_bound, assert_class_refuses, assert_source_built, small_nets
 
 ROOT = Path(__file__).resolve().parents[1]
 ENTRIES = {"oprl_learner_set_bc": 2, "oprl_learner_read_bc": 3, "oprl_bc_seed": 12}
 
 
 def test_the_abi_additions_are_bound():
-    assert _capi.OPRL_ABI_VERSION == 4 and "td3bc" not in _capi.ALGO and len(_capi.ALGO) == 6   # a mode, not an algorithm
-    lib = _capi.load()
-    assert lib.oprl_abi_version() == 4
-    header = (ROOT / "include" / "oprl_amd.h").read_text()
-    assert "#define OPRL_ABI_VERSION 4" in header
-    for name, n_args in ENTRIES.items():
-        assert hasattr(lib, name)
-        res, args = _capi.SIGNATURES[name]
-        assert res is C.c_int and len(args) == n_args
-        assert f"int {name}(" in header
-    # the hyper-parameter struct is where it was: BC is no field of it
-    assert [f[0] for f in _capi.OprlHparams._fields_][-2:] == ["v_min", "v_max"]
+    lib, _header = assert_abi_bound(ENTRIES, mode_name="td3bc")          # a mode, not an algorithm: BC is no field of the hparams
     # null arguments are refused without a GPU
     assert lib.oprl_learner_set_bc(None, 2.5) == -1 and b"null" in lib.oprl_last_error()
     assert lib.oprl_learner_read_bc(None, None, None) == -1 and b"null" in lib.oprl_last_error()
@@ -42,9 +30,7 @@ def test_the_abi_additions_are_bound():
 
 
 def test_the_build_lists_the_new_source():
-    from oprl_amd import build
-    assert "bc_seed.hip" in build.SOURCES
-    assert (build.CSRC / "bc_seed.hip").exists() and (build.CSRC / "bc_seed.h").exists()
+    assert_source_built("bc_seed")
 
 
 def test_exports():
@@ -110,14 +96,7 @@ def test_the_class_refuses_before_any_gpu_call(kw, msg, monkeypatch):
     """ValueError at construction; and again from create() for fields set afterwards — before require_gpu, which a
     machine without a GPU would fail with RuntimeError instead."""
     import oprl_amd.algos.td3 as mod
-    monkeypatch.setattr(mod, "require_gpu", lambda device: pytest.fail("the GPU was asked for"))
-    with pytest.raises(ValueError, match=msg):
-        TD3BC(logger=NullLogger(), state_dim=4, action_dim=2, **kw)
-    algo = TD3BC(logger=NullLogger(), state_dim=4, action_dim=2)
-    for k, v in kw.items():
-        setattr(algo, k, v)
-    with pytest.raises(ValueError, match=msg):
-        algo.create()
+    assert_class_refuses(TD3BC, mod, kw, msg, monkeypatch)
 
 
 def test_a_prioritized_buffer_is_refused():
@@ -132,8 +111,7 @@ def test_a_prioritized_buffer_is_refused():
 # ---- the oracle ----------------------------------------------------------------------------------------------------------
 def small_oracle(**kw):
     S, A = 5, 3
-    nets = [fx.make_net(11, [S, 16, 16, A]), fx.make_net(12, [S + A, 16, 16, 1]), fx.make_net(13, [S + A, 16, 16, 1])]
-    return TD3BCOracle(S, A, *nets, **kw), S, A
+    return TD3BCOracle(S, A, *small_nets(S, A), **kw), S, A
 
 
 @pytest.mark.parametrize("kw", [{}, dict(no_bc=True), dict(no_lambda=True), dict(bc_alpha=0.3)],
