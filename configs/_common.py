@@ -124,20 +124,41 @@ LAYER_NORM_FLAG = ("--layer-norm", bool, False,
                    "sequence, f32, one learner; not with --per")
 
 
+DROPOUT_FLAG = ("--dropout", float, 0.0,
+                "dropout rate in front of the critics' LayerNorm (Linear -> Dropout -> LayerNorm -> ReLU; DroQ): needs "
+                "--layer-norm (configs/droq.py has both on)")
+
+
 def layer_norm_kwargs(args: Namespace) -> dict:
-    return dict(layer_norm=bool(args.layer_norm))
+    kw = dict(layer_norm=bool(args.layer_norm))
+    if args.dropout > 0.0:
+        kw["dropout"] = float(args.dropout)
+    return kw
+
+
+def droq_kwargs(args: Namespace) -> dict:
+    """configs/droq.py: LayerNorm is the recipe's; ``--dropout`` replaces the class's rate only where it is given."""
+    return dict(dropout=float(args.dropout)) if args.dropout > 0.0 else {}
 
 
 @dataclass
 class LayerNormScript(TrainingScript):
-    """configs/sac.py and configs/redq.py: ``--layer-norm`` sets the algorithm's ``layer_norm`` field."""
+    """configs/sac.py, configs/redq.py and configs/droq.py: ``--layer-norm`` sets the algorithm's ``layer_norm`` field,
+    ``--dropout RATE`` its ``dropout``.  ``recipe``: the algorithm's own defaults have both on (DroQ)."""
 
-    extra_flags: tuple = (LAYER_NORM_FLAG,)
+    extra_flags: tuple = (LAYER_NORM_FLAG, DROPOUT_FLAG)
     algo_kwargs: Callable[[Namespace], dict] | None = layer_norm_kwargs
+    recipe: bool = False
 
     def refuse(self) -> None:
         super().refuse()
+        if not 0.0 <= self.args.dropout < 1.0:
+            raise ValueError(f"--dropout {self.args.dropout!r}: the rate must lie in [0, 1)")
+        if self.recipe:
+            self.args.layer_norm = True
         if not self.args.layer_norm:
+            if self.args.dropout > 0.0:
+                raise ValueError("--dropout without --layer-norm: dropout runs inside the LayerNorm critics' kernels")
             return
         if self.per:
             raise ValueError("--layer-norm with --per: the LayerNorm critics' kernels take no importance weights")

@@ -16,6 +16,8 @@
  *                    (Nakamoto et al. 2023, Cal-QL), the calibrated form of that mode
  *   oprl_learner_set_layernorm, oprl_mlp_ln   no counterpart: layer normalisation in the critics of a SAC / REDQ learner
  *                    (the RLPD / DroQ critic block)
+ *   oprl_learner_set_dropout, oprl_mlp_ln_drop   no counterpart: Philox dropout in front of that normalisation (Hiraoka
+ *                    et al. 2022, DroQ)
  *   oprl_replay_*    ReplayBufferProtocol              buffers/protocols.py:6-26
  *                    EpisodicReplayBuffer.{add_transition,sample}  buffers/episodic_buffer.py:81-133
  *   oprl_mlp_*       MLP / Critic / policies forward      algos/nn_models.py:27-194
@@ -779,6 +781,28 @@ int oprl_learner_set_layernorm(oprl_learner* h, const oprl_layernorm* ln);
 int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1, int32_t k1,
                 int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows, float* dz_rows,
                 float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream);
+
+/* ---- Dropout in the LayerNorm critics (Hiraoka et al. 2022, DroQ): Linear -> Dropout -> LayerNorm -> ReLU.
+ * Per hidden layer l in {0, 1}, batch row b and column c: zd = keep(b, l, c) ? z scale : 0 with scale = 1.0f / (1.0f - rate)
+ * in float32, and the LayerNorm above is taken of zd; backward, dL/dz = keep ? dL/dzd scale : 0.  The mask is
+ *   keep = philox4x32_10(ctr = (lo32 T, hi32 T, b, l 64 + c / 4), key = (lo32 K, hi32 K))[c % 4] >= (uint32)((double)rate 2^32)
+ * with K the learner's noise key of stream 6 and T = (u 4 + k) 16 + j: u the learner's update count before the update (the
+ * counter of oprl_redq_subset), k the pass (0: target critics on (s', a'); 1: the critic step on (s, a); 2: the actor phase's
+ * critics on (s, pi)), j the critic's index.  Dropout runs in every pass that evaluates a critic; nothing of the mask is
+ * stored (a backward regenerates it), and a checkpoint needs nothing beyond the update count.
+ * Called once, after oprl_learner_set_layernorm and before the first update.  rate 0, or a rate so small that its
+ * threshold (uint32)(rate 2^32) is 0, leaves the mode off and is no error (it does not count as the one call).
+ * OPRL_ERR_INVALID: a null handle; a rate that is NaN, negative or >= 1.  OPRL_ERR_STATE: the LN mode is off, a second
+ * call, a learner that has updated.  Everything the LN mode refuses stays refused.  A refused call changes nothing. */
+int oprl_learner_set_dropout(oprl_learner* h, float rate);
+/* oprl_mlp_ln with that dropout at `rate` from the Philox key `key` and the stream `stream_id` (the T above; all 64 bits
+ * count), b the row's index in the batch.  split = 1: the backward-only launch regenerates the forward launch's mask (the
+ * same bits as split = 0).  rate 0 is oprl_mlp_ln.  OPRL_ERR_INVALID beyond oprl_mlp_ln's: a rate that is NaN, negative or
+ * >= 1.  The kernel tests' entry point. */
+int oprl_mlp_ln_drop(const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1, int32_t k1,
+                     int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows, float* dz_rows,
+                     float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream, float rate, uint64_t key,
+                     uint64_t stream_id);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ import sys as _sys
 _SUBMODULES = [
     "logging", "parse_args",
     "algos", "algos.protocols", "algos.base_algorithm", "algos.nn_models", "algos.nn_functions",
-    "algos.ddpg", "algos.td3", "algos.sac", "algos.tqc", "algos.redq", "algos.d4pg", "algos.td3_bc", "algos.iql", "algos.cql", "algos.calql",
+    "algos.ddpg", "algos.td3", "algos.sac", "algos.tqc", "algos.redq", "algos.droq", "algos.d4pg", "algos.td3_bc", "algos.iql", "algos.cql", "algos.calql",
     "buffers", "buffers.protocols", "buffers.episodic_buffer", "buffers.prioritized_buffer", "buffers.nstep_buffer",
     "buffers.offline_dataset", "buffers.hindsight_buffer", "buffers.prior_buffer",
     "environment", "environment.protocols", "environment.make_env", "environment.synthetic_goal", "environment.normalized",

@@ -179,6 +179,9 @@ SIGNATURES = {
     "oprl_learner_update_calql": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P]),
     "oprl_learner_set_layernorm": (C.c_int, [_P, C.POINTER(OprlLayerNorm)]),
     "oprl_mlp_ln": (C.c_int, [C.POINTER(OprlNet), _P, _F, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "oprl_learner_set_dropout": (C.c_int, [_P, _F]),
+    "oprl_mlp_ln_drop": (C.c_int, [C.POINTER(OprlNet), _P, _F, _P, _I32, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _F, C.c_uint64, C.c_uint64]),
 }
 
 _lib = None

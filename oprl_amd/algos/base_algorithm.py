@@ -159,10 +159,17 @@ def check_prioritized_config(algo) -> None:
 
 def check_layer_norm_config(algo) -> None:
     """``layer_norm=True`` puts LayerNorm into the critics of SAC and REDQ on the exact-fp32 generic launch sequence of one
-    GPU: called by ``create()`` before anything touches the GPU."""
-    if not getattr(algo, "layer_norm", False):
-        return
+    GPU: called by ``create()`` before anything touches the GPU.  ``dropout`` (DroQ's
+    Linear -> Dropout -> LayerNorm -> ReLU, section 26) runs inside the LN kernels: a rate in [0, 1), and none without them."""
     name = type(algo).__name__
+    rate = getattr(algo, "dropout", 0.0)
+    if not 0.0 <= rate < 1.0:        # (NaN fails both)
+        raise ValueError(f"{name}(dropout={rate!r}): the rate must lie in [0, 1)")
+    if not getattr(algo, "layer_norm", False):
+        if rate > 0.0:
+            raise ValueError(f"{name}(dropout={rate!r}) needs layer_norm=True: dropout runs inside the LN kernels, in front of "
+                             "the normalisation (the DroQ block)")
+        return
     if algo.prioritized:
         raise ValueError(f"{name}(layer_norm=True, prioritized=True): the LN kernels take no importance weights "
                          "(prioritized replay with LayerNorm critics is not built)")
@@ -221,6 +228,7 @@ def check_nstep_gamma(algo, replay_buffer) -> None:
 
 IQL_STATE_KEYS = ("value", "value_m", "value_v", "value_step")
 LN_STATE_KEYS = ("critic_ln", "critic_ln_target", "critic_ln_m", "critic_ln_v")
+DROPOUT_STATE_KEY = "critic_dropout"     # the rate, only while the dropout mode is on (the masks follow the update count)
 
 
 def _rows_f32(obs) -> np.ndarray:
@@ -329,6 +337,7 @@ class HipLearner:
         self._value_mlp = None         # the value net of the implicit-Q-learning mode (set_iql) ...
         self._iql_on = False           # ... and whether the mode is on (the net and its moments are kept while it is off)
         self._ln = None                # the critics' LayerNorm holder (set_layernorm), or None
+        self._dropout = 0.0            # the critics' dropout rate (set_dropout); 0: off
         self._ptrs = self._snapshot_ptrs()
         h = C.c_void_p()
         with _capi.on_device(device):
@@ -405,6 +414,8 @@ class HipLearner:
                       value_v=self.value_v.cpu().clone(), value_step=int(n.value))
         if self._ln is not None:      # LayerNorm critics: the parameters, their target copy and both Adam moments
             sd.update({k: x.detach().cpu().clone() for k, x in zip(LN_STATE_KEYS, self._ln.tensors())})
+        if getattr(self, "_dropout", 0.0) > 0.0:
+            sd[DROPOUT_STATE_KEY] = float(self._dropout)
         return sd
 
     def load_state_dict(self, sd: dict[str, Any]) -> None:
@@ -431,6 +442,14 @@ class HipLearner:
                 raise ValueError(f"checkpoint has no {', '.join(missing)}: this learner's critics carry layer normalisation "
                                  "(layer_norm=True) and resume its parameters, target copy and Adam moments with the rest")
             pairs += [(x, sd[k]) for k, x in zip(LN_STATE_KEYS, self._ln.tensors())]
+        rate = getattr(self, "_dropout", 0.0)
+        if (DROPOUT_STATE_KEY in sd) != (rate > 0.0):
+            raise ValueError(f"checkpoint carries {DROPOUT_STATE_KEY}={sd[DROPOUT_STATE_KEY]!r} but this learner's critics have no dropout "
+                             "(dropout=0)" if rate == 0.0 else
+                             f"checkpoint has no {DROPOUT_STATE_KEY}: this learner's critics drop at rate {rate!r} (dropout > 0)")
+        if rate > 0.0 and float(np.float32(sd[DROPOUT_STATE_KEY])) != float(np.float32(rate)):
+            raise ValueError(f"checkpoint's {DROPOUT_STATE_KEY}={sd[DROPOUT_STATE_KEY]!r} is not this learner's rate {rate!r}: "
+                             "the masks of the updates to come would differ")
         for dst, src in pairs:
             if dst.shape != src.shape:
                 raise ValueError(f"checkpoint tensor shape {tuple(src.shape)} != {tuple(dst.shape)}")
@@ -665,6 +684,15 @@ class HipLearner:
             _capi.check(self.lib.oprl_learner_set_layernorm(self.handle, C.byref(d)), "oprl_learner_set_layernorm")
         self._ln = holder
         self._ptrs = self._snapshot_ptrs()      # the holder's tensors join the pointers check_bound() watches
+
+    def set_dropout(self, rate: float) -> None:
+        """Dropout in front of the critics' layer normalisation (oprl_learner_set_dropout; DroQ), in
+        every pass that evaluates a critic, from Philox masks addressed by the update count: nothing is stored and
+        ``state_dict()`` carries the rate alone (``critic_dropout``).  After ``set_layernorm``, once, before the first
+        update; rate 0, or one below 2^-32, leaves the mode off; a refused call leaves the learner as it was."""
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.oprl_learner_set_dropout(self.handle, float(rate)), "oprl_learner_set_dropout")
+        self._dropout = float(rate) if int(float(np.float32(rate)) * 2.0 ** 32) > 0 else 0.0
 
     def set_calql(self, on: bool) -> None:
         """The calibrated form of the CQL mode (oprl_learner_set_calql; Cal-QL): the penalty's

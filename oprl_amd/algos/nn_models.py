@@ -355,7 +355,9 @@ def attach_layer_norm(critic: nn.Module, holder: CriticLayerNorm, target: bool) 
 
 def _forward_sa_ln(mlp: "MLP", states: t.Tensor, actions: t.Tensor, ln, net: int) -> t.Tensor:
     """``mlp`` on [s | a] with LayerNorm between every hidden Linear and its ReLU, in torch on the tensors' device: what
-    the LN slice kernels compute (the critic modules' forward when LN is on; not a hot path)."""
+    the LN slice kernels compute (the critic modules' forward when LN is on; not a hot path).  It is the inference form:
+    a learner with ``dropout > 0`` drops inside its kernels in every training pass, this forward
+    never does."""
     holder, target = ln
     x = t.cat([states, actions], dim=-1)
     linears = [m for m in mlp.nn if isinstance(m, nn.Linear)]

@@ -69,6 +69,7 @@ class REDQ(Temperature, OffPolicyAlgorithm):
     no_fuse: bool = False         # (REDQ has no fused form: no effect)
     prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # f32 only: the learner refuses the others
+    dropout: float = 0.0          # Linear -> Dropout -> LayerNorm -> ReLU (DroQ): the rate in [0, 1), needs layer_norm=True
     layer_norm: bool = False      # Linear -> LayerNorm -> ReLU in the critics' hidden layers (RLPD / DroQ)
 
     actor: PolicyProtocol = field(init=False)
@@ -113,6 +114,8 @@ class REDQ(Temperature, OffPolicyAlgorithm):
             attach_layer_norm(self.critic, self.critic_ln, False)
             attach_layer_norm(self.critic_target, self.critic_ln, True)
             self.learner.set_layernorm(self.critic_ln)
+            if self.dropout > 0.0:
+                self.learner.set_dropout(self.dropout)
         self._created = True
         return self
 

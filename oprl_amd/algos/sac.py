@@ -37,6 +37,7 @@ class SAC(Temperature, OffPolicyAlgorithm):
     no_fuse: bool = False     # True: the generic per-net launch sequence instead of the fused kernels
     prioritized: bool = False      # train from a PrioritizedEpisodicReplayBuffer: importance-weighted critic loss, |TD| back as priorities (generic launch sequence, f32)
     precision: str = "f32"        # "f32": exact-fp32 MFMA (parity mode); "bf16": bf16 MFMA inputs, fp32 accumulate / master / Adam (include/oprl_amd.h)
+    dropout: float = 0.0          # Linear -> Dropout -> LayerNorm -> ReLU (DroQ): the rate in [0, 1), needs layer_norm=True
     layer_norm: bool = False      # Linear -> LayerNorm -> ReLU in the critics' hidden layers (RLPD / DroQ): generic launch sequence, f32
 
     actor: PolicyProtocol = field(init=False)
@@ -80,6 +81,8 @@ class SAC(Temperature, OffPolicyAlgorithm):
             attach_layer_norm(self.critic, self.critic_ln, False)
             attach_layer_norm(self.critic_target, self.critic_ln, True)
             self.learner.set_layernorm(self.critic_ln)
+            if self.dropout > 0.0:
+                self.learner.set_dropout(self.dropout)
         self._created = True
         return self
 

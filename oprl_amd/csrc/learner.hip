@@ -313,7 +313,8 @@ bool gauss_actor(const oprl_learner* h) {
   return h->cfg.algo == OPRL_SAC || h->cfg.algo == OPRL_TQC || h->cfg.algo == OPRL_REDQ;
 }
 
-// Philox key of noise stream `stream_id` (1: next-state draw / TD3 smoothing, 2: actor-step draw, 3: REDQ's target subset).
+// Philox key of noise stream `stream_id` (1: next-state draw / TD3 smoothing, 2: actor-step draw, 3: REDQ's target subset;
+// 4, 5: the CQL mode's draws; 6: the dropout masks of the LN critics, kDropStream).
 // Seed 0 on rank 0 is the bare stream constant; anything else is mixed in (splitmix64 finaliser).
 unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id) {
   uint64_t x = seed ^ ((uint64_t)rank * 0x9E3779B97F4A7C15ULL);

@@ -28,7 +28,14 @@ MlpArgs base_args(oprl_learner* h, const oprl_net& n, bool target, int B) {
     }
   }
   if (h->ln.on)                      // (a critic of a learner with LN: its view goes with the launch, net_rounds.hip)
-    for (int j = 0; j < h->nc; ++j) if (&n == &h->cfg.critics[j]) a.reserved = target ? &h->ln.target[j] : &h->ln.online[j];
+    for (int j = 0; j < h->nc; ++j) if (&n == &h->cfg.critics[j]) {
+      LnView& v = target ? h->ln.target[j] : h->ln.online[j];
+      if (v.drop_thresh != 0) {      // dropout: the key, and the stream T = (u 4 + k) 16 + j of this pass of critic j in this
+        v.drop_key = noise_key(h, kDropStream);        // update (a backward-only launch of the same phase draws the same)
+        v.drop_stream = ((unsigned long long)h->update_count * 4 + (target ? 0 : h->ln.drop_pass)) * 16 + j;
+      }
+      a.reserved = &v;
+    }
   a.B = B;
   a.action_dim = h->A;
   a.policy_noise = (float)h->cfg.hp.policy_noise;
@@ -226,6 +233,7 @@ int generic_critic_phase(oprl_learner* h, StepRows& rows, int B, const float* no
   const oprl_learner_config& c = h->cfg;
   const float *r = rows.cur.r, *d = rows.cur.d;
   RC(fresh32_tables(h, 3, st));      // (a PrecX2 learner's generic launches read the fp32 packs)
+  h->ln.drop_pass = 1;
   const int nc = h->nc, algo = c.algo;
   if (h->iql.on) return iql_critic_phase(h, rows, B, st);      // the implicit-Q-learning mode: its own sequence
   RC(next_action_step(h, rows, B, noise0, st));
@@ -346,6 +354,7 @@ static int const_action_grads(oprl_learner* h, const float* s, int B, int n_q, c
 int generic_actor_phase(oprl_learner* h, StepRows& rows, int B, const float* noise1, hipStream_t st) {
   const float* s = rows.cur.s;
   RC(fresh32_tables(h, 3, st));
+  h->ln.drop_pass = 2;
   const int algo = h->cfg.algo;
   const int n_q = (algo == OPRL_TD3 || algo == OPRL_DDPG || algo == OPRL_D4PG) ? 1 : h->nc;   // TD3 uses Q1 only
   // (the offers to the riding launches below never outlive this update: after an error return the next must not find one)

@@ -493,7 +493,8 @@ void set_adam(AdamScalars& ad, double lr, double beta1, double beta2, double eps
 int next_tp_tag(unsigned* counter, unsigned long long* xbuf, size_t xbuf_bytes, hipStream_t st, unsigned* out);
 const oprl_net& eff(const oprl_learner* h, const oprl_net& n);
 int check_device_error(const oprl_learner* h);
-unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id);      // Philox key of a noise stream (1 .. 3: the update's and REDQ's; 4, 5: the CQL mode's)
+unsigned long long noise_key(uint64_t seed, int rank, uint64_t stream_id);      // Philox key of a noise stream (1 .. 3: the update's and REDQ's; 4, 5: the CQL mode's; 6: the LN critics' dropout masks)
+constexpr uint64_t kDropStream = 6;
 inline unsigned long long noise_key(const oprl_learner* h, uint64_t stream_id) { return noise_key(h->noise_seed, h->noise_rank, stream_id); }
 void redq_subset(uint64_t seed, int rank, uint64_t counter, int n, int m, int* out);
 bool tp_generic(const oprl_learner* h, const oprl_net& n, int B);

@@ -65,9 +65,14 @@ struct CqlMode {
 // the caller's four arrays [nc][2 hidden layers][gamma | beta][256] (parameters, target copy, Adam m and v), eps, and one
 // allocation of its own, made when the mode is turned on — the zh rows [nc][2][Bmax][256] and rstd [nc][2][Bmax] a
 // forward-only launch leaves for the backward-only one | the per-slice dgamma / dbeta sums [nc][2][slices at Bmax][2][256].
-// online[j] / target[j]: critic j's views as MlpArgs::reserved carries them to the launchers (net_rounds.hip)
+// online[j] / target[j]: critic j's views as MlpArgs::reserved carries them to the launchers (net_rounds.hip).
+// Dropout in front of the normalisation (oprl_learner_set_dropout): drop_rate (0: off; the views hold the
+// key, threshold and scale), and drop_pass, the pass k of the stream T = (u 4 + k) 16 + j that base_args writes into a
+// view before each launch of critic j — 1 in the critic phase, 2 in the actor phase; a target critic's pass is 0
 struct LnMode {
   bool on = false;
+  float drop_rate = 0.f;
+  int drop_pass = 1;
   float *theta = nullptr, *theta_target = nullptr, *adam_m = nullptr, *adam_v = nullptr;
   float eps = 0.f;
   float* base = nullptr;

@@ -770,6 +770,36 @@ extern "C" int oprl_learner_set_layernorm(oprl_learner* h, const oprl_layernorm*
   return OPRL_OK;
 }
 
+// ---------------------------------------------------------------- dropout in the LN critics
+static bool drop_rate_ok(float rate) { return rate >= 0.f && rate < 1.f; }      // (NaN fails both)
+
+// a view's dropout fields but the pass's stream: threshold (uint32)(rate 2^32) (0: off), scale 1 / (1 - rate) in float32
+static void set_drop(LnView& v, float rate, uint64_t key) {
+  v.drop_thresh = (uint32_t)((double)rate * 4294967296.0);
+  v.drop_scale = v.drop_thresh != 0 ? 1.0f / (1.0f - rate) : 1.0f;
+  v.drop_key = v.drop_thresh != 0 ? key : 0;
+}
+
+// Linear -> Dropout -> LayerNorm -> ReLU in every critic pass of a learner whose LN mode is on: the views get the key of
+// threshold and the scale here, and the key of noise stream 6 and the pass's stream T before each launch (base_args).
+extern "C" int oprl_learner_set_dropout(oprl_learner* h, float rate) {
+  const char* who = "oprl_learner_set_dropout";
+  if (!h) { set_err("%s: null learner handle", who); return OPRL_ERR_INVALID; }
+  if (!drop_rate_ok(rate)) { set_err("%s: rate=%g must lie in [0, 1)", who, (double)rate); return OPRL_ERR_INVALID; }
+  LnMode& m = h->ln;
+  if (!m.on) { set_err("%s: the critics carry no layer normalisation (oprl_learner_set_layernorm comes first: dropout runs inside the LN kernels)", who); return OPRL_ERR_STATE; }
+  if (m.drop_rate > 0.f) { set_err("%s: the mode is already on (it is set once, before the first update)", who); return OPRL_ERR_STATE; }
+  if (h->update_count > 0) { set_err("%s: the learner has run %lld updates; the mode is set before the first", who, (long long)h->update_count); return OPRL_ERR_STATE; }
+  LnView probe;
+  memset((void*)&probe, 0, sizeof probe);
+  set_drop(probe, rate, 0);
+  if (probe.drop_thresh == 0) return OPRL_OK;      // (rate 0, or below 2^-32: the mode stays off)
+  m.drop_rate = rate;
+  // (the key follows the learner's seed, which may be set later: base_args writes it with the stream)
+  for (int j = 0; j < h->nc; ++j) { set_drop(m.online[j], rate, 0); set_drop(m.target[j], rate, 0); }
+  return OPRL_OK;
+}
+
 // k_ln_adam: every critic's per-slice dgamma / dbeta sums of this update's critic step, added in slice order, and the
 // Adam (+ Polyak when critic_targets_due) step with lr_critic at the step count of the critics' dW launch — which the
 // caller makes next and which commits the count (dw_commit)
@@ -790,10 +820,9 @@ int oprl_host::ln_adam_step(oprl_learner* h, int B, hipStream_t st) {
 // forward-only launch that keeps x, zh and rstd, then a backward-only launch that reloads them.  Row arrays hold `rows`
 // (>= B) rows per hidden layer: x / dz / zh [2][rows][256], rstd [2][rows]; dx1 [B][k1] the gradient over the x1 columns;
 // dln [2][2][256] the reduced dgamma | dbeta.  The kernel tests' entry point (tests/test_gpu_ln_slice.py).
-extern "C" int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1, int32_t k1,
-                           int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows, float* dz_rows,
-                           float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream) {
-  const char* who = "oprl_mlp_ln";
+static int mlp_ln_run(const char* who, const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1,
+                      int32_t k1, int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows, float* dz_rows,
+                      float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream, float rate, uint64_t key, uint64_t stream_id) {
   if (!net || !ln_theta || !x0 || !out || !x_rows || !zh_rows || !rstd_rows) { set_err("%s: null argument", who); return OPRL_ERR_INVALID; }
   if (dout != nullptr && (!dz_rows || !dln)) { set_err("%s: a backward (dout) needs dz_rows and dln", who); return OPRL_ERR_INVALID; }
   int width = 0;
@@ -803,12 +832,13 @@ extern "C" int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps
   if (k0 < 1 || k0 + (x1 ? k1 : 0) != net->dims[0] || (x1 && k1 < 1)) { set_err("%s: k0+k1=%d != input dim %d", who, k0 + (x1 ? k1 : 0), net->dims[0]); return OPRL_ERR_INVALID; }
   if (dx1 != nullptr && (!x1 || !dout || k1 > kNarrowMax)) { set_err("%s: dx1 needs x1 (k1 <= %d) and dout", who, kNarrowMax); return OPRL_ERR_INVALID; }
   if (!std::isfinite(eps) || !(eps > 0.f)) { set_err("%s: eps=%g must be finite and positive", who, (double)eps); return OPRL_ERR_INVALID; }
+  if (!drop_rate_ok(rate)) { set_err("%s: rate=%g must lie in [0, 1)", who, (double)rate); return OPRL_ERR_INVALID; }
   hipStream_t st = (hipStream_t)stream;
   HIPC(init_ln_attrs());
   RC(fresh32(net, st));
   const int slices = n_slices(B), nout = net->dims[net->n_layers];
   float* sums = nullptr;
-  if (dout != nullptr) RC(mode_block("oprl_mlp_ln", (size_t)kLnHidden * slices * 2 * kLnWidth * sizeof(float), (void**)&sums));
+  if (dout != nullptr) RC(mode_block(who, (size_t)kLnHidden * slices * 2 * kLnWidth * sizeof(float), (void**)&sums));
   MlpArgs a;
   memset(&a, 0, sizeof a);
   a.net = net_view(*net, false);
@@ -818,6 +848,8 @@ extern "C" int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps
   LnView v;
   memset((void*)&v, 0, sizeof v);
   v.gb = ln_theta; v.eps = eps;
+  set_drop(v, rate, key);
+  v.drop_stream = stream_id;       // (the backward-only launch below carries the forward launch's)
   for (int l = 0; l < kLnHidden; ++l) {
     a.Xg[l + 1] = x_rows + (size_t)l * rows * kLnWidth;
     if (dout != nullptr) a.dYg[l] = dz_rows + (size_t)l * rows * kLnWidth;
@@ -858,4 +890,21 @@ extern "C" int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps
   }
   HIPC(e);
   return OPRL_OK;
+}
+
+extern "C" int oprl_mlp_ln(const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1, int32_t k1,
+                           int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows, float* dz_rows,
+                           float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream) {
+  return mlp_ln_run("oprl_mlp_ln", net, ln_theta, eps, x0, k0, x1, k1, B, rows, split, dout, out, x_rows, dz_rows, zh_rows, rstd_rows,
+                    dx1, dln, stream, 0.f, 0, 0);
+}
+
+// oprl_mlp_ln with dropout in front of both normalisations: the mask of (key, stream_id), b the row's index
+// in the batch.  The kernel tests' entry point (tests/test_gpu_droq_slice.py).
+extern "C" int oprl_mlp_ln_drop(const oprl_net* net, const float* ln_theta, float eps, const float* x0, int32_t k0, const float* x1,
+                                int32_t k1, int32_t B, int32_t rows, int32_t split, const float* dout, float* out, float* x_rows,
+                                float* dz_rows, float* zh_rows, float* rstd_rows, float* dx1, float* dln, void* stream, float rate,
+                                uint64_t key, uint64_t stream_id) {
+  return mlp_ln_run("oprl_mlp_ln_drop", net, ln_theta, eps, x0, k0, x1, k1, B, rows, split, dout, out, x_rows, dz_rows, zh_rows,
+                    rstd_rows, dx1, dln, stream, rate, key, stream_id);
 }

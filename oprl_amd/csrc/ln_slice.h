@@ -7,6 +7,12 @@
 // and backward from g = dL/dn (ReLU-masked)
 //   dbeta += sum_b g;  dgamma += sum_b g zh;  gz = g gamma;  dz = rstd (gz - mean gz - zh mean(gz zh))
 // dz is what the dW tiles read as dYg[l], x_l what they read as Xg[l + 1]: k_dw_adam does not change.
+//
+// Dropout (DroQ's Linear -> Dropout -> LayerNorm -> ReLU) sits between z and the row pass:
+//   zd = keep(b, l, c) ? z scale : 0,  scale = 1 / (1 - rate) in float32;  the LayerNorm above is taken of zd,
+//   and the backward's dz (now dL/dzd) becomes dL/dz = keep ? dz scale : 0 before it is written.
+//   keep = philox4x32_10(ctr = (lo T, hi T, b, l 64 + c / 4), key = drop_key)[c % 4] >= drop_thresh
+// b is the row's index in the batch.  Nothing of the mask is stored: a backward regenerates it from the same (key, T).
 #pragma once
 #include "kernels.h"
 
@@ -25,7 +31,12 @@ struct LnView {
   float* sums;                    // [2][sum_slices][dgamma | dbeta][256] this launch's per-slice sums; null: none are
   int sum_slices;                 //   written (target nets, the actor phase's critic passes)
   float eps;
+  unsigned long long drop_key;    // dropout: the Philox key, and the pass's stream T (a backward-only launch carries the
+  unsigned long long drop_stream; //   T of the forward launch whose rows it reloads)
+  uint32_t drop_thresh;           // (uint32)(rate 2^32): a word below it drops its column; 0: no dropout, no Philox call
+  float drop_scale;               // 1 / (1 - rate)
 };
+static_assert(sizeof(LnView) == 80, "LnView's layout");
 
 struct MlpMultiLnArgs { MlpArgs a[kMaxMulti]; LnView v[kMaxMulti]; };
 static_assert(sizeof(MlpMultiLnArgs) <= 4096, "k_mlp_slice_multi_ln's argument block exceeds the 4 KB kernel-argument limit");

@@ -2,7 +2,9 @@
 //
 //   k_mlp_slice_ln<256>        k_mlp_slice (kernels.hip) with Linear -> LayerNorm -> ReLU hidden layers: the same GEMMs
 //                              (gemm_packed), head (slice_head), seeds (slice_seed) and input-gradient path; the hidden
-//                              GEMMs' epilogue stores z, and a row pass follows each of them
+//                              GEMMs' epilogue stores z, and a row pass follows each of them; with dropout
+//                              the row pass first masks and scales z from one Philox call per lane, the backward row
+//                              pass masks and scales dz from the same call
 //   k_mlp_slice_multi_ln<256>  its grid (slices, nets <= kMaxMulti) form
 //   k_ln_adam                  the per-slice dgamma / dbeta sums added in slice order + Adam + Polyak per element
 //
@@ -38,14 +40,34 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// The dropout mask of this lane's four columns 4 lane .. 4 lane + 3 of batch row brow in hidden layer l, as bits 0 .. 3
+// (set: kept).  One Philox call; it reads no memory, so the callers issue it in front of their LDS reads.
+__device__ __forceinline__ uint32_t drop_keep4(const LnView& V, int l, int brow, int lane) {
+  const u32x4 w = philox4x32_10(u32x4{(uint32_t)V.drop_stream, (uint32_t)(V.drop_stream >> 32), (uint32_t)brow, (uint32_t)(l * 64 + lane)},
+                                (uint32_t)V.drop_key, (uint32_t)(V.drop_key >> 32));
+  const uint32_t th = V.drop_thresh;
+  return (w.x >= th ? 1u : 0u) | (w.y >= th ? 2u : 0u) | (w.z >= th ? 4u : 0u) | (w.w >= th ? 8u : 0u);
+}
+
 // Forward row pass over Hs [kR][WL] holding z: x = relu(gamma zh + beta) in place, zh to Zs, rstd to rs[row].
+// With dropout (V.drop_thresh != 0, uniform over the launch's net) z becomes zd = keep ? z scale : 0 first.
 // The caller has made z visible (barrier); the next GEMM's own barrier makes x visible.
-__device__ __forceinline__ void ln_forward_rows(float* Hs, float* Zs, float* rs, const float* __restrict__ gb, float eps) {
+__device__ __forceinline__ void ln_forward_rows(float* Hs, float* Zs, float* rs, const LnView& V, int l, int row0) {
   constexpr int WL = lds_ld(kLnWidth);
   const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  const float* __restrict__ gb = V.gb + l * 2 * kLnWidth;
+  const float eps = V.eps;
+  const bool drop = __builtin_expect(V.drop_thresh != 0, 0);      // (off keeps the straight path)
+  uint32_t keep = 0;
+  if (drop) keep = drop_keep4(V, l, row0 + row, lane);
   const f32x4 gam = ld4(gb + 4 * lane), bet = ld4(gb + kLnWidth + 4 * lane);
   float* p = Hs + row * WL + 4 * lane;
-  const f32x4 z = ld4(p);
+  f32x4 z = ld4(p);
+  if (drop) {
+    const float scale = V.drop_scale;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) z[t] = (keep >> t) & 1u ? z[t] * scale : 0.f;
+  }
   const float mu = wave_sum((z[0] + z[1]) + (z[2] + z[3])) * (1.f / kLnWidth);
   const f32x4 d = z - mu;
   const float var = wave_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3])) * (1.f / kLnWidth);
@@ -61,11 +83,16 @@ __device__ __forceinline__ void ln_forward_rows(float* Hs, float* Zs, float* rs,
 
 // Backward row pass over Gs [kR][WL] holding g = dL/dn (masked): dz in place.  Before that the slice's column sums over
 // its `live` rows (< kR in the last slice of a ragged batch: rows >= B are never summed) go to sums [dgamma | dbeta][256].
+// With dropout the dz written is dL/dz = keep ? dz scale : 0, the mask regenerated from the forward's (key, T).
 // The caller has made g visible (barrier); contains the barrier between the column reads and the in-place writes.
-__device__ __forceinline__ void ln_backward_rows(float* Gs, const float* Zs, const float* rs, const float* __restrict__ gb,
+__device__ __forceinline__ void ln_backward_rows(float* Gs, const float* Zs, const float* rs, const LnView& V, int l, int row0,
                                                  float* __restrict__ sums, int live) {
   constexpr int WL = lds_ld(kLnWidth);
   const int lane = threadIdx.x & 63, row = threadIdx.x >> 6;
+  const float* __restrict__ gb = V.gb + l * 2 * kLnWidth;
+  const bool drop = __builtin_expect(V.drop_thresh != 0, 0);      // (off keeps the straight path)
+  uint32_t keep = 0;
+  if (drop) keep = drop_keep4(V, l, row0 + row, lane);
   const f32x4 gam = ld4(gb + 4 * lane);
   float* p = Gs + row * WL + 4 * lane;
   const f32x4 g = ld4(p), zh = ld4(Zs + row * WL + 4 * lane);
@@ -87,6 +114,11 @@ __device__ __forceinline__ void ln_backward_rows(float* Gs, const float* Zs, con
   f32x4 dz;
 #pragma unroll
   for (int t = 0; t < 4; ++t) dz[t] = rstd * ((gz[t] - m1) - zh[t] * m2);
+  if (drop) {
+    const float scale = V.drop_scale;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) dz[t] = (keep >> t) & 1u ? dz[t] * scale : 0.f;
+  }
   *reinterpret_cast<f32x4*>(p) = dz;
 }
 
@@ -119,11 +151,11 @@ __device__ __forceinline__ void mlp_slice_ln_body(const MlpArgs& A, const LnView
     gemm_packed(x0s, kX0Ld, net.pf[0], NTW, cdiv(net.dims[0], 16), scr, net.b[0], kLnWidth,
                 [&](int row, int col, float v) { hb[row * WL + col] = v; });
     __syncthreads();
-    ln_forward_rows(hb, zhS, rstdS, V.gb, V.eps);
+    ln_forward_rows(hb, zhS, rstdS, V, 0, row0);
     gemm_packed(hb, WL, net.pf[1], NTW, NTW, scr, net.b[1], kLnWidth,
                 [&](int row, int col, float v) { hb[HB + row * WL + col] = v; });
     __syncthreads();
-    ln_forward_rows(hb + HB, zhS + HB, rstdS + kR, V.gb + 2 * kLnWidth, V.eps);
+    ln_forward_rows(hb + HB, zhS + HB, rstdS + kR, V, 1, row0);
     gemm_packed(hb + HB, WL, net.pf[2], cdiv(Nout, 16), NTW, scr, net.b[2], Nout,
                 [&](int row, int col, float v) { outS[row * kOutLd + col] = col < Nout ? v : 0.f; });
     // (the narrow GEMM ended with a barrier: h, zh and rstd are complete)
@@ -160,7 +192,7 @@ __device__ __forceinline__ void mlp_slice_ln_body(const MlpArgs& A, const LnView
     });
     __syncthreads();
     float* sums = V.sums != nullptr ? V.sums + ((size_t)(l - 1) * V.sum_slices + blockIdx.x) * (2 * kLnWidth) : nullptr;
-    ln_backward_rows(dx, zhS + (l - 1) * HB, rstdS + (l - 1) * kR, V.gb + (l - 1) * 2 * kLnWidth, sums, live);
+    ln_backward_rows(dx, zhS + (l - 1) * HB, rstdS + (l - 1) * kR, V, l - 1, row0, sums, live);
     if (A.dYg[l - 1] != nullptr) {
       __syncthreads();
       store_rows4(dx, WL, A.dYg[l - 1], kLnWidth, kLnWidth, row0, B);

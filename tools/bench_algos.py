@@ -22,6 +22,7 @@ import torch as t
 from oprl_amd.algos.cql import CQL
 from oprl_amd.algos.d4pg import D4PG
 from oprl_amd.algos.ddpg import DDPG
+from oprl_amd.algos.droq import DroQ
 from oprl_amd.algos.iql import IQL
 from oprl_amd.algos.redq import REDQ
 from oprl_amd.algos.sac import SAC
@@ -45,7 +46,9 @@ CASES = [("DDPG walker B=256", DDPG, 24, 6, 256, {}),
          ("CQL walker N=10 B=256", CQL, 24, 6, 256, dict(log_every=10 ** 9)),      # (7936 wide rows in the critic step)
          ("SAC-walker B=256", SAC, 24, 6, 256, dict(log_every=10 ** 9)),           # (the fixed temperature, as CQL's default)
          ("SAC-LN walker B=256", SAC, 24, 6, 256, dict(log_every=10 ** 9, layer_norm=True)),      # (LayerNorm critics: the single-CU LN slice kernels)
-         ("REDQ-LN walker N=10 M=2 B=256", REDQ, 24, 6, 256, dict(log_every=10 ** 9, layer_norm=True))]
+         ("REDQ-LN walker N=10 M=2 B=256", REDQ, 24, 6, 256, dict(log_every=10 ** 9, layer_norm=True)),
+         ("REDQ-LN-drop walker N=10 M=2 p=0.01 B=256", REDQ, 24, 6, 256, dict(log_every=10 ** 9, layer_norm=True, dropout=0.01)),      # (dropout's cost over REDQ-LN)
+         ("DroQ walker N=2 M=2 p=0.01 B=256", DroQ, 24, 6, 256, dict(log_every=10 ** 9))]      # (two LN critics with dropout: one 2-net launch per round)
 PRECISIONS = ("f32", "bf16", "x2")
 
 
@@ -124,7 +127,7 @@ def main():
     for name, cls, S, A, B, kw in [(f"{c[0]} [{p}]", *c[1:5], dict(c[5], precision=p)) for c in CASES for p in precs]:
         if only and only not in name:
             continue
-        if (cls in (D4PG, TD3BC, IQL, CQL) or kw.get("layer_norm")) and kw["precision"] != "f32":
+        if (cls in (D4PG, TD3BC, IQL, CQL, DroQ) or kw.get("layer_norm")) and kw["precision"] != "f32":
             continue                    # (f32 only)
         b = Bench(name, cls, S, A, B, kw)
         for _rep in range(2):           # best of two passes (the first one still sees clock ramp-up)
