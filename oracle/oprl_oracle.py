@@ -292,10 +292,30 @@ class DDPGOracle:
                          g_critic=g_c, g_actor=g_a)
 
 
+class TwinCritics:
+    """What TD3 and SAC share: ``critic`` / ``critic_target`` hold q1's then q2's parameters (DoubleCritic.parameters()
+    order, one optimiser over both), and the critic step is the twin MSE against one y."""
+
+    def _q(self, params, j):
+        return params[:self.n1] if j == 0 else params[self.n1:]
+
+    def critic_step(self, s, a, y):
+        """The twin critics' MSE against y: one Adam step over both, and ``last`` anew."""
+        B = s.shape[0]
+        acts1 = q_forward(self._q(self.critic, 0), s, a)
+        acts2 = q_forward(self._q(self.critic, 1), s, a)
+        q1, q2 = acts1[-1], acts2[-1]
+        loss = ((q1 - y) ** 2).mean() + ((q2 - y) ** 2).mean()
+        g1, _ = mlp_backward(self._q(self.critic, 0), acts1, 2.0 * (q1 - y) / B)
+        g2, _ = mlp_backward(self._q(self.critic, 1), acts2, 2.0 * (q2 - y) / B)
+        self.opt_critic.step(self.critic, g1 + g2)
+        self.last = dict(q1=q1, q2=q2, y=y, critic_loss=loss, g_critic=g1 + g2)
+
+
 # --------------------------------------------------------------------------- #
 # TD3 (algos/td3.py:71-146)                                                   #
 # --------------------------------------------------------------------------- #
-class TD3Oracle:
+class TD3Oracle(TwinCritics):
     def __init__(self, state_dim, action_dim, actor, critic1, critic2, gamma=0.99,
                  tau=5e-3, lr_actor=3e-4, lr_critic=3e-4, policy_noise=0.2,
                  noise_clip=0.5, policy_freq=2, max_action=1.0):
@@ -313,37 +333,30 @@ class TD3Oracle:
         self.update_step = 0
         self.last: dict = {}
 
-    def _q(self, params, j):
-        return params[:self.n1] if j == 0 else params[self.n1:]
-
-    def update(self, s, a, r, d, s2, noise):
-        """noise: the N(0,1) draw of td3.py:98 (randn_like(action))."""
-        B = s.shape[0]
-        d = d.to(s.dtype)
-        acts1 = q_forward(self._q(self.critic, 0), s, a)
-        acts2 = q_forward(self._q(self.critic, 1), s, a)
-        q1, q2 = acts1[-1], acts2[-1]
+    def td_target(self, r, d, s2, noise):
         n = (noise * self.policy_noise).clamp(-self.noise_clip, self.noise_clip)
         a2 = (det_policy_forward(self.actor_target, s2)[0] + n).clamp(-self.max_action, self.max_action)
         q1n = q_forward(self._q(self.critic_target, 0), s2, a2)[-1]
         q2n = q_forward(self._q(self.critic_target, 1), s2, a2)[-1]
-        y = r + (1.0 - d) * self.gamma * t.min(q1n, q2n)
-        loss = ((q1 - y) ** 2).mean() + ((q2 - y) ** 2).mean()
-        g1, _ = mlp_backward(self._q(self.critic, 0), acts1, 2.0 * (q1 - y) / B)
-        g2, _ = mlp_backward(self._q(self.critic, 1), acts2, 2.0 * (q2 - y) / B)
-        self.opt_critic.step(self.critic, g1 + g2)
-        self.last = dict(q1=q1, q2=q2, y=y, critic_loss=loss, g_critic=g1 + g2)
+        return r + (1.0 - d) * self.gamma * t.min(q1n, q2n)
 
+    def actor_step(self, s):
+        B = s.shape[0]
+        pi, a_acts = det_policy_forward(self.actor, s)
+        c_acts = q_forward(self._q(self.critic, 0), s, pi)
+        self.last["actor_loss"] = -c_acts[-1].mean()
+        dqa = t.full_like(c_acts[-1], -1.0 / B)
+        _, dx = mlp_backward(self._q(self.critic, 0), c_acts, dqa, need_dx=True, need_dw=False)
+        du = dx[:, self.S:] * (1 - pi * pi)
+        g_a, _ = mlp_backward(self.actor, a_acts, du)
+        self.opt_actor.step(self.actor, g_a)
+        self.last["g_actor"] = g_a
+
+    def update(self, s, a, r, d, s2, noise):
+        """noise: the N(0,1) draw of td3.py:98 (randn_like(action))."""
+        self.critic_step(s, a, self.td_target(r, d.to(s.dtype), s2, noise))
         if self.update_step % self.policy_freq == 0:
-            pi, a_acts = det_policy_forward(self.actor, s)
-            c_acts = q_forward(self._q(self.critic, 0), s, pi)
-            self.last["actor_loss"] = -c_acts[-1].mean()
-            dqa = t.full_like(c_acts[-1], -1.0 / B)
-            _, dx = mlp_backward(self._q(self.critic, 0), c_acts, dqa, need_dx=True, need_dw=False)
-            du = dx[:, self.S:] * (1 - pi * pi)
-            g_a, _ = mlp_backward(self.actor, a_acts, du)
-            self.opt_actor.step(self.actor, g_a)
-            self.last["g_actor"] = g_a
+            self.actor_step(s)
             polyak(self.critic_target, self.critic, self.tau)
             polyak(self.actor_target, self.actor, self.tau)
         self.update_step += 1
@@ -352,7 +365,7 @@ class TD3Oracle:
 # --------------------------------------------------------------------------- #
 # SAC (algos/sac.py:75-155)                                                   #
 # --------------------------------------------------------------------------- #
-class SACOracle:
+class SACOracle(TwinCritics):
     def __init__(self, state_dim, action_dim, actor, critic1, critic2, gamma=0.99,
                  tau=5e-3, lr_actor=3e-4, lr_critic=3e-4, lr_alpha=1e-3,
                  alpha_init=0.2, tune_alpha=False):
@@ -373,25 +386,16 @@ class SACOracle:
         self.update_step = 0
         self.last: dict = {}
 
-    def _q(self, params, j):
-        return params[:self.n1] if j == 0 else params[self.n1:]
-
-    def update(self, s, a, r, d, s2, eps_next, eps_cur):
-        B = s.shape[0]
-        d = d.to(s.dtype)
-        acts1 = q_forward(self._q(self.critic, 0), s, a)
-        acts2 = q_forward(self._q(self.critic, 1), s, a)
-        q1, q2 = acts1[-1], acts2[-1]
+    def td_target(self, r, d, s2, eps_next):
         a2, logp2, _ = gaussian_forward(self.actor, s2, eps_next, self.A)
         q1n = q_forward(self._q(self.critic_target, 0), s2, a2)[-1]
         q2n = q_forward(self._q(self.critic_target, 1), s2, a2)[-1]
         q_next = t.min(q1n, q2n) - self.alpha * logp2
-        y = r + (1.0 - d) * self.gamma * q_next
-        loss = ((q1 - y) ** 2).mean() + ((q2 - y) ** 2).mean()
-        g1, _ = mlp_backward(self._q(self.critic, 0), acts1, 2.0 * (q1 - y) / B)
-        g2, _ = mlp_backward(self._q(self.critic, 1), acts2, 2.0 * (q2 - y) / B)
-        self.opt_critic.step(self.critic, g1 + g2)
+        return r + (1.0 - d) * self.gamma * q_next
 
+    def actor_step(self, s, eps_cur):
+        """Returns log pi of the sampled actions, which the temperature step reads."""
+        B = s.shape[0]
         pi, logp, cache = gaussian_forward(self.actor, s, eps_cur, self.A)
         c1 = q_forward(self._q(self.critic, 0), s, pi)
         c2 = q_forward(self._q(self.critic, 1), s, pi)
@@ -405,16 +409,21 @@ class SACOracle:
         dout = gaussian_backward_seed(cache, d_a, d_logp, self.A)
         g_a, _ = mlp_backward(self.actor, cache["acts"], dout)
         self.opt_actor.step(self.actor, g_a)
-        self.last = dict(q1=q1, q2=q2, y=y, critic_loss=loss, actor_loss=actor_loss,
-                         logp=logp, g_critic=g1 + g2, g_actor=g_a)
+        self.last.update(actor_loss=actor_loss, logp=logp, g_actor=g_a)
+        return logp
 
+    def temperature_step(self, logp):
+        g_alpha = -(self.target_entropy + logp.mean().to(t.float64))
+        la = [self.log_alpha.reshape(1)]
+        self.opt_alpha.step(la, [g_alpha.reshape(1)])
+        self.log_alpha = la[0].reshape(())
+        self.alpha = float(self.log_alpha.exp().item())
+
+    def update(self, s, a, r, d, s2, eps_next, eps_cur):
+        self.critic_step(s, a, self.td_target(r, d.to(s.dtype), s2, eps_next))
+        logp = self.actor_step(s, eps_cur)
         if self.tune_alpha:
-            g_alpha = -(self.target_entropy + logp.mean().to(t.float64))
-            la = [self.log_alpha.reshape(1)]
-            self.opt_alpha.step(la, [g_alpha.reshape(1)])
-            self.log_alpha = la[0].reshape(())
-            self.alpha = float(self.log_alpha.exp().item())
-
+            self.temperature_step(logp)
         polyak(self.critic_target, self.critic, self.tau)
         self.update_step += 1
 

@@ -90,10 +90,7 @@ class CQLOracle(orc.SACOracle):
 
     # ---- y, the wide rows and the log-densities from the nets as they stand
     def operands(self, s, a, r, d, s2, eps_next, eps, uni):
-        a2, logp2, _ = orc.gaussian_forward(self.actor, s2, eps_next, self.A)
-        q1n = orc.q_forward(self._q(self.critic_target, 0), s2, a2)[-1]
-        q2n = orc.q_forward(self._q(self.critic_target, 1), s2, a2)[-1]
-        y = r + ((1.0 - d) * self.gamma) * (t.min(q1n, q2n) - self.alpha * logp2)
+        y = self.td_target(r, d, s2, eps_next)
         raw_s, raw_s2 = orc.mlp_forward(self.actor, s)[-1], orc.mlp_forward(self.actor, s2)[-1]
         x, logd = sampled_actions(raw_s, raw_s2, eps, uni, self.A, self.N)
         ws, wa = wide_rows(s, a, x, s2 if self.at_next else None)
@@ -132,36 +129,16 @@ class CQLOracle(orc.SACOracle):
         cp = [x.clone().requires_grad_(True) for x in self.critic]
         return list(t.autograd.grad(self.critic_loss(cp, y, ws, wa, logd), cp))
 
+    def critic_step(self, s, a, y) -> None:
+        """SAC's critic step replaced: the penalised loss on the wide rows of ``update``'s draws."""
+        g_c, info = self.critic_grads(y, *self._wide)
+        self.opt_critic.step(self.critic, g_c)
+        self.last = dict(y=y, critic_loss=info["td1"] + info["td2"], penalty=self.cql_alpha * (info["gap1"] + info["gap2"]), **info)
+
     def update(self, s, a, r, d, s2, eps_next, eps_cur, eps, uni) -> None:
         s, a, r, d, s2, eps_next, eps_cur, eps, uni = (x.to(self.dtype) for x in (s, a, r, d, s2, eps_next, eps_cur, eps, uni))
-        B = s.shape[0]
-        y, ws, wa, logd = self.operands(s, a, r, d, s2, eps_next, eps, uni)
-        g_c, info = self.critic_grads(y, ws, wa, logd)
-        self.opt_critic.step(self.critic, g_c)
-
-        # SAC's actor step, temperature step and Polyak (SACOracle.update, oracle/oprl_oracle.py)
-        pi, logp, cache = orc.gaussian_forward(self.actor, s, eps_cur, self.A)
-        c1 = orc.q_forward(self._q(self.critic, 0), s, pi)
-        c2 = orc.q_forward(self._q(self.critic, 1), s, pi)
-        qa1, qa2 = c1[-1], c2[-1]
-        actor_loss = self.alpha * logp.mean() - t.min(qa1, qa2).mean()
-        w1 = (qa1 < qa2).to(qa1.dtype) + 0.5 * (qa1 == qa2).to(qa1.dtype)
-        _, dx1 = orc.mlp_backward(self._q(self.critic, 0), c1, -w1 / B, need_dx=True, need_dw=False)
-        _, dx2 = orc.mlp_backward(self._q(self.critic, 1), c2, -(1 - w1) / B, need_dx=True, need_dw=False)
-        d_a = dx1[:, self.S:] + dx2[:, self.S:]
-        dout = orc.gaussian_backward_seed(cache, d_a, t.full_like(logp, self.alpha / B), self.A)
-        g_a, _ = orc.mlp_backward(self.actor, cache["acts"], dout)
-        self.opt_actor.step(self.actor, g_a)
-        if self.tune_alpha:
-            g_alpha = -(self.target_entropy + logp.mean().to(t.float64))
-            la = [self.log_alpha.reshape(1)]
-            self.opt_alpha.step(la, [g_alpha.reshape(1)])
-            self.log_alpha = la[0].reshape(())
-            self.alpha = float(self.log_alpha.exp().item())
-        orc.polyak(self.critic_target, self.critic, self.tau)
-        self.last = dict(y=y, critic_loss=info["td1"] + info["td2"], actor_loss=actor_loss, logp=logp,
-                         penalty=self.cql_alpha * (info["gap1"] + info["gap2"]), **info)
-        self.update_step += 1
+        self._wide = self.operands(s, a, r, d, s2, eps_next, eps, uni)[1:]
+        super().update(s, a, r, d, s2, eps_next, eps_cur)
 
 
 # ---- the parity runs' fixture, shared by tests/test_cql_host.py (CPU) and tests/test_gpu_cql.py ------------------------------

@@ -14,15 +14,7 @@ from __future__ import annotations
 import torch as t
 
 from oracle import oprl_oracle as orc
-
-
-def mlp(p: list[t.Tensor], x: t.Tensor) -> t.Tensor:
-    n = len(p) // 2
-    for l in range(n):
-        x = x @ p[2 * l].t() + p[2 * l + 1]
-        if l < n - 1:
-            x = t.relu(x)
-    return x
+from tests.soft_oracle import cast, mlp
 
 
 def atoms(n_atoms: int, v_min: float, v_max: float, dtype=t.float64) -> t.Tensor:
@@ -65,10 +57,9 @@ class D4PGOracle:
     def __init__(self, S: int, A: int, actor: list[t.Tensor], critic: list[t.Tensor], n_atoms: int, v_min: float,
                  v_max: float, gamma=0.99, tau=5e-3, lr_actor=3e-4, lr_critic=3e-4, dtype=t.float64,
                  no_done: bool = False, skip_polyak: bool = False):
-        cp = lambda ps: [x.detach().to(dtype).clone() for x in ps]   # noqa: E731
         self.S, self.A = S, A
-        self.actor, self.actor_target = cp(actor), cp(actor)
-        self.critic, self.critic_target = cp(critic), cp(critic)
+        self.actor, self.actor_target = cast(actor, dtype), cast(actor, dtype)
+        self.critic, self.critic_target = cast(critic, dtype), cast(critic, dtype)
         self.v_min, self.v_max, self.gamma, self.tau = float(v_min), float(v_max), gamma, tau
         self.z = atoms(n_atoms, self.v_min, self.v_max, dtype)
         self.opt_actor, self.opt_critic = orc.Adam(lr_actor), orc.Adam(lr_critic)

@@ -91,7 +91,7 @@ def drop_mlp(p: list[t.Tensor], ln: t.Tensor, x: t.Tensor, keep: np.ndarray | No
 
 
 class DroQOracle(lno.LNOracle):
-    """``LNOracle`` whose every ``q`` evaluation knows (u, k, j).  ``LNOracle.update`` evaluates the critics in a fixed
+    """``LNOracle`` whose every ``q`` evaluation knows (u, k, j).  ``SoftOracle.update`` evaluates the critics in a fixed
     order — the M target critics of the subset, the N critics of the critic step, then (on an actor step) the N critics on
     (s, pi) — from which pass and critic index follow."""
 

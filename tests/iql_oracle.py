@@ -1,6 +1,6 @@
 """An implicit-Q-learning update in plain torch, written from the formulas of DESIGN.md §17 (Kostrikov et al. 2021, the
 deterministic-policy form), for tests/test_iql_host.py, tests/test_gpu_iql_seed.py and tests/test_gpu_iql.py.  It borrows
-the forward / backward helpers, Adam and Polyak of oracle/oprl_oracle.py and TD3Oracle's layout of the twin critics.
+the forward / backward helpers, Adam and Polyak of oracle/oprl_oracle.py and TD3Oracle's twin critics: layout and step.
 
 One update on rows (s, a, r, d, s'), in this order:
 
@@ -24,6 +24,7 @@ from __future__ import annotations
 import torch as t
 
 from oracle import oprl_oracle as orc
+from tests.soft_oracle import cast
 
 
 def seed_rows(q1, q2, v, pi, a, tau, beta, clip):
@@ -43,27 +44,23 @@ def seed_rows(q1, q2, v, pi, a, tau, beta, clip):
     return dict(u=u, seed=seed, w=w, da=da, omega=omega, sums=sums)
 
 
-class IQLOracle:
+class IQLOracle(orc.TwinCritics):
     def __init__(self, state_dim, action_dim, actor, critic1, critic2, value, expectile=0.7, beta=3.0, adv_clip=100.0,
                  gamma=0.99, tau=5e-3, lr_actor=3e-4, lr_critic=3e-4, lr_value=3e-4, dtype=t.float64,
                  sym: bool = False, late: bool = False, no_clip: bool = False):
-        cast = lambda ps: [x.detach().to(dtype).clone() for x in ps]   # noqa: E731
         self.S, self.A, self.dtype = state_dim, action_dim, dtype
         self.gamma, self.tau = gamma, tau
         self.expectile, self.beta, self.adv_clip = float(expectile), float(beta), float(adv_clip)
         self.sym, self.late, self.no_clip = sym, late, no_clip
-        self.actor = cast(actor)
-        self.actor_target = cast(actor)
-        self.critic = cast(critic1) + cast(critic2)        # one optimiser over q1 then q2, as TD3Oracle
-        self.critic_target = cast(self.critic)
+        self.actor = cast(actor, dtype)
+        self.actor_target = cast(actor, dtype)
+        self.critic = cast(critic1, dtype) + cast(critic2, dtype)      # one optimiser over q1 then q2, as TD3Oracle
+        self.critic_target = cast(self.critic, dtype)
         self.n1 = len(critic1)
-        self.value = cast(value)
+        self.value = cast(value, dtype)
         self.opt_actor, self.opt_critic, self.opt_value = orc.Adam(lr_actor), orc.Adam(lr_critic), orc.Adam(lr_value)
         self.update_step = 0
         self.last: dict = {}
-
-    def _q(self, params, j):
-        return params[:self.n1] if j == 0 else params[self.n1:]
 
     # ---- u, omega and the weights from the nets as they stand
     def advantage(self, s, a):
@@ -114,7 +111,6 @@ class IQLOracle:
 
     def update(self, s, a, r, d, s2) -> None:
         s, a, r, d, s2 = (x.to(self.dtype) for x in (s, a, r, d, s2))
-        B = s.shape[0]
         if not self.late:
             vn = orc.mlp_forward(self.value, s2)[-1]
         g_v, vinfo = self.value_grads(s, a)
@@ -123,17 +119,10 @@ class IQLOracle:
         if self.late:                                   # (the variant: everything read after V has moved)
             vn = orc.mlp_forward(self.value, s2)[-1]
             u = self.advantage(s, a)[1]
-        acts1 = orc.q_forward(self._q(self.critic, 0), s, a)
-        acts2 = orc.q_forward(self._q(self.critic, 1), s, a)
-        q1, q2 = acts1[-1], acts2[-1]
-        y = r + ((1.0 - d) * self.gamma) * vn
-        loss = ((q1 - y) ** 2).mean() + ((q2 - y) ** 2).mean()
-        g1, _ = orc.mlp_backward(self._q(self.critic, 0), acts1, 2.0 * (q1 - y) / B)
-        g2, _ = orc.mlp_backward(self._q(self.critic, 1), acts2, 2.0 * (q2 - y) / B)
-        self.opt_critic.step(self.critic, g1 + g2)
+        self.critic_step(s, a, r + ((1.0 - d) * self.gamma) * vn)      # (TD3's twin step, with y from V)
         g_a, ainfo = self.actor_grads(s, a, u)
         self.opt_actor.step(self.actor, g_a)
         orc.polyak(self.critic_target, self.critic, self.tau)
         orc.polyak(self.actor_target, self.actor, self.tau)
-        self.last = dict(q1=q1, q2=q2, y=y, critic_loss=loss, q_mean=(q1.mean() + q2.mean()) / 2, **vinfo, **ainfo)
+        self.last.update(q_mean=(self.last["q1"].mean() + self.last["q2"].mean()) / 2, **vinfo, **ainfo)
         self.update_step += 1

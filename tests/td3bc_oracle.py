@@ -16,32 +16,15 @@ from __future__ import annotations
 import torch as t
 
 from oracle import oprl_oracle as orc
+from tests.soft_oracle import cast
 
 
 class TD3BCOracle(orc.TD3Oracle):
     def __init__(self, state_dim, action_dim, actor, critic1, critic2, bc_alpha=2.5, dtype=t.float64,
                  no_bc: bool = False, no_lambda: bool = False, **kw):
-        cast = lambda ps: [x.detach().to(dtype).clone() for x in ps]   # noqa: E731
-        super().__init__(state_dim, action_dim, cast(actor), cast(critic1), cast(critic2), **kw)
+        super().__init__(state_dim, action_dim, cast(actor, dtype), cast(critic1, dtype), cast(critic2, dtype), **kw)
         self.bc_alpha, self.dtype = float(bc_alpha), dtype
         self.no_bc, self.no_lambda = no_bc, no_lambda
-
-    # ---- the critic step: TD3's (oracle/oprl_oracle.py TD3Oracle.update, first half)
-    def critic_step(self, s, a, r, d, s2, noise) -> None:
-        B = s.shape[0]
-        acts1 = orc.q_forward(self._q(self.critic, 0), s, a)
-        acts2 = orc.q_forward(self._q(self.critic, 1), s, a)
-        q1, q2 = acts1[-1], acts2[-1]
-        n = (noise * self.policy_noise).clamp(-self.noise_clip, self.noise_clip)
-        a2 = (orc.det_policy_forward(self.actor_target, s2)[0] + n).clamp(-self.max_action, self.max_action)
-        q1n = orc.q_forward(self._q(self.critic_target, 0), s2, a2)[-1]
-        q2n = orc.q_forward(self._q(self.critic_target, 1), s2, a2)[-1]
-        y = r + (1.0 - d) * self.gamma * t.min(q1n, q2n)
-        loss = ((q1 - y) ** 2).mean() + ((q2 - y) ** 2).mean()
-        g1, _ = orc.mlp_backward(self._q(self.critic, 0), acts1, 2.0 * (q1 - y) / B)
-        g2, _ = orc.mlp_backward(self._q(self.critic, 1), acts2, 2.0 * (q2 - y) / B)
-        self.opt_critic.step(self.critic, g1 + g2)
-        self.last = dict(q1=q1, q2=q2, y=y, critic_loss=loss)
 
     # ---- the actor step's gradient, by hand
     def actor_grads(self, s, a):
@@ -72,7 +55,7 @@ class TD3BCOracle(orc.TD3Oracle):
 
     def update(self, s, a, r, d, s2, noise) -> None:
         s, a, r, d, s2, noise = (x.to(self.dtype) for x in (s, a, r, d, s2, noise))
-        self.critic_step(s, a, r, d, s2, noise)
+        self.critic_step(s, a, self.td_target(r, d, s2, noise))
         if self.update_step % self.policy_freq == 0:
             g_a, info = self.actor_grads(s, a)
             self.opt_actor.step(self.actor, g_a)
